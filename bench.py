@@ -39,6 +39,13 @@ roofline: the binding resource of the dominant kernel (ft_slices for config
 (profiles/counters.json, tools/profile_round.sh + tools/roofline.py): VALU
 issue, LDS-array busy and bytes past L2, each over the kernel's live time
 measured here with HIP events on its launch stream; `frac` = the largest.
+
+A plain run sets up, settles, warms up, times --steps steps, writes the outputs
+of the last timed step under --dump-outputs DIR (if given) and prints the result
+line.  Everything else (CPU baselines and the parity spot checks against them,
+the host-buffer entry points, the results gathered to one host buffer, the
+plan / stack kernel times from a pass of their own, each net alone, the extra
+config-3 / engine-actor / move-work lines) runs only with --full.
 """
 from __future__ import annotations
 
@@ -96,11 +103,21 @@ def parse_args():
                     help="with --small-net on groups: two evaluation calls per step instead of one "
                          "fnnue_eval_groups_dual_device call (A/B)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-seconds", type=float, default=3.0, help="wall budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: CPU baseline and parity spot "
+                         "checks, host-buffer entry points, gathered results, plan / stack kernel times (a pass of "
+                         "their own), each net alone, and on the default workload the extra config-3 / engine-actor "
+                         "/ move-work lines (trim with the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; at most 64 MB in all, "
+                         "a fixed seeded sample of larger outputs); the inputs are seeded, so two builds can be "
+                         "compared output for output")
+    ap.add_argument("--cpu-seconds", type=float, default=3.0, help="--full: wall budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default run: skip the extra config-3 and engine-actor lines appended after the headline")
-    ap.add_argument("--no-host-api", action="store_true", help="skip timing the host-buffer entry points")
+                    help="--full on the default workload: skip the extra config-3 and engine-actor lines appended "
+                         "after the headline")
+    ap.add_argument("--no-host-api", action="store_true", help="--full: skip timing the host-buffer entry points")
     ap.add_argument("--kernel-events", choices=["ft", "all"], default="ft",
                     help="HIP events in the timed steps: around the FT main kernel only (default), or around every "
                          "phase (plan / FT / stacks; each event record costs the stream a few microseconds)")
@@ -199,6 +216,28 @@ def resource_fractions(c: dict, t_s: float) -> dict:
         v["frac"] = round(v["achieved"] / v["peak"], 4)
         v["achieved"] = round(v["achieved"], 1) if v["unit"] == "GB/s" else float(f"{v['achieved']:.4g}")
     return fr
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> dict:
+    """Write each array as dirpath/<name>.npy in float64 (exact for the int32
+    results).  Past 64 MB in all, every array is cut to an equal share of the
+    budget by a fixed seeded sample of its elements (sorted indices, the same
+    from run to run)."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 8
+    share = (DUMP_BUDGET_BYTES - 1024 * len(arrays)) // 8 // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        n = a.size
+        if total > DUMP_BUDGET_BYTES and n > share:
+            a = a[np.sort(np.random.default_rng(0).choice(n, size=share, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a.astype(np.float64))
+        written[name] = {"elements": int(a.size), "of": int(n)}
+    return written
 
 
 class Shard:
@@ -427,11 +466,17 @@ def backend_line(args) -> dict:
     compact_same = bool(np.array_equal(off[:kmax + 1], off_c[:kmax + 1]) and all(
         (cout[i].psqt, cout[i].positional) == (out[i].psqt, out[i].positional) for i in range(0, nres, 97)) and all(
         cout[i].score == out[i].score for i in range(0, nres, 97)))
-    # results of the last (largest) call: parity spot check + CPU baseline on the chess batches
-    got_ps = np.array([out[i].psqt for i in range(int(off[kmax]))], dtype=np.int32)
-    got_po = np.array([out[i].positional for i in range(int(off[kmax]))], dtype=np.int32)
-    cpu = parity = None
-    if not args.no_cpu_baseline:
+    # results of the last (largest) call: dumped, and under --full the parity spot check + CPU baseline on the
+    # chess batches
+    cpu = parity = dumped = None
+    baseline = args.full and not args.no_cpu_baseline
+    if baseline or args.dump_outputs:
+        got_ps = np.array([out[i].psqt for i in range(nres)], dtype=np.int32)
+        got_po = np.array([out[i].positional for i in range(nres)], dtype=np.int32)
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"psqt": got_ps, "positional": got_po,
+                                                  "offsets": off[:kmax + 1].astype(np.int64)})
+    if baseline:
         from oracle.oracle import OracleNet  # cpu_baseline leg (test infrastructure)
         from oracle.oracle import lib as olib
         chess = [i for i in range(kmax) if bodies[i].variant in ("standard", "chess960")]
@@ -476,7 +521,10 @@ def backend_line(args) -> dict:
         "roofline": backend_roofline(sizes),
         "cpu_baseline": cpu, "parity_spot_check": parity,
         "setup_s": {"net": round(t_net, 2), "inputs": round(t_gen, 2)},
+        "full": bool(args.full),
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     del keep
     return line
 
@@ -727,9 +775,22 @@ def run(args) -> dict | None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     step_ms = [round(a.elapsed_time(b), 4) for a, b in step_events] if step_events is not None else None
+    # ---- results of the last timed step to the host (outside the timed region) ----
+    psqt = shards[0].psqt.cpu().numpy()
+    positional = shards[0].positional.cpu().numpy()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"psqt": np.concatenate([psqt] + [s.psqt.cpu().numpy() for s in shards[1:]]),
+                  "positional": np.concatenate([positional] + [s.positional.cpu().numpy() for s in shards[1:]])}
+        if args.small_net:
+            arrays["small_psqt"] = np.concatenate([s.small[0].cpu().numpy() for s in shards])
+            arrays["small_positional"] = np.concatenate([s.small[1].cpu().numpy() for s in shards])
+        dumped = dump_outputs(args.dump_outputs, arrays)
     launches, plan_ms, ft_ms, stack_ms = evs[0][0].timing_phases()
     small_t = evs[1][0].timing_phases() if len(evs) > 1 else None
-    if ft_only:
+    # plan and stack kernel times: from the timed steps with --kernel-events all, else from a pass of their own (--full)
+    phases_measured = args.full or not ft_only
+    if ft_only and args.full:
         for ctxs in evs:
             ctxs[0].set_timing(True)
         for _ in range(min(args.steps, 50)):
@@ -750,7 +811,7 @@ def run(args) -> dict | None:
     # per-net costs come from these passes, the two-net step from the timed
     # steps above.
     nets_alone = None
-    if len(evs) > 1 and launch == "single":
+    if len(evs) > 1 and launch == "single" and args.full:
         nets_alone = []
         m = max(5, min(args.steps, 50))
         for k in range(len(evs)):
@@ -793,11 +854,11 @@ def run(args) -> dict | None:
     plan_avg, ft_avg, stack_avg = plan_ms / L, ft_ms / L, stack_ms / L
     bytes_per_launch = float(rows.sum()) * (2 * args.hd + 4 * PSQT_BUCKETS) + npos * (36 + 8)
 
-    # ---- results of device 0 to the host (outside the timed region) ----
-    psqt = shards[0].psqt.cpu().numpy()
-    positional = shards[0].positional.cpu().numpy()
+    # ---- every shard's results gathered to one host (--full; outside the timed region) ----
     gathered = None
-    if dist_on:
+    if not args.full:
+        pass
+    elif dist_on:
         # evals gathered back to rank 0 over RCCL (north star "evals are gathered back"), timed on its own
         dev = torch.device("cuda", local)
         dist.barrier()
@@ -830,22 +891,27 @@ def run(args) -> dict | None:
                     "how": "one process: D2H of every device's shard into disjoint slices of pinned host buffers"}
     small = None
     if args.small_net and rank == 0:
+        l2, p2, f2, s2 = small_t
+        small = {"hd": args.small_net, "plan_avg_ms": round(p2 / max(l2, 1), 4) if phases_measured else None,
+                 "ft_kernel_avg_ms": round(f2 / max(l2, 1), 4),
+                 "stack_kernel_avg_ms": round(s2 / max(l2, 1), 4) if phases_measured else None,
+                 "parity_spot_check": None}
+    if small is not None and args.full:
         # parity of the small net on a bounded sample against the oracle (test infrastructure)
         from oracle.oracle import OracleNet
         on2 = OracleNet(F.synthesize_net(args.seed + 1000, args.small_net, 0))
         k = min(npos, 200_000)
         ps2, po2, rc2 = on2.simd_eval_packed(pos[:k], threads=threads)
         g2 = shards[0].small[:, :k].cpu().numpy()
-        l2, p2, f2, s2 = small_t
-        small = {"hd": args.small_net, "plan_avg_ms": round(p2 / max(l2, 1), 4),
-                 "ft_kernel_avg_ms": round(f2 / max(l2, 1), 4), "stack_kernel_avg_ms": round(s2 / max(l2, 1), 4),
-                 "parity_spot_check": {"checked": k, "mismatches": int(((g2[0] != ps2) | (g2[1] != po2)).sum())
-                                       if rc2 == 0 else None}}
+        small["parity_spot_check"] = {"checked": k, "mismatches": int(((g2[0] != ps2) | (g2[1] != po2)).sum())
+                                      if rc2 == 0 else None}
 
     cpu, parity = None, None
     # The CPU baseline at every N (rank 0 / device 0's shard, same host cores):
-    # it doubles as the parity spot check of that shard.
-    if rank == 0 and not args.no_cpu_baseline and variant is not None:
+    # it doubles as the parity spot check of that shard.  (--full)
+    if not args.full:
+        pass
+    elif rank == 0 and not args.no_cpu_baseline and variant is not None:
         from oracle.oracle import VariantOracleNet  # cpu_baseline leg: the scalar C restatement is the CPU port
         on = VariantOracleNet(F.synthesize_variant_net(args.seed, args.hd, variant), variant)
         done, mism, t0 = 0, 0, time.perf_counter()
@@ -921,7 +987,7 @@ def run(args) -> dict | None:
     # The host-buffer entry points (host arrays in and out over PCIe, validity
     # checked on the device) — reported beside `value`, never as it.
     host_api = None
-    if not dist_on and not args.no_host_api:
+    if args.full and not dist_on and not args.no_host_api:
         reps = 3
         hpos = pos if launch != "devices" else np.concatenate([pos] * len(devices))
         hoff = off
@@ -961,7 +1027,7 @@ def run(args) -> dict | None:
         tree_ok = db.get("tree") == tree_hash()
     kernels = {}
     for name, t_ms in ((main_k, ft_avg), ("stack_kernel", stack_avg)):
-        rec = {"live_avg_ms": round(t_ms, 4)}
+        rec = {"live_avg_ms": round(t_ms, 4) if name == main_k or phases_measured else None}
         c = (counters or {}).get(name, {}).get("counters")
         if c and t_ms > 0:
             rec["fractions"] = resource_fractions(c, t_ms * 1e-3)
@@ -984,8 +1050,9 @@ def run(args) -> dict | None:
         roofline.update(bound=bound, achieved=b["achieved"], peak=b["peak"], unit=b["unit"], frac=b["frac"],
                         traffic=int(fr["hbm"]["bytes"]) if "hbm" in fr else None)
     roofline.update({
-        "kernel": main_k, "kernel_avg_ms": round(ft_avg, 4), "plan_avg_ms": round(plan_avg, 4),
-        "stack_kernel_avg_ms": round(stack_avg, 4), "kernels": kernels,
+        "kernel": main_k, "kernel_avg_ms": round(ft_avg, 4),
+        "plan_avg_ms": round(plan_avg, 4) if phases_measured else None,
+        "stack_kernel_avg_ms": round(stack_avg, 4) if phases_measured else None, "kernels": kernels,
         "gather_equivalent_GBps": round(bytes_per_launch / (ft_avg * 1e-3) / 1e9, 1) if ft_avg > 0 else None,
         "algorithmic_bytes_per_launch": int(bytes_per_launch),
         "counters": {"source": src, "tree_matches": tree_ok},
@@ -1051,7 +1118,10 @@ def run(args) -> dict | None:
             "small_net": small,
             "setup_s": {"net": round(t_net, 2), "inputs": round(t_gen, 2)},
             "settle": settle,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if nets_alone is not None:
             out["nets_alone"] = nets_alone
         if step_ms is not None:
@@ -1112,7 +1182,7 @@ def move_work_line(args) -> dict:
 
 
 def extra_lines(args) -> dict:
-    """The default run's extra workloads, measured after
+    """The default run's extra workloads under --full, measured after
     the headline and outside its timed steps: BASELINE config 3 with the big +
     small net through the dual call (20 steps), the engine actor at 1 / 64 /
     1024 acquired batches per go(), and its move work at 1 / 8 move batches;
@@ -1122,6 +1192,7 @@ def extra_lines(args) -> dict:
     a3 = argparse.Namespace(**vars(args))
     a3.workload, a3.games, a3.small_net, a3.no_dual = "games", 10_000, 128, False
     a3.steps, a3.warmup, a3.cpu_seconds, a3.no_host_api = 20, 3, 1.0, True
+    a3.full, a3.dump_outputs = True, None
     o = run(a3)
     r = o["roofline"]
     extra["config3_big_small"] = {
@@ -1137,6 +1208,7 @@ def extra_lines(args) -> dict:
     ab = argparse.Namespace(**vars(args))
     ab.workload, ab.go_batches, ab.go_seconds, ab.go_calls = "backend", "1,64,1024", 0.3, 0
     ab.steps, ab.warmup, ab.cpu_seconds = 1000, 3, 1.0
+    ab.full, ab.dump_outputs = True, None
     o = backend_line(ab)
     extra["actor"] = {"workload": o["config"]["workload"], "per_batches": [
         {k: row[k] for k in ("batches_per_go", "positions_per_go", "calls", "ms_per_go_median", "ms_per_go_mean",
@@ -1160,7 +1232,7 @@ def main():
     out = run(args)
     if out is None:
         return
-    if default_run and not args.no_extra:
+    if default_run and args.full and not args.no_extra:
         out["extra"] = extra_lines(args)
     print(json.dumps(out), flush=True)
 

@@ -8,7 +8,7 @@ set -uo pipefail
 tag=$1
 out=gpurun_out/$tag
 mkdir -p "$out"
-timeout -k 10 400 python bench.py --workload backend > "$out/bench_backend.log" 2>&1 || { tail -5 "$out/bench_backend.log"; exit 1; }
+timeout -k 10 400 python bench.py --full --workload backend > "$out/bench_backend.log" 2>&1 || { tail -5 "$out/bench_backend.log"; exit 1; }
 grep '^{' "$out/bench_backend.log" | tail -1 > "$out/bench_backend.json"
 bash tools/backend_trace.sh "$tag" 1,1024 40 || exit 1
 T=gpurun_out/btrace_$tag/trace

@@ -10,7 +10,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     for v in main "$@"; do
       lib=$PWD/exp/libfnnue_$v.so; [ $v = main ] && lib=$PWD/fishnet_amd/libfnnue.so
       log=gpurun_out/exp/${v}_${wl}_$r.log
-      FNNUE_LIB=$lib timeout -k 10 300 python bench.py --workload $wl --steps ${STEPS:-100} --cpu-seconds 1 \
+      FNNUE_LIB=$lib timeout -k 10 300 python bench.py --full --workload $wl --steps ${STEPS:-100} --cpu-seconds 1 \
         --no-host-api ${BENCH_ARGS:-} > $log 2>&1
       rc=$?
       python3 - "$v" "$wl" "$rc" "$log" <<'PY'

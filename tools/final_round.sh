@@ -45,7 +45,7 @@ has bench || exit 0
 cp profiles/counters.json "$out/counters.json"
 b() {  # b <name> <bench args...>
   local name=$1; shift
-  step "bench_$name" 400 python bench.py --steps 200 "$@"
+  step "bench_$name" 400 python bench.py --full --steps 200 "$@"
   grep '^{' "$out/bench_$name.log" | tail -1 > "$out/bench_$name.json"
 }
 b positions

@@ -17,7 +17,7 @@ for st in $STEPS; do
       tail -1 $O/smoke.log ;;
     positions|games|children|crazyhouse|atomic|crazyhouse-games|atomic-games|devices)
       a="--workload $st"; [ $st = devices ] && a="--launch devices --gpus 1"
-      timeout -k 10 400 python bench.py $a $BENCH_ARGS > $O/bench_$st.json 2> $O/bench_$st.err \
+      timeout -k 10 400 python bench.py --full $a $BENCH_ARGS > $O/bench_$st.json 2> $O/bench_$st.err \
         || { echo "bench $st rc=$?"; tail -20 $O/bench_$st.err; exit 1; }
       python -c "import json;d=json.load(open('$O/bench_$st.json'));r=d['roofline'];print('$st', d['config']['positions_per_gpu'], round(d['value']/1e6,1), round(d['ms_per_step'],3), r['frac'], r['bound'], r['plan_avg_ms'], r['kernel_avg_ms'], r['stack_kernel_avg_ms'], round((d['cpu_baseline'] or {}).get('value',0)/1e6,2), d['parity_spot_check'], (d['gathered'] or {}).get('gather_ms'))" ;;
     *) echo "unknown step $st"; exit 2 ;;
