@@ -15,7 +15,8 @@
 //   plan_count    per-workgroup LDS histograms of item keys (kb, n) and of
 //                 position buckets -> global counts
 //   plan_scan     one workgroup: exclusive scans -> item / slot offsets, and
-//                 the unit table (kb, item range of <= kUnitItems)
+//                 the unit table (kb, item range): units of equal work per
+//                 king block, ordered for the XCDs (slice_units.h)
 //   plan_scatter  counting-sort scatter: per item its 32 feature rows (u16,
 //                 relative to kb, padded with the zero row) and its output
 //                 slot; positions re-ordered by layer-stack bucket; PSQT term
@@ -313,7 +314,8 @@ size_t sliced_tiles_bytes(uint32_t hd) { return tile_uint4_count(hd) * sizeof(ui
 // a multiple of 4 words: hipMemsetAsync of a size that is not a multiple of
 // 16 bytes runs two fill kernels
 size_t sliced_ctr_words() { return (3 * kBins + 16 + 3) & ~(size_t)3; }
-uint32_t sliced_max_units(uint32_t chunk) { return 32 + (2 * chunk + kUnitItems - 1) / kUnitItems; }
+// two items per position over 32 king blocks (the bound is proved at slice_max_units)
+uint32_t sliced_max_units(uint32_t chunk) { return slice_max_units(2 * chunk, 32); }
 
 #define FNNUE_HD_DISPATCH(hd, CALL) \
   switch (hd) {                     \
@@ -345,7 +347,7 @@ hipError_t launch_sliced_plan(const fnnue_pos* pos, uint32_t n, const SlicedPlan
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL(plan_count_kernel, dim3(blocks), dim3(1024), 0, stream, pos, n, P.ctr, err);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(plan_scan_kernel_t<32>, dim3(1), dim3(1024), 0, stream, P.ctr, (int4*)P.units, (uint32_t)kUnitItems);
+  hipLaunchKernelGGL(plan_scan_kernel_t<32>, dim3(1), dim3(1024), 0, stream, P.ctr, (int4*)P.units, kUnitWork);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(plan_scatter_kernel, dim3((n + kScatterPositions - 1) / kScatterPositions), dim3(kScatterPositions), 0, stream,
                      pos, n, P.ctr, P.items, P.flist, P.perm, bucket, psqt);

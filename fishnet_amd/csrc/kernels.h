@@ -42,7 +42,9 @@ hipError_t launch_stack(uint32_t hd, const uint8_t* x, const uint8_t* bucket, ui
                         hipStream_t stream);
 
 // LDS-stationary feature transformer (ft_sliced.hip).
-// Perspective-items per (king block) work unit: 48 passes of 128 items.
+// Chess plans cut units by work (slice_units.h, FT_UNIT_WORK); FT_UNIT_ITEMS is
+// the fixed unit of the variant plans (variant.hip) and was the chess unit:
+// perspective-items per (king block) work unit: 48 passes of 128 items.
 // Measured on config 2 (1M positions): 4096 595-600M, 5120 586-592M, 6144
 // 603-613M, 7168 594-599M, 8192 592-597M positions/s (crazyhouse: neutral).
 // Must stay a multiple of 128 (a pass step) so pass items 2k / 2k + 1 keep

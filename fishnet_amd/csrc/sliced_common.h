@@ -8,6 +8,7 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "net.h"
+#include "slice_units.h"
 
 namespace fnnue {
 namespace {
@@ -201,22 +202,22 @@ __host__ __device__ constexpr uint32_t seg_count_class(uint32_t nfeat) {
   return C == 1 ? 0u : nfeat > 29 ? 3u : nfeat > 25 ? 2u : nfeat > 20 ? 1u : 0u;
 }
 
-// One workgroup of 1024 threads.  unit_items = 0: segment units (see
-// seg_plies of work) instead of fixed-size ones.  KB king blocks (32: chess; 64:
+// One workgroup of 1024 threads.  unit_work = 0: segment units (see
+// seg_plies of work) instead of the ft_slices units of unit_work each.  KB king blocks (32: chess; 64:
 // the variant feature sets), counters laid out as KB * NB item bins + 9
 // position bins, then offsets, cursors and the unit count (kCnt / kOff / kCur
 // / kNUnits for KB = 32, kV* for 64, SegCtr for segments).  NB = 33: bin =
-// list length (fixed-size units); NB = 33 C: bin = C * length bin + class.
+// list length (ft_slices units); NB = 33 C: bin = C * length bin + class.
 // The body runs in any 1024-thread workgroup (plan_scan_kernel_t, or a phase of
 // the one-workgroup segment plan) on LDS the caller provides:
 // plan_scan_lds_words<KB, NB>() words.
 template <int KB, int NB>
 __host__ __device__ constexpr int plan_scan_lds_words() {
-  return (KB * NB + kPosBins) + 16 + KB * NB + KB + 1;
+  return (KB * NB + kPosBins) + 16 + KB * NB + KB + 1 + 2 * KB;
 }
 template <int KB, int NB = 33>
 __device__ __forceinline__ void plan_scan_body(uint32_t* __restrict__ ctr, int4* __restrict__ units,
-                                               uint32_t unit_items, uint32_t seg_plies, uint32_t* __restrict__ nu_out,
+                                               uint32_t unit_work, uint32_t seg_plies, uint32_t* __restrict__ nu_out,
                                                uint32_t* __restrict__ lds) {
   constexpr int kIB = KB * NB, kB = kIB + kPosBins, kO = kB, kC = 2 * kB, kNU = 3 * kB;
   auto len_bin = [](int i) { return (i % NB) / (NB / 33); };
@@ -267,7 +268,7 @@ __device__ __forceinline__ void plan_scan_body(uint32_t* __restrict__ ctr, int4*
     }
   // end of king block kb's items
   auto kb_end = [&](int kb) -> uint32_t { return kb == KB - 1 ? s[KB * NB - 1] + ctr[KB * NB - 1] : s[(kb + 1) * NB]; };
-  if (unit_items == 0) {
+  if (unit_work == 0) {
     // Segment units: unit u of king block kb starts at the first item whose
     // cumulative work (a bin's items weighed seg_bin_weight) reaches
     // u * seg_plies.  Bins are contiguous in item order, so each
@@ -317,33 +318,88 @@ __device__ __forceinline__ void plan_scan_body(uint32_t* __restrict__ ctr, int4*
       const int kb = units[v].x;
       units[v].z = v + 1 < ubase[kb + 1] ? units[v + 1].y : (int)kb_end(kb);
     }
-  } else if (t < KB) {
-    // Unit table: each king block's item range in chunks of <= unit_items;
-    // lane kb counts its block's units, a wave prefix sum places them.
-    const int kb = t;
-    const uint32_t b = s[kb * NB];
-    const uint32_t e = kb_end(kb);
-    const uint32_t mine = (e - b + unit_items - 1) / unit_items;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < KB; o <<= 1) {
-      const uint32_t v = __shfl_up(incl, o, KB);
-      if (kb >= o) incl += v;
+  } else {
+    // Units of equal work per king block, ordered for the XCDs (slice_units.h):
+    // block kb holding work w is cut into m = round(w / W) units; the blocks
+    // are ranked by work per unit, and the unit of rank r goes to table entry
+    // slice_table_slot(r).  unit_work = the budget W before slice_budget.
+    uint32_t* pb = lds + kB + 16;    // [kIB] work before bin i within its king block
+    uint32_t* ubase = pb + kIB;      // [KB + 1] rank of each king block's first unit; [KB] = the unit count
+    uint32_t* bw = ubase + KB + 1;   // [KB] work of the block
+    uint32_t* bm = bw + KB;          // [KB] units of the block
+    int* uw = reinterpret_cast<int*>(units);
+    for (int k = 0; k < per; ++k) {  // local[k] = count of bin t*per + k
+      const int i = t * per + k;
+      if (i < kIB) pb[i] = local[k] * slice_item_cost(len_bin(i));
     }
-    uint32_t nu = incl - mine;
-    for (uint32_t c = b; c < e; c += unit_items) units[nu++] = make_int4(kb, (int)c, (int)min(e, c + unit_items), 0);
-    if (kb == KB - 1) ctr[kNU] = incl;
+    __syncthreads();
+    if (t < KB) {
+      uint32_t w = 0;
+      for (int b = 0; b < NB; ++b) {
+        const uint32_t v = pb[t * NB + b];
+        pb[t * NB + b] = w;
+        w += v;
+      }
+      uint32_t work = w;
+#pragma unroll
+      for (int o = 1; o < KB; o <<= 1) work += __shfl_xor(work, o, KB);
+      const uint32_t W = slice_budget(work, kb_end(KB - 1), unit_work);
+      const uint32_t m = slice_block_units(w, W);
+      // rank among the blocks: more work per unit first, then the king block
+      const uint32_t key = m ? w / m : 0;
+      uint32_t first = 0, nu = 0;
+      for (int j = 0; j < KB; ++j) {
+        const uint32_t kj = __shfl(key, j, KB), mj = __shfl(m, j, KB);
+        nu += mj;
+        if (kj > key || (kj == key && j < t)) first += mj;
+      }
+      ubase[t] = first;
+      bw[t] = w;
+      bm[t] = m;
+      if (t == 0) {
+        ubase[KB] = nu;
+        if (nu_out) *nu_out = nu;
+        else ctr[kNU] = nu;
+      }
+      if (m) {  // the block's first unit starts, and its last unit ends, with the block
+        const uint32_t e0 = 4 * slice_table_slot(first, nu), e1 = 4 * slice_table_slot(first + m - 1, nu);
+        uw[e0] = t;
+        uw[e0 + 1] = (int)s[t * NB];
+        uw[e0 + 3] = 0;
+        uw[e1 + 2] = (int)kb_end(t);
+      }
+    }
+    __syncthreads();
+    // 1024 / KB threads per king block place its cuts: cut u starts unit u and
+    // ends unit u - 1 (separate words of two table entries: no thread writes
+    // another's).  The cut lies in the last bin whose work offset is <= its work.
+    constexpr int kLanes = 1024 / KB;
+    const int kb = t / kLanes;
+    const uint32_t w = bw[kb], m = bm[kb], first = ubase[kb], nu = ubase[KB], b0 = s[kb * NB];
+    for (uint32_t u = 1 + t % kLanes; u < m; u += kLanes) {
+      const uint32_t target = slice_cut_work(u, w, m);
+      int b = -1;
+#pragma unroll
+      for (int k = 0; k < NB; ++k) b += pb[kb * NB + k] <= target ? 1 : 0;
+      const int i = kb * NB + b;
+      const int at = (int)(b0 + slice_cut_item(target, pb[i], s[i] - b0, slice_item_cost(len_bin(i))));
+      const uint32_t e0 = 4 * slice_table_slot(first + u, nu), e1 = 4 * slice_table_slot(first + u - 1, nu);
+      uw[e0] = kb;
+      uw[e0 + 1] = at;
+      uw[e0 + 3] = 0;
+      uw[e1 + 2] = at;
+    }
   }
 }
 
 template <int KB, int NB = 33>
 __global__ __launch_bounds__(1024) __attribute__((unused)) void plan_scan_kernel_t(uint32_t* __restrict__ ctr,
                                                                                   int4* __restrict__ units,
-                                                                                  uint32_t unit_items,
+                                                                                  uint32_t unit_work,
                                                                                   uint32_t seg_plies = 0,
                                                                                   uint32_t* __restrict__ nu_out = nullptr) {
   __shared__ uint32_t lds[plan_scan_lds_words<KB, NB>()];
-  plan_scan_body<KB, NB>(ctr, units, unit_items, seg_plies, nu_out, lds);
+  plan_scan_body<KB, NB>(ctr, units, unit_work, seg_plies, nu_out, lds);
 }
 
 constexpr int kListStrideWords = 17;  // words per lane of the list staging rows (68 B)

@@ -3,7 +3,7 @@
 # (bench it with FNNUE_LIB=..., tools/exp_run.sh).  The shipped sources are
 # never edited: the csrc tree is copied to build/exp_<name>/, the optional
 # patch (git diff format, paths relative to the repo root) is applied there,
-# extra -D flags (the tunables FT_UNIT_ITEMS, SEG_UNIT_PLIES, PLAN_WG,
+# extra -D flags (the tunables FT_UNIT_WORK, FT_UNIT_ITEMS, SEG_UNIT_PLIES, PLAN_WG,
 # FT_DEPTH) go to every HIP source.
 #   usage: tools/exp_build.sh <name> [file.patch] [-DFLAG ...]
 set -euo pipefail
