@@ -26,6 +26,7 @@ FT_SLICED, FT_GATHER, FT_AUTO = 0, 1, 2
 FT_GATHER_MAX = 16384  # FNNUE_FT_AUTO gathers chess positions calls up to this size
 PLAYOUT_FINAL, PLAYOUT_PLIES, PLAYOUT_CHILDREN = 0, 1, 2
 VARIANT_CHESS, VARIANT_CRAZYHOUSE, VARIANT_ATOMIC = 0, 1, 2
+VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature set, their own rules
 POS_BYTES = 36
 VPOS_BYTES = 48
 
@@ -136,6 +137,7 @@ SIGNATURES = {
     # include/fnnue_backend.h
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_channel_nets": ([_vp, _i32, _vp, _P(_vp)], _i32),
+    "fnnue_backend_channel_netv": ([_P(_vp), _sz, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_free": ([_vp], None),
     "fnnue_backend_batch_size": ([_vp, _P(_sz)], _i32),
     "fnnue_backend_go": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp], _i32),

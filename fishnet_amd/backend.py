@@ -252,14 +252,19 @@ class _Nets(C.Structure):
 
 
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
-            atomic=None, timeout_ms: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
+            atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
-    (fnnue_backend_channel_nets): each batch is evaluated by its variant's net.
+    (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` theirs
+    (fnnue_backend_channel_netv): each batch is evaluated by its variant's net.
     `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
-    if crazyhouse is None and atomic is None:
+    if kingofthehill is not None or racingkings is not None:
+        given = [n for n in (net, crazyhouse, atomic, kingofthehill, racingkings) if n is not None]
+        arr = (C.c_void_p * len(given))(*[n._h.value for n in given])
+        N.check(N.lib.fnnue_backend_channel_netv(arr, len(given), device, C.byref(init), C.byref(h)))
+    elif crazyhouse is None and atomic is None:
         N.check(N.lib.fnnue_backend_channel(net._h, device, C.byref(init), C.byref(h)))
     else:
         nets = _Nets(net._h if net is not None else None, crazyhouse._h if crazyhouse is not None else None,

@@ -56,7 +56,7 @@ using namespace fnnue::detail;
 namespace {
 
 constexpr int32_t kNormalizeToPawnSf151 = 361;  // upstream uci.h NormalizeToPawnValue (SF 15.1, recalled)
-constexpr int kKinds = 3;                       // net slots: kVariantChess, kVariantCrazyhouse, kVariantAtomic
+constexpr int kKinds = kVariants;               // net slots: one per variant id (net.h kVariant*)
 constexpr uint32_t kDefaultTimeoutMs = 60000;
 // Per-batch text bounds: far beyond any lichess batch (a FEN is < 100 bytes;
 // the longest possible game, ~5,900 moves, < 64 KB of UCI), so that a piece's
@@ -138,17 +138,21 @@ size_t count_moves(const char* s) {
   return s ? scan_tokens(s, &len) : 0;
 }
 
+// A position without a legal move with one of these is lost (`mate 0`), else drawn (`cp 0`).
+constexpr uint8_t kFinalDecided = kFinalCheck | kFinalExtinct | kFinalVariant;
+
 int64_t to_cp(int32_t psqt, int32_t positional, int32_t norm) {
   const int64_t v = ((int64_t)psqt + positional) / 16;  // OutputScale, C truncation
   return v * 100 / norm;
 }
 
 // A root with no legal move: the engine prints `info depth 0 score mate 0`
-// (checkmated; atomic: its king exploded) or `score cp 0` (stalemate) and
+// (checkmated; atomic: its king exploded; kingofthehill / racingkings: lost
+// by the variant's rule) or `score cp 0` (stalemate, a racingkings draw) and
 // `bestmove (none)` ([ref] src/stockfish.rs:359-376, 418-425: Score::Mate(0)
 // / Score::Cp(0), best_move None, nodes 0).
 void terminal_response(fnnue_position_response& r, uint8_t fin) {
-  r.score_kind = (fin & (kFinalCheck | kFinalExtinct)) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+  r.score_kind = (fin & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
   r.score = 0;
   r.depth = 0;
   r.nodes = 0;
@@ -194,15 +198,17 @@ inline void put_compact(fnnue_position_compact* r, int32_t psqt, int32_t positio
 
 // The net slot of a batch's variant (shakmaty Variant names, [ref]
 // src/api.rs:304; logger.rs:194-201): standard chess (EngineFlavor::Official
-// for analysis, queue.rs:530-539) and the two variants with a Fairy-Stockfish
+// for analysis, queue.rs:530-539) and the four variants with a Fairy-Stockfish
 // NNUE feature set here.  -1: a variant this backend does not evaluate
-// (antichess, horde, kingOfTheHill, racingKings, threeCheck).
+// (antichess, horde, threeCheck).
 int kind_of(const char* v) {
   if (!v || !*v || !std::strcmp(v, "standard") || !std::strcmp(v, "chess960") || !std::strcmp(v, "fromPosition") ||
       !std::strcmp(v, "chess"))
     return kVariantChess;
   if (!std::strcmp(v, "crazyhouse")) return kVariantCrazyhouse;
   if (!std::strcmp(v, "atomic")) return kVariantAtomic;
+  if (!std::strcmp(v, "kingOfTheHill")) return kVariantKingOfTheHill;
+  if (!std::strcmp(v, "racingKings")) return kVariantRacingKings;
   return -1;
 }
 
@@ -268,7 +274,9 @@ int variant_move_root(int variant, const fnnue_acquired& a, MoveRoot& R, std::ve
     vb::do_move(k, m);
     kids.push_back(vb::pack(k));
     R.uci.push_back(vb::vuci(b, m));
-    R.kid_fin.push_back(vb::final_state(k));
+    // a child the mover has lost by the variant's rule (racingkings: black
+    // did not catch up) is marked, so that it is never chosen as a mate
+    R.kid_fin.push_back((uint8_t)(vb::final_state(k) | (vb::variant_over(k) && vb::variant_won(k) ? kFinalWon : 0)));
     return true;
   });
   return FNNUE_OK;
@@ -877,7 +885,7 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
       // The last ply is the only one that can have no legal move (nothing can
       // be played from it): mate 0 / cp 0 instead of an evaluation.
       const bool ends = fin[g] & kFinalNoMoves;
-      const uint8_t end_kind = (fin[g] & (kFinalCheck | kFinalExtinct)) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+      const uint8_t end_kind = (fin[g] & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
       if (j.cout) {
         fnnue_position_compact* r = j.cout + b;
         const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
@@ -922,7 +930,7 @@ void fnnue_backend::fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint3
   for (size_t t = 0; t < W.roots.size(); ++t) {
     const MoveRoot& R = W.mroots[t];
     const size_t i = W.roots[t];
-    // rank: 2 = mates, 1 = evaluated, 0 = never (value orders within a rank)
+    // rank: 2 = mates, 1 = evaluated, 0 = loses at once (value orders within a rank)
     size_t best = 0;
     int best_rank = -1;
     int64_t bv = INT64_MIN;
@@ -931,7 +939,10 @@ void fnnue_backend::fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint3
       const uint8_t f = R.kid_fin[q];
       int rank = 1;
       int64_t v;
-      if (f & (kFinalCheck | kFinalExtinct) && (f & kFinalNoMoves)) {
+      if (f & kFinalWon) {
+        rank = 0;
+        v = 0;
+      } else if (f & kFinalDecided && (f & kFinalNoMoves)) {
         rank = 2;
         v = 0;
       } else if (f & kFinalNoMoves) {
@@ -946,8 +957,8 @@ void fnnue_backend::fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint3
       }
     }
     const size_t x = W.kid_first[t] + best;
-    const uint8_t kind = best_rank == 2 ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-    const int64_t score = best_rank == 2 ? 1 : bv * 100 / norm;
+    const uint8_t kind = best_rank != 1 ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+    const int64_t score = best_rank == 2 ? 1 : best_rank == 0 ? -1 : bv * 100 / norm;
     if (j.cout) {
       put_compact(j.cout + j.off[i], -kps[x], -kpo[x], (int32_t)score, kind, 1, 0);
       fnnue_batch_compact& B = j.bout[i];
@@ -991,7 +1002,7 @@ void fnnue_backend::fill_hostonly(Job& j, const std::vector<size_t>& all_skipped
       const uint8_t fin = W.troots[t].fin;
       if (j.cout) {
         put_compact(j.cout + j.off[i], 0, 0, 0,
-                    (fin & (kFinalCheck | kFinalExtinct)) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP, 0,
+                    (fin & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP, 0,
                     FNNUE_COMPACT_NO_MOVES);
         batch(i);
         continue;
@@ -1268,19 +1279,13 @@ int fnnue_backend_batch_size(const fnnue_acquired* a, size_t* n) {
   return FNNUE_OK;
 }
 
-int fnnue_backend_channel_nets(const fnnue_backend_nets* nets, int device, const fnnue_backend_init* init,
-                               fnnue_backend** out) {
-  if (!nets || !out) return fail(FNNUE_E_ARG, "null argument");
-  *out = nullptr;
-  const fnnue_net* slot[kKinds] = {nets->chess, nets->crazyhouse, nets->atomic};
-  if (!slot[0] && !slot[1] && !slot[2]) return fail(FNNUE_E_ARG, "no net");
-  static const char* const kName[kKinds] = {"chess (HalfKAv2_hm)", "crazyhouse", "atomic"};
-  for (int k = 0; k < kKinds; ++k) {
-    if (!slot[k]) continue;
-    int variant = -1;
-    if (int rc = fnnue_net_variant(slot[k], &variant)) return rc;
-    if (variant != k) return fail(FNNUE_E_ARCH, std::string("the ") + kName[k] + " slot needs a " + kName[k] + " net");
-  }
+}  // extern "C"
+
+namespace {
+
+// The actor over one net per slot (slot k: a net of variant k, or null).
+int channel_slots(const fnnue_net* const (&slot)[kKinds], int device, const fnnue_backend_init* init,
+                  fnnue_backend** out) {
   if (init && init->normalize_to_pawn < 0) return fail(FNNUE_E_ARG, "normalize_to_pawn must be positive");
   reap_abandoned();
   fnnue_backend* b = nullptr;
@@ -1328,15 +1333,46 @@ int fnnue_backend_channel_nets(const fnnue_backend_nets* nets, int device, const
   return FNNUE_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int fnnue_backend_channel_nets(const fnnue_backend_nets* nets, int device, const fnnue_backend_init* init,
+                               fnnue_backend** out) {
+  if (!nets || !out) return fail(FNNUE_E_ARG, "null argument");
+  *out = nullptr;
+  const fnnue_net* slot[kKinds] = {nets->chess, nets->crazyhouse, nets->atomic};
+  if (!slot[0] && !slot[1] && !slot[2]) return fail(FNNUE_E_ARG, "no net");
+  static const char* const kName[3] = {"chess (HalfKAv2_hm)", "crazyhouse", "atomic"};
+  for (int k = 0; k < 3; ++k) {
+    if (!slot[k]) continue;
+    int variant = -1;
+    if (int rc = fnnue_net_variant(slot[k], &variant)) return rc;
+    if (variant != k) return fail(FNNUE_E_ARCH, std::string("the ") + kName[k] + " slot needs a " + kName[k] + " net");
+  }
+  return channel_slots(slot, device, init, out);
+}
+
+int fnnue_backend_channel_netv(const fnnue_net* const* nets, size_t n, int device, const fnnue_backend_init* init,
+                               fnnue_backend** out) {
+  if (!nets || !out) return fail(FNNUE_E_ARG, "null argument");
+  *out = nullptr;
+  if (n == 0) return fail(FNNUE_E_ARG, "no net");
+  const fnnue_net* slot[kKinds] = {};
+  for (size_t i = 0; i < n; ++i) {
+    int variant = -1;
+    if (!nets[i]) return fail(FNNUE_E_ARG, "null net");
+    if (int rc = fnnue_net_variant(nets[i], &variant)) return rc;
+    if (!variant_known(variant)) return fail(FNNUE_E_ARCH, "a net of unknown variant " + std::to_string(variant));
+    if (slot[variant]) return fail(FNNUE_E_ARG, std::string("two ") + variant_name(variant) + " nets");
+    slot[variant] = nets[i];
+  }
+  return channel_slots(slot, device, init, out);
+}
+
 int fnnue_backend_channel(const fnnue_net* net, int device, const fnnue_backend_init* init, fnnue_backend** out) {
   if (!net || !out) return fail(FNNUE_E_ARG, "null argument");
-  int variant = 0;
-  if (int rc = fnnue_net_variant(net, &variant)) return rc;
-  fnnue_backend_nets nets{};
-  if (variant == kVariantChess) nets.chess = net;
-  else if (variant == kVariantCrazyhouse) nets.crazyhouse = net;
-  else nets.atomic = net;
-  return fnnue_backend_channel_nets(&nets, device, init, out);
+  return fnnue_backend_channel_netv(&net, 1, device, init, out);
 }
 
 void fnnue_backend_free(fnnue_backend* b) {

@@ -40,6 +40,14 @@ constexpr uint32_t kBuildErrFen = 1, kBuildErrMove = 2, kBuildErrCount = 3;
 // (checkmated, or atomic: its king exploded) or `score cp 0` (stalemate)
 // ([ref] src/stockfish.rs:359-376 parses them to Score::Mate(0) / Cp(0)).
 constexpr uint8_t kFinalNoMoves = 1, kFinalCheck = 2, kFinalExtinct = 4;
+// The game was decided by the variant's own rule (kingofthehill: a king on the
+// hill; racingkings: one king on rank 8): `score mate 0`.  (The racingkings
+// draw with both kings on rank 8 is kFinalNoMoves alone.)
+constexpr uint8_t kFinalVariant = 8;
+// Host only (move work, backend.cpp): the decided game is won by the side to
+// move (racingkings: black missed its catch-up move).
+constexpr uint8_t kFinalWon = 0x40;
+static_assert(kFinalNoMoves == FNNUE_END_NO_MOVES && kFinalVariant == FNNUE_END_VARIANT, "fnnue.h FNNUE_END_*");
 // A game the replay rejected: kFinalFailed | its kBuildErr* code (replay_games_device).
 constexpr uint8_t kFinalFailed = 0x80;
 

@@ -213,7 +213,7 @@ int host_vpos_state(const fnnue_vpos& p, int variant) {
     n += p.hand[i];
   }
   if (n > 32 || p.stm > 1) return 0;
-  if (variant == kVariantAtomic && wk + bk == 1) return 2;
+  if (variant_one_king(variant) && wk + bk == 1) return 2;
   return wk == 1 && bk == 1 ? 1 : 0;
 }
 
@@ -378,7 +378,10 @@ hipEvent_t mid_event(std::array<hipEvent_t, 4>* ev) { return ev ? (*ev)[1] : nul
 extern "C" {
 
 const char* fnnue_last_error(void) { return g_err.c_str(); }
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 1u; }  // 3.1: fnnue_backend_go_timeout, FNNUE_E_TIMEOUT
+// 3.1: fnnue_backend_go_timeout, FNNUE_E_TIMEOUT
+// 3.2: FNNUE_VARIANT_KINGOFTHEHILL / FNNUE_VARIANT_RACINGKINGS accepted wherever a variant id is,
+//      FNNUE_END_VARIANT, fnnue_backend_channel_netv
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 2u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -397,11 +400,12 @@ int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   return FNNUE_OK;
 }
 
+static bool variant_net_id(int variant) { return variant_known(variant) && variant != kVariantChess; }
+
 int fnnue_net_load_variant_mem(const void* buf, size_t len, int variant, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
   *out = nullptr;
-  if (variant != FNNUE_VARIANT_CRAZYHOUSE && variant != FNNUE_VARIANT_ATOMIC)
-    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (!variant_net_id(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   std::unique_ptr<fnnue_net> n(new (std::nothrow) fnnue_net);
   if (!n) return fail(FNNUE_E_OOM, "host allocation failed");
   std::string err;
@@ -510,8 +514,7 @@ int fnnue_net_synthesize(uint64_t seed, uint32_t hd, uint32_t flags, void** buf,
 
 int fnnue_net_synthesize_variant(uint64_t seed, uint32_t hd, int variant, uint32_t flags, void** buf, size_t* len) {
   if (!buf || !len) return fail(FNNUE_E_ARG, "null argument");
-  if (variant != FNNUE_VARIANT_CRAZYHOUSE && variant != FNNUE_VARIANT_ATOMIC)
-    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (!variant_net_id(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   if (!hd_supported(hd)) return fail(FNNUE_E_ARCH, "unsupported hd");
   try {
     Net n;

@@ -113,7 +113,10 @@ struct ChessFs {
   }
 };
 
-template <int V>  // kVariantCrazyhouse / kVariantAtomic
+// V: kVariantCrazyhouse, kVariantAtomic, or kVariantKingOfTheHill for the
+// board-only set without atomic's one-king records (kingofthehill and
+// racingkings: the plan kernels, which decode; the rest runs as atomic).
+template <int V>
 struct VariantFs {
   using Pos = fnnue_vpos;
   static constexpr int R = (int)variant_rows(V);
@@ -124,7 +127,7 @@ struct VariantFs {
   static constexpr uint32_t kNone = 16u * R;
   using Dec = VariantBoard;
   template <bool kOcc = true>
-  __device__ static __forceinline__ Dec decode(const Pos* p) { return vdecode<kOcc>(p, kHand); }
+  __device__ static __forceinline__ Dec decode(const Pos* p) { return vdecode<kOcc>(p, kHand, variant_one_king(V)); }
   __device__ static __forceinline__ Dec load_base(const Pos* p, uint32_t info) {
     Dec d;
     const uint32_t* pw = reinterpret_cast<const uint32_t*>(p);
@@ -1117,6 +1120,8 @@ hipError_t launch_seg_plan(int variant, const void* pos, uint32_t n, const void*
     return seg_plan_t<VariantFs<kVariantCrazyhouse>>(vp, n, sp, sbase, star, P, G, bucket, err, stream);
   if (variant == kVariantAtomic)
     return seg_plan_t<VariantFs<kVariantAtomic>>(vp, n, sp, sbase, star, P, G, bucket, err, stream);
+  if (variant_board_only(variant))
+    return seg_plan_t<VariantFs<kVariantKingOfTheHill>>(vp, n, sp, sbase, star, P, G, bucket, err, stream);
   return hipErrorInvalidValue;
 }
 
@@ -1135,6 +1140,7 @@ hipError_t launch_seg_plan_small(int variant, const void* pos, uint32_t n, const
   if (variant == kVariantChess) { FNNUE_SMALL_PLAN(ChessFs, fnnue_pos) }
   if (variant == kVariantCrazyhouse) { FNNUE_SMALL_PLAN(VariantFs<kVariantCrazyhouse>, fnnue_vpos) }
   if (variant == kVariantAtomic) { FNNUE_SMALL_PLAN(VariantFs<kVariantAtomic>, fnnue_vpos) }
+  if (variant_board_only(variant)) { FNNUE_SMALL_PLAN(VariantFs<kVariantKingOfTheHill>, fnnue_vpos) }
 #undef FNNUE_SMALL_PLAN
   return hipErrorInvalidValue;
 }
@@ -1147,7 +1153,7 @@ hipError_t launch_seg_units(int variant, const SlicedPlan& P, void* units, uint3
   return hipGetLastError();
   if (variant == kVariantChess) { FNNUE_SEG_UNITS(ChessFs) }
   if (variant == kVariantCrazyhouse) { FNNUE_SEG_UNITS(VariantFs<kVariantCrazyhouse>) }
-  if (variant == kVariantAtomic) { FNNUE_SEG_UNITS(VariantFs<kVariantAtomic>) }
+  if (variant_board_only(variant)) { FNNUE_SEG_UNITS(VariantFs<kVariantAtomic>) }
 #undef FNNUE_SEG_UNITS
   return hipErrorInvalidValue;
 }
@@ -1173,7 +1179,7 @@ hipError_t launch_seg_ft(uint32_t hd, int variant, uint32_t n, int mode, const N
     }                                                                                    \
   }
   if (variant == kVariantCrazyhouse) FNNUE_VSEG(kVariantCrazyhouse)
-  if (variant == kVariantAtomic) FNNUE_VSEG(kVariantAtomic)
+  if (variant_board_only(variant)) FNNUE_VSEG(kVariantAtomic)
 #undef FNNUE_VSEG
   return hipErrorInvalidValue;
 }

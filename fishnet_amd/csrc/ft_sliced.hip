@@ -382,7 +382,7 @@ size_t variant_tiles_bytes(uint32_t hd, int variant) {
   if (variant == kVariantCrazyhouse) {                                          \
     using G = VariantGeom<kVBoardRows + kVHandRows>;                            \
     FNNUE_VHD_DISPATCH(hd, CALLG)                                               \
-  } else if (variant == kVariantAtomic) {                                       \
+  } else if (variant_board_only(variant)) {                                     \
     using G = VariantGeom<kVBoardRows>;                                         \
     FNNUE_VHD_DISPATCH(hd, CALLG)                                               \
   }                                                                             \

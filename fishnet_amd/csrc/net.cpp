@@ -209,7 +209,7 @@ void synthesize_net(uint64_t seed, uint32_t hd, uint32_t flags, Net& net, int va
   net.file_hash = ft_hash(hd, variant) ^ net_hash(hd);
   net.desc = "fishnet-amd synthetic SFNNv5 net seed=" + std::to_string(seed) + " hd=" + std::to_string(hd) +
              " flags=" + std::to_string(flags) +
-             (variant ? " variant=" + std::string(variant == kVariantCrazyhouse ? "crazyhouse" : "atomic") : "");
+             (variant ? " variant=" + std::string(variant_name(variant)) : "");
   net.ft_bias.resize(hd);
   net.ft_w.resize((size_t)hd * net.nfeat);
   net.psqt_w.resize((size_t)kPsqtBuckets * net.nfeat);

@@ -23,6 +23,25 @@ constexpr int kFeatures = 22528;                // 64 king sq / 2 (mirror) * 11 
 // types x 16 hand slots.
 constexpr uint32_t kFtHashBaseVariants = 0x5F234CB8u;  // HalfKAv2::HashValue
 constexpr int kVariantChess = 0, kVariantCrazyhouse = 1, kVariantAtomic = 2;
+// The board-only feature set of atomic under other rules (no explosions).
+constexpr int kVariantKingOfTheHill = 3, kVariantRacingKings = 4;
+constexpr int kVariants = 5;
+constexpr bool variant_known(int v) { return v >= kVariantChess && v < kVariants; }
+// Board-only feature set (704 rows per king square): atomic and the two above.
+constexpr bool variant_board_only(int v) {
+  return v == kVariantAtomic || v == kVariantKingOfTheHill || v == kVariantRacingKings;
+}
+// A position with one king is a finished game's record, answered (0, 0):
+// atomic alone (an exploded king); everywhere else it is an invalid position.
+constexpr bool variant_one_king(int v) { return v == kVariantAtomic; }
+constexpr const char* variant_name(int v) {
+  return v == kVariantChess                ? "chess"
+         : v == kVariantCrazyhouse         ? "crazyhouse"
+         : v == kVariantAtomic             ? "atomic"
+         : v == kVariantKingOfTheHill      ? "kingofthehill"
+         : v == kVariantRacingKings        ? "racingkings"
+                                           : "unknown";
+}
 constexpr int kVBoardRows = 704, kVHandSlots = 16, kVHandRows = 2 * 5 * kVHandSlots;
 constexpr uint32_t variant_rows(int variant) {  // feature rows per own-king square
   return variant == kVariantCrazyhouse ? kVBoardRows + kVHandRows : kVBoardRows;

@@ -24,14 +24,14 @@ namespace fnnue {
 
 namespace {
 
-__global__ __launch_bounds__(1024) void vplan_count_kernel(const fnnue_vpos* __restrict__ pos, uint32_t n, int pockets,
+__global__ __launch_bounds__(1024) void vplan_count_kernel(const fnnue_vpos* __restrict__ pos, uint32_t n, int pockets, int one_king,
                                                           uint32_t* __restrict__ ctr, uint32_t* __restrict__ err) {
   __shared__ uint32_t h[kVBins];
   for (int i = threadIdx.x; i < kVBins; i += blockDim.x) h[i] = 0;
   __syncthreads();
   uint32_t bad = 0;
   for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-    const VariantBoard v = vdecode<false>(pos + p, pockets != 0);  // counts only: no occupancy mask
+    const VariantBoard v = vdecode<false>(pos + p, pockets != 0, one_king != 0);  // counts only: no occupancy mask
     if (!v.ok) {
       bad |= v.over ? 0u : 1u;  // an exploded king is a result (0, 0), not an error
       atomicAdd(&h[kVItemBins + 8], 1u);
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kScatterPositions) void vplan_scatter_kernel(
   int kw = 0, kb = 0, kp = kVItemBins + 8;
   uint32_t rw = 0, rb = 0, rp = 0;
   if (live) {
-    v = vdecode(pos + p, R > kVBoardRows);
+    v = vdecode(pos + p, R > kVBoardRows, false);  // (the count kernel latched any error)
     if (v.ok) {
       kw = vblock(0, v.b.wk) * 33 + v.nfeat;
       kb = vblock(1, v.b.bk) * 33 + v.nfeat;
@@ -164,13 +164,14 @@ uint32_t variant_max_units(uint32_t chunk) { return 64 + (2 * chunk + kUnitItems
 hipError_t launch_variant_plan(const fnnue_vpos* pos, uint32_t n, int variant, const SlicedPlan& P, int32_t* psqt,
                                uint8_t* bucket, uint32_t* err, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  if (variant != kVariantCrazyhouse && variant != kVariantAtomic) return hipErrorInvalidValue;
+  if (variant != kVariantCrazyhouse && !variant_board_only(variant)) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(P.ctr, 0, variant_ctr_words() * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   const bool pockets = variant == kVariantCrazyhouse;
   uint32_t blocks = (n + 1023) / 1024;
   if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(vplan_count_kernel, dim3(blocks), dim3(1024), 0, stream, pos, n, pockets ? 1 : 0, P.ctr, err);
+  hipLaunchKernelGGL(vplan_count_kernel, dim3(blocks), dim3(1024), 0, stream, pos, n, pockets ? 1 : 0,
+                     variant_one_king(variant) ? 1 : 0, P.ctr, err);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(vplan_scan_kernel, dim3(1), dim3(1024), 0, stream, P.ctr, (int4*)P.units);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -18,7 +18,7 @@ struct VariantBoard {
 };
 
 template <bool kOcc = true>
-__device__ __forceinline__ VariantBoard vdecode(const fnnue_vpos* p, bool pockets) {
+__device__ __forceinline__ VariantBoard vdecode(const fnnue_vpos* p, bool pockets, bool one_king) {
   VariantBoard v;
   v.b = lane_decode<kOcc>(reinterpret_cast<const fnnue_pos*>(p));
   const uint8_t* h = reinterpret_cast<const uint8_t*>(p) + 33;
@@ -35,9 +35,9 @@ __device__ __forceinline__ VariantBoard vdecode(const fnnue_vpos* p, bool pocket
   v.ok = v.b.ok && v.b.stm <= 1 && !bad && v.nfeat <= 32;
   // Atomic: a capture next to a king explodes it and ends the game; the
   // position after it (exactly one king left) is a terminal record the
-  // evaluator answers with (0, 0) without latching an error.  Only variants
-  // without pockets here (crazyhouse kings are never removed).
-  v.over = !pockets && v.b.sane && !bad && v.nfeat <= 32 && v.b.nwk + v.b.nbk == 1;
+  // evaluator answers with (0, 0) without latching an error.  Atomic alone
+  // (one_king): crazyhouse, kingofthehill and racingkings kings are never removed.
+  v.over = one_king && !pockets && v.b.sane && !bad && v.nfeat <= 32 && v.b.nwk + v.b.nbk == 1;
   return v;
 }
 

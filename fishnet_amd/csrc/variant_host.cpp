@@ -31,8 +31,16 @@ fnnue_vpos pack_v(const VState& v) {
   return p;
 }
 
-void start_position(VState& v) {
+void start_position(VState& v, int variant) {
   std::memset(&v, 0, sizeof v);
+  if (variant == kVariantRacingKings) {  // 8/8/8/8/8/8/krbnNBRK/qrbnNBRQ
+    const int r1[8] = {5 | 8, 4 | 8, 3 | 8, 2 | 8, 2, 3, 4, 5}, r2[8] = {6 | 8, 4 | 8, 3 | 8, 2 | 8, 2, 3, 4, 6};
+    for (int f = 0; f < 8; ++f) {
+      v.b[f] = (uint8_t)r1[f];
+      v.b[8 + f] = (uint8_t)r2[f];
+    }
+    return;
+  }
   const int back[8] = {4, 2, 3, 5, 6, 3, 2, 4};
   for (int f = 0; f < 8; ++f) {
     v.b[f] = (uint8_t)back[f];
@@ -134,7 +142,14 @@ int pack_checked(const vb::VBoard& b, fnnue_vpos* out) {
 }
 
 
-bool valid_variant(int variant) { return variant == FNNUE_VARIANT_CRAZYHOUSE || variant == FNNUE_VARIANT_ATOMIC; }
+bool valid_variant(int variant) { return variant_known(variant) && variant != kVariantChess; }
+
+// The variant's standard start position.
+const char* start_fen_of(int variant) {
+  return variant == kVariantCrazyhouse    ? "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR[] w KQkq - 0 1"
+         : variant == kVariantRacingKings ? "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1"
+                                          : "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
+}
 
 uint64_t vperft(const vb::VBoard& b, int depth) {
   if (depth == 0) return 1;
@@ -180,20 +195,19 @@ extern "C" {
 
 int fnnue_vpos_from_fen(int variant, const char* fen, fnnue_vpos* out) {
   if (!fen || !out) return fail(FNNUE_E_ARG, "null argument");
-  if (variant != FNNUE_VARIANT_CRAZYHOUSE && variant != FNNUE_VARIANT_ATOMIC)
-    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   vb::VBoard b;
   if (!vb::parse_fen(fen, 0, (uint32_t)std::strlen(fen), variant, b))
-    return fail(FNNUE_E_FEN, std::string("unparsable ") + (variant == FNNUE_VARIANT_CRAZYHOUSE ? "crazyhouse" : "atomic") +
-                                 " FEN (placement, holdings, side to move, one king per side): " + fen);
+    return fail(FNNUE_E_FEN, std::string("unparsable ") + variant_name(variant) +
+                                 " FEN (placement, holdings, side to move, one king per side; racingkings: no "
+                                 "pawns, no castling rights): " + fen);
   return pack_checked(b, out);
 }
 
 int fnnue_random_vpositions(uint64_t seed, int variant, size_t count, uint32_t max_plies, int mode, fnnue_vpos* out,
                             size_t cap, uint32_t* off, size_t off_cap, size_t* n_out, size_t* n_groups) {
   if (!n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  if (variant != FNNUE_VARIANT_CRAZYHOUSE && variant != FNNUE_VARIANT_ATOMIC)
-    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   if (mode != FNNUE_PLAYOUT_FINAL && mode != FNNUE_PLAYOUT_PLIES) return fail(FNNUE_E_ARG, "bad mode");
   std::vector<fnnue_vpos> res;
   std::vector<uint32_t> offs{0};
@@ -202,7 +216,7 @@ int fnnue_random_vpositions(uint64_t seed, int variant, size_t count, uint32_t m
       uint64_t st = seed ^ (0xD1B54A32D192ED03ull * (i + 1));
       const uint32_t L = (uint32_t)(splitmix64(st) % ((uint64_t)max_plies + 1));
       VState v;
-      start_position(v);
+      start_position(v, variant);
       if (mode == FNNUE_PLAYOUT_PLIES) res.push_back(pack_v(v));
       for (uint32_t k = 0; k < L; ++k) {
         random_step(v, st, variant);
@@ -323,8 +337,7 @@ int fnnue_random_vgames(uint64_t seed, int variant, size_t count, uint32_t max_p
   if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   if (threads < 1) threads = 1;
   if (threads > 256) threads = 256;
-  const char* start = variant == FNNUE_VARIANT_CRAZYHOUSE ? "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR[] w KQkq - 0 1"
-                                                          : "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
+  const char* start = start_fen_of(variant);
   vb::VBoard root;
   vb::parse_fen(start, 0, (uint32_t)std::strlen(start), variant, root);
   // Game i: L ~ U[0, max_plies] uniformly random legal moves from (seed, i),

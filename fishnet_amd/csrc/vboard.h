@@ -1,4 +1,5 @@
-// vboard.h — crazyhouse and atomic rules on bitboards, one source for the host
+// vboard.h — crazyhouse, atomic, king-of-the-hill and racing-kings rules on
+// bitboards, one source for the host
 // (fnnue_game_vpositions, fnnue_vperft) and the device batch builder
 // (vbuilder.hip): FEN with holdings and promoted marks, legal moves including
 // drops, do_move with pockets (crazyhouse) or explosions (atomic), packing to
@@ -21,6 +22,16 @@
 //    next to each other never attack (a capture next to the capturer's own
 //    king would explode it).  Castling needs the king's path unattacked in
 //    that sense.
+//  * kingofthehill: chess; a position with either king on d4, e4, d5 or e5 is
+//    over (the king there belongs to the side that just moved: the side to
+//    move has lost) and has no legal move.
+//  * racingkings: no pawns, no castling; a move is legal iff neither king is
+//    attacked after it (no checks are given); a position with a king on rank 8
+//    is over and has no legal move, except that with white's king there,
+//    black's not and black to move the game goes on while black's king has a
+//    rank-8 neighbour square not occupied by a black piece and not attacked
+//    by white (shakmaty's RacingKings::is_variant_end: it does not ask
+//    whether that step is otherwise legal).  Both kings there: a draw.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +47,8 @@ namespace vb {
 #define FNNUE_HD __host__ __device__ __forceinline__
 
 constexpr int kCrazyhouse = FNNUE_VARIANT_CRAZYHOUSE, kAtomic = FNNUE_VARIANT_ATOMIC;
+constexpr int kKingOfTheHill = FNNUE_VARIANT_KINGOFTHEHILL, kRacingKings = FNNUE_VARIANT_RACINGKINGS;
+constexpr uint64_t kHill = 0x0000001818000000ull;  // d4 e4 d5 e5
 constexpr int PAWN = 1, KNIGHT = 2, BISHOP = 3, ROOK = 4, QUEEN = 5, KING = 6;
 constexpr uint64_t kNotA = 0xFEFEFEFEFEFEFEFEull, kNotH = 0x7F7F7F7F7F7F7F7Full;
 constexpr uint64_t kNotAB = 0xFCFCFCFCFCFCFCFCull, kNotGH = 0x3F3F3F3F3F3F3F3Full;
@@ -49,7 +62,7 @@ struct VBoard {
   int8_t cr[2][2];    // castling rook squares [colour][0 king side, 1 queen side], -1 none
   int8_t ep;          // en-passant target square or -1
   uint8_t stm;
-  uint8_t variant;    // kCrazyhouse / kAtomic
+  uint8_t variant;    // kCrazyhouse / kAtomic / kKingOfTheHill / kRacingKings
   uint8_t c960;       // castling needs Chess960 (king-takes-rook) notation
 };
 
@@ -189,6 +202,36 @@ FNNUE_HD bool king_danger(const VBoard& b, int s, int us, uint64_t occ) {
   return attacked(b, s, them, occ);
 }
 
+// Has the game ended by the variant's own rule (kingofthehill: a king on the
+// hill; racingkings: a king on rank 8, unless black may still catch up)?  No
+// move is legal in such a position.
+FNNUE_HD bool variant_over(const VBoard& b) {
+  if (b.variant == kKingOfTheHill) return (b.bt[KING] & kHill) != 0;
+  if (b.variant != kRacingKings) return false;
+  const uint64_t goal = b.bt[KING] & kRank8;
+  if (!goal) return false;
+  if (b.stm == 0 || (goal & b.bc[1])) return true;
+  const int bk = king_sq(b, 1);
+  if (bk < 0) return true;
+  const uint64_t occ = occupied(b);
+  bool catch_up = false;
+  for (uint64_t t = king_att(bk) & kRank8 & ~b.bc[1]; t; t &= t - 1) catch_up = catch_up || !attacked(b, vlsb(t), 0, occ);
+  return !catch_up;
+}
+// In a position variant_over() ended: has the side to move lost (false: a
+// racingkings draw with both kings on rank 8, or the side to move's own king
+// alone on rank 8 — white's after black missed its catch-up move)?
+FNNUE_HD bool variant_lost(const VBoard& b) {
+  if (b.variant == kKingOfTheHill) return true;
+  const uint64_t goal = b.bt[KING] & kRank8;
+  return !(goal & colour(b, b.stm));
+}
+FNNUE_HD bool variant_won(const VBoard& b) {
+  if (b.variant != kRacingKings) return false;
+  const uint64_t goal = b.bt[KING] & kRank8;
+  return (goal & colour(b, b.stm)) && !(goal & colour(b, b.stm ^ 1));
+}
+
 FNNUE_HD void do_move(VBoard& b, const VMove& m) {
   const int us = b.stm, them = us ^ 1;
   int new_ep = -1;
@@ -255,7 +298,12 @@ FNNUE_HD bool legal_after(const VBoard& before, const VBoard& after) {
   // `after` has the other side to move: ask whether `us`'s king is in danger there
   VBoard a = after;
   a.stm = (uint8_t)us;
-  return !king_danger(a, ku, us, occupied(a));
+  if (king_danger(a, ku, us, occupied(a))) return false;
+  if (before.variant == kRacingKings) {  // no move gives check
+    const int kt = king_sq(after, them);
+    if (kt >= 0 && attacked(after, kt, us, occupied(after))) return false;
+  }
+  return true;
 }
 
 // Castling conditions for the rook on rsq (side 0 king side, 1 queen side):
@@ -290,6 +338,7 @@ FNNUE_HD bool pseudo_member(const VBoard& b, const VMove& m) {
   const int us = b.stm, them = us ^ 1;
   const uint64_t occ = occupied(b), own = colour(b, us), opp = colour(b, them);
   const uint64_t tm = 1ull << m.to;
+  if (variant_over(b)) return false;  // a finished position has no move
   if (m.kind == 2) {
     if (b.variant != kCrazyhouse || m.piece < PAWN || m.piece > QUEEN || !in_hand(b, us, m.piece)) return false;
     uint64_t empty = ~occ;
@@ -339,6 +388,7 @@ __host__ __device__ void for_each_legal(const VBoard& b, F&& f, uint64_t from_ma
   const int us = b.stm, them = us ^ 1;
   const uint64_t occ = occupied(b), own = colour(b, us), opp = colour(b, them);
   const bool atomic = b.variant == kAtomic;
+  if (variant_over(b)) return;
   auto emit = [&](int from, int to, int piece, int kind) -> bool {
     const VMove m{(int8_t)from, (int8_t)to, (int8_t)piece, (int8_t)kind};
     VBoard c = b;
@@ -403,16 +453,22 @@ __host__ __device__ void for_each_legal(const VBoard& b, F&& f, uint64_t from_ma
 }
 
 // Game-end flags of a position (builder.h kFinal*): no legal move (bit 0),
-// the side to move's king attacked (bit 1), its king exploded (bit 2, atomic).
+// the side to move's king attacked (bit 1), its king exploded (bit 2, atomic),
+// the game decided by the variant's own rule (bit 3: kingofthehill,
+// racingkings; not for the racingkings draw with both kings on rank 8).
+FNNUE_HD uint8_t end_flags(const VBoard& b, bool any) {
+  const int us = b.stm, k = king_sq(b, us);
+  const bool check = k >= 0 && king_danger(b, k, us, occupied(b));
+  const bool decided = variant_over(b) && (variant_lost(b) || variant_won(b));
+  return (uint8_t)((any ? 0 : 1) | (check ? 2 : 0) | (k < 0 ? 4 : 0) | (decided ? 8 : 0));
+}
 FNNUE_HD uint8_t final_state(const VBoard& b) {
   bool any = false;
   for_each_legal(b, [&](const VMove&) -> bool {
     any = true;
     return false;
   });
-  const int us = b.stm, k = king_sq(b, us);
-  const bool check = k >= 0 && king_danger(b, k, us, occupied(b));
-  return (uint8_t)((any ? 0 : 1) | (check ? 2 : 0) | (k < 0 ? 4 : 0));
+  return end_flags(b, any);
 }
 
 FNNUE_HD fnnue_vpos pack(const VBoard& b) {
@@ -474,6 +530,9 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
   if (len == 0) return false;
   int r = 7, f = 0, last = -1;
   bool holdings = false;
+  // kingofthehill / racingkings FENs are plain chess FENs (no holdings, no
+  // promoted marks): what the chess parser of the device builder accepts
+  const bool plain = variant == kKingOfTheHill || variant == kRacingKings;
   for (uint32_t i = st; i < st + (uint32_t)len; ++i) {
     const char ch = text[i];
     if (holdings) {
@@ -487,18 +546,19 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
       continue;
     }
     if (ch == '[') {
-      if (r != 0 || f != 8) return false;
+      if (r != 0 || f != 8 || plain) return false;
       holdings = true;
       continue;
     }
     if (ch == '~') {
-      if (last < 0) return false;
+      if (last < 0 || plain) return false;
       b.promoted |= 1ull << last;
       continue;
     }
     if (ch == '/') {
       if (f != 8) return false;
       if (r == 0) {  // a ninth field: holdings
+        if (plain) return false;
         holdings = true;
         continue;
       }
@@ -523,6 +583,7 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
   if (len != 1 || (text[st] != 'w' && text[st] != 'b')) return false;
   b.stm = text[st] == 'w' ? 0 : 1;
   if (vpopcnt(b.bt[KING] & b.bc[0]) != 1 || vpopcnt(b.bt[KING] & b.bc[1]) != 1) return false;
+  if (variant == kRacingKings && b.bt[PAWN]) return false;  // racingkings has no pawns
   uint32_t cst;
   const int clen = next_token(text, p, end, cst);
   if (clen > 0 && !(clen == 1 && text[cst] == '-')) {
@@ -561,6 +622,8 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
       if (rsq >= 0 && ((k & 7) != 4 || (rsq & 7) != (side == 0 ? 7 : 0))) b.c960 = 1;
     }
   }
+  // racingkings has no castling rights
+  if (variant == kRacingKings && (b.cr[0][0] >= 0 || b.cr[0][1] >= 0 || b.cr[1][0] >= 0 || b.cr[1][1] >= 0)) return false;
   uint32_t est;
   const int elen = next_token(text, p, end, est);
   if (elen == 2 && text[est] >= 'a' && text[est] <= 'h' && text[est + 1] >= '1' && text[est + 1] <= '8')

@@ -1,5 +1,6 @@
 // vbuilder.hip — device batch builder for Fairy-Stockfish variants
-// (crazyhouse, atomic): the variant half of IncomingBatch::from_acquired
+// (crazyhouse, atomic, kingofthehill, racingkings): the variant half of
+// IncomingBatch::from_acquired
 // ([ref] src/queue.rs:524-552 with body.variant != Standard, routed to the
 // MultiVariant engine at :530-539; variants from src/assets.rs:384-391).
 //
@@ -9,11 +10,18 @@
 // (fnnue_game_vpositions) runs, which the tests hold it to record for record —
 // writing one fnnue_vpos per ply; CHILDREN adds one thread per ply for its
 // legal children (drops included).
+//
+// kingofthehill and racingkings play chess moves (no drops, no explosions), so
+// they replay on the chess rule set's lane-parallel chain (chess_rules.h
+// ChessRules::lane_chain) with their own legality and end of the game
+// (PlainRules below), on DBoard boards; the host runs the same rules from
+// vboard.h, and the tests hold the two to each other record for record.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "builder.h"
+#include "chess_rules.h"
 #include "replay_wave.h"
 #include "vboard.h"
 
@@ -308,12 +316,122 @@ struct VariantRules {
     }, own ? 1ull << sq : 0ull, own, drops);
     return any;
   }
-  __device__ static uint8_t end_flags(const vb::VBoard& b, bool any) {
-    const int us = b.stm, k = vb::king_sq(b, us);
-    const bool check = k >= 0 && vb::king_danger(b, k, us, vb::occupied(b));
-    return (uint8_t)((any ? 0 : kFinalNoMoves) | (check ? kFinalCheck : 0) | (k < 0 ? kFinalExtinct : 0));
+  __device__ static uint8_t end_flags(const vb::VBoard& b, bool any) { return vb::end_flags(b, any); }
+};
+
+// kingofthehill / racingkings (V): the chess rule set with
+//  * fnnue_vpos records (the chess record, empty pockets),
+//  * vboard.h's FEN acceptance for them (racingkings: no pawns, no castling
+//    rights) and match_uci's token rules (promotion letters in either case),
+//  * the variant's legality: nothing is legal in a finished position, and no
+//    racingkings move gives check,
+//  * the variant's game-end flags.
+// Scalars, Win, window, lane_chain, fix, advance and board_from are ChessRules'.
+template <int V>
+struct PlainRules : ChessRules {
+  using Pos = fnnue_vpos;
+  __device__ static fnnue_vpos widen(const fnnue_pos& p) {
+    uint32_t q[12];
+    memcpy(q, &p, sizeof(p));
+    q[9] = q[10] = q[11] = 0;
+    fnnue_vpos v;
+    memcpy(&v, q, sizeof(v));
+    return v;
+  }
+  __device__ static fnnue_vpos pack(const DBoard& b) { return widen(fnnue::pack(b)); }
+  __device__ static fnnue_vpos pack_from(const uint32_t (&w)[16], const Scalars& sc) {
+    return widen(ChessRules::pack_from(w, sc));
+  }
+  __device__ static const char* start_fen(int) {
+    return V == kVariantRacingKings ? "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1" : ChessRules::start_fen(0);
+  }
+  __device__ static uint32_t start_fen_len(int) { return V == kVariantRacingKings ? 39 : 56; }
+  __device__ static DBoard start_board(int) {
+    if constexpr (V != kVariantRacingKings) return ChessRules::start_board(0);
+    DBoard b;
+    b.bc[WHITE] = 0xF0F0ull;
+    b.bc[BLACK] = 0x0F0Full;
+    b.bt[0] = b.bt[PAWN] = 0;
+    b.bt[KNIGHT] = 0x1818ull;
+    b.bt[BISHOP] = 0x2424ull;
+    b.bt[ROOK] = 0x4242ull;
+    b.bt[QUEEN] = 0x0081ull;
+    b.bt[KING] = 0x8100ull;
+    b.cr = 0xFFFFFFFFu;
+    b.ep = -1;
+    b.stm = WHITE;
+    b.c960 = 0;
+    return b;
+  }
+  __device__ static bool parse_fen(const char* t, uint32_t p, uint32_t e, int, DBoard& b) {
+    if (!fnnue::parse_fen(t, p, e, b)) return false;
+    if (V == kVariantRacingKings && (b.bt[PAWN] || b.cr != 0xFFFFFFFFu)) return false;
+    // vboard.h takes an en-passant square only while it is empty
+    if (b.ep >= 0 && (((b.bc[0] | b.bc[1]) >> b.ep) & 1)) b.ep = -1;
+    return true;
+  }
+  __device__ static uint32_t encode(const char* c, int len) {
+    const int from = replay::tok_sq(c[0], c[1]), to = replay::tok_sq(c[2], c[3]);
+    if (from < 0 || to < 0) return replay::kTokBad;
+    int promo = 0;
+    if (len == 5) {
+      promo = vb::piece_type_of(c[4]);
+      if (!promo || promo == vb::PAWN || promo == vb::KING) return replay::kTokBad;
+    }
+    return (uint32_t)from | ((uint32_t)to << 6) | ((uint32_t)promo << 12);
+  }
+  __device__ static bool verify(const DBoard& b, const DMove& m) {
+    return !plain_over<V>(b) && pseudo_member(b, m) && legal<V>(b, m);
+  }
+  __device__ static bool any_legal_from(const DBoard& b, int sq, bool) {
+    if (!((colour(b, b.stm) >> sq) & 1)) return false;
+    bool any = false;
+    const DBoard c = b;  // a copy for the by-reference generator: the chain's board stays in registers
+    for_each_legal<V>(c, [&](const DMove&) -> bool {
+      any = true;
+      return false;
+    }, 1ull << sq);
+    return any;
+  }
+  // vb::end_flags: decided by the variant's rule unless both racingkings kings are home (a draw)
+  __device__ static uint8_t end_flags(const DBoard& b, bool any) {
+    const uint64_t home = b.bt[KING] & 0xFF00000000000000ull;
+    const bool draw = V == kVariantRacingKings && (home & b.bc[0]) && (home & b.bc[1]);
+    return (uint8_t)(ChessRules::end_flags(b, any) | (plain_over<V>(b) && !draw ? kFinalVariant : 0));
   }
 };
+
+// CHILDREN of the plain variants, one thread per ply, in vb::for_each_legal's
+// order (own pieces by square; a pawn's push, double push, captures, en
+// passant; castling king side, queen side: chess_rules.h for_each_legal).
+template <int V>
+__global__ void pcount_children_kernel(const DBoard* __restrict__ states, uint32_t n, uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DBoard b = states[i];
+  uint32_t c = 0;
+  for_each_legal<V>(b, [&](const DMove&) -> bool {
+    ++c;
+    return true;
+  });
+  cnt[i] = 1u + c;
+}
+
+template <int V>
+__global__ void pwrite_children_kernel(const DBoard* __restrict__ states, uint32_t n, const uint32_t* __restrict__ off,
+                                       fnnue_vpos* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DBoard b = states[i];
+  uint32_t o = off[i];
+  out[o++] = PlainRules<V>::pack(b);
+  for_each_legal<V>(b, [&](const DMove& m) -> bool {
+    DBoard c = b;
+    do_move(c, m);
+    out[o++] = PlainRules<V>::pack(c);
+    return true;
+  });
+}
 
 __global__ void vcount_children_kernel(const vb::VBoard* __restrict__ states, uint32_t n, uint32_t* __restrict__ cnt) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -347,6 +465,15 @@ __global__ void vwrite_children_kernel(const vb::VBoard* __restrict__ states, ui
 hipError_t replay_vgames_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                 const uint32_t* d_ply_off, uint32_t ngames, fnnue_vpos* d_out, void* d_states,
                                 uint8_t* d_final, uint32_t* d_err, hipStream_t s) {
+  // d_states: DBoard for kingofthehill / racingkings, vb::VBoard otherwise
+  if (variant == kVariantKingOfTheHill)
+    return replay::launch_replay<PlainRules<kVariantKingOfTheHill>>(variant, d_text, d_fen_off, d_mv_off, ngames,
+                                                                    d_ply_off, d_out, static_cast<DBoard*>(d_states),
+                                                                    d_err, d_final, s);
+  if (variant == kVariantRacingKings)
+    return replay::launch_replay<PlainRules<kVariantRacingKings>>(variant, d_text, d_fen_off, d_mv_off, ngames,
+                                                                  d_ply_off, d_out, static_cast<DBoard*>(d_states),
+                                                                  d_err, d_final, s);
   return replay::launch_replay<VariantRules>(variant, d_text, d_fen_off, d_mv_off, ngames, d_ply_off, d_out,
                                              static_cast<vb::VBoard*>(d_states), d_err, d_final, s);
 }
@@ -361,7 +488,9 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
   };
   hipError_t e;
   uint32_t *plies = nullptr, *ply_off = nullptr, *err = nullptr, *cnt = nullptr, *coff = nullptr;
-  vb::VBoard* states = nullptr;
+  void* states = nullptr;
+  const bool plain = variant == kVariantKingOfTheHill || variant == kVariantRacingKings;
+  const size_t state_bytes = plain ? sizeof(DBoard) : sizeof(vb::VBoard);
   using W = BuilderScratch;
   if ((e = ws.get(W::kPlies, (size_t)(ngames + 1) * 4, (void**)&plies)) != hipSuccess) return fail(e);
   if ((e = ws.get(W::kPlyOff, (size_t)(ngames + 1) * 4, (void**)&ply_off)) != hipSuccess) return fail(e);
@@ -390,7 +519,7 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
         hipSuccess)
       return fail(e);
   } else {
-    if ((e = ws.get(W::kStates, (size_t)total_plies * sizeof(vb::VBoard), (void**)&states)) != hipSuccess)
+    if ((e = ws.get(W::kStates, (size_t)total_plies * state_bytes, &states)) != hipSuccess)
       return fail(e);
     if ((e = ws.get(W::kCnt, (size_t)(total_plies + 1) * 4, (void**)&cnt)) != hipSuccess) return fail(e);
     if ((e = ws.get(W::kCoff, (size_t)(total_plies + 1) * 4, (void**)&coff)) != hipSuccess) return fail(e);
@@ -407,8 +536,16 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
       return R;
     }
     if ((e = hipMemsetAsync(cnt + total_plies, 0, 4, s)) != hipSuccess) return fail(e);
-    hipLaunchKernelGGL(vcount_children_kernel, dim3((total_plies + bs - 1) / bs), dim3(bs), 0, s, states,
-                       total_plies, cnt);
+    const dim3 cgrid((total_plies + bs - 1) / bs);
+    if (variant == kVariantKingOfTheHill)
+      hipLaunchKernelGGL(pcount_children_kernel<kVariantKingOfTheHill>, cgrid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(states), total_plies, cnt);
+    else if (variant == kVariantRacingKings)
+      hipLaunchKernelGGL(pcount_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(states), total_plies, cnt);
+    else
+      hipLaunchKernelGGL(vcount_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),
+                         total_plies, cnt);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e);
     if ((e = builder_exclusive_scan(cnt, coff, total_plies, s, ws)) != hipSuccess) return fail(e);
     uint32_t total = 0;
@@ -420,8 +557,15 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
       R.capacity = true;
       return R;
     }
-    hipLaunchKernelGGL(vwrite_children_kernel, dim3((total_plies + bs - 1) / bs), dim3(bs), 0, s, states,
-                       total_plies, coff, d_out);
+    if (variant == kVariantKingOfTheHill)
+      hipLaunchKernelGGL(pwrite_children_kernel<kVariantKingOfTheHill>, cgrid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(states), total_plies, coff, d_out);
+    else if (variant == kVariantRacingKings)
+      hipLaunchKernelGGL(pwrite_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(states), total_plies, coff, d_out);
+    else
+      hipLaunchKernelGGL(vwrite_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),
+                         total_plies, coff, d_out);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(d_group_off, coff, (size_t)(total_plies + 1) * 4, hipMemcpyDeviceToDevice, s)) !=
         hipSuccess)

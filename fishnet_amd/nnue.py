@@ -39,7 +39,8 @@ class Net:
 
     @classmethod
     def load_variant(cls, path: str, variant: int) -> "Net":
-        """A Fairy-Stockfish variant net (VARIANT_CRAZYHOUSE / VARIANT_ATOMIC)."""
+        """A Fairy-Stockfish variant net (VARIANT_CRAZYHOUSE / VARIANT_ATOMIC /
+        VARIANT_KINGOFTHEHILL / VARIANT_RACINGKINGS; the last three share one file format)."""
         h = C.c_void_p()
         N.check(N.lib.fnnue_net_load_variant(path.encode(), variant, C.byref(h)))
         return cls(h.value)
@@ -169,6 +170,7 @@ def game_vchildren(variant: int, fen: str, moves: str | list[str]) -> tuple[np.n
 
 
 END_NO_MOVES, END_CHECK, END_EXTINCT = 1, 2, 4
+END_VARIANT = 8  # the side to move has lost by the variant's own rule (kingofthehill, racingkings)
 
 
 def game_end(fen: str, moves: str | list[str] = "", variant: int = 0) -> int:

@@ -121,16 +121,25 @@ void fnnue_buffer_free(void *buf);
 #define FNNUE_VARIANT_CHESS 0
 #define FNNUE_VARIANT_CRAZYHOUSE 1 /* 64 x (704 board + 160 hand) features */
 #define FNNUE_VARIANT_ATOMIC 2     /* 64 x 704 board features (also kingofthehill, racingkings) */
+/* The board-only feature set of atomic with the variant's own rules (no
+ * explosions, one king per side always: a position without is
+ * FNNUE_E_POSITION).  kingofthehill: chess, over with a king on d4 e4 d5 e5.
+ * racingkings: start 8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1, no pawns and no
+ * castling rights (such a FEN is FNNUE_E_FEN), no move gives check, over with
+ * a king on rank 8 unless black may still catch up. */
+#define FNNUE_VARIANT_KINGOFTHEHILL 3
+#define FNNUE_VARIANT_RACINGKINGS 4
 int fnnue_net_load_variant(const char *path, int variant, fnnue_net **out);
 int fnnue_net_load_variant_mem(const void *buf, size_t len, int variant, fnnue_net **out);
 int fnnue_net_variant(const fnnue_net *net, int *variant);
 int fnnue_net_synthesize_variant(uint64_t seed, uint32_t hd, int variant, uint32_t flags, void **buf, size_t *len);
 /* FEN (crazyhouse holdings as "[PNbq]" after the placement or as a 9th
- * placement field; "~" promotion marks ignored) -> packed variant position. */
+ * placement field; "~" promotion marks ignored; kingofthehill / racingkings:
+ * plain chess FENs, holdings and marks refused) -> packed variant position. */
 int fnnue_vpos_from_fen(int variant, const char *fen, fnnue_vpos *out);
-/* Test inputs: `count` seeded pseudo-legal random walks from the start
- * position (captures go to the capturer's hand and drops come back out for
- * crazyhouse; captures explode for atomic, kings never removed), up to
+/* Test inputs: `count` seeded pseudo-legal random walks from the variant's
+ * start position (captures go to the capturer's hand and drops come back out
+ * for crazyhouse; captures explode for atomic, kings never removed), up to
  * max_plies each.  FNNUE_PLAYOUT_FINAL: the last position of each walk;
  * FNNUE_PLAYOUT_PLIES: every position as CHAIN groups (off[], n_groups + 1). */
 int fnnue_random_vpositions(uint64_t seed, int variant, size_t count, uint32_t max_plies, int mode, fnnue_vpos *out,
@@ -138,9 +147,11 @@ int fnnue_random_vpositions(uint64_t seed, int variant, size_t count, uint32_t m
 /* Variant games (the expansion of IncomingBatch::from_acquired for the
  * variants the reference sends to Fairy-Stockfish, [ref] src/queue.rs:524-552,
  * :530-539): crazyhouse FENs with holdings / promoted marks and UCI moves with
- * drops ("P@e4"), atomic captures with explosions; every move checked for
- * legality in its variant (shakmaty's Uci::to_move).  Host replay: the root and
- * the position after every move (n_moves + 1 records). */
+ * drops ("P@e4"), atomic captures with explosions, kingofthehill and
+ * racingkings games (no move after the game's end, no racingkings check);
+ * every move checked for legality in its variant (shakmaty's Uci::to_move).
+ * Host replay: the root and the position after every move (n_moves + 1
+ * records). */
 int fnnue_game_vpositions(int variant, const char *fen, const char *moves, fnnue_vpos *out, size_t cap,
                           size_t *n_out);
 /* Same plus every legal 1-ply child (drops included) of each position, as STAR
@@ -150,7 +161,8 @@ int fnnue_game_vchildren(int variant, const char *fen, const char *moves, fnnue_
 /* perft of the variant move generator (known answers pin it). */
 int fnnue_vperft(int variant, const char *fen, int depth, uint64_t *nodes);
 /* Up to `plies` uniformly random legal moves (drops included) from `fen`, as
- * space-separated UCI; stops when no move is left or a king exploded. */
+ * space-separated UCI; stops when no move is left (mate, stalemate, the
+ * variant's end of the game) or a king exploded. */
 int fnnue_random_vgame(uint64_t seed, int variant, const char *fen, uint32_t plies, char *moves, size_t cap,
                        size_t *len);
 /* Test / bench inputs: every ply of `count` seeded random LEGAL games of the
@@ -318,13 +330,17 @@ int fnnue_game_positions(const char *fen, const char *moves, fnnue_pos *out, siz
 int fnnue_game_children(const char *fen, const char *moves, fnnue_pos *out, size_t cap, uint32_t *off,
                         size_t off_cap, size_t *n_out, size_t *n_groups);
 /* Has the game ended on the board after `moves`?  *flags = FNNUE_END_*: no
- * legal move, the side to move's king attacked, its king exploded (atomic).
+ * legal move, the side to move's king attacked, its king exploded (atomic),
+ * the side to move has lost by the variant's own rule (kingofthehill: the
+ * other king on the hill; racingkings: one king on rank 8 — the racingkings
+ * draw with both kings there is FNNUE_END_NO_MOVES alone).
  * A position without a legal move is where the engine answers `score mate 0`
- * (checkmate / explosion) or `score cp 0` (stalemate) with `bestmove (none)`
+ * (checkmate / explosion / variant loss) or `score cp 0` (stalemate, draw) with `bestmove (none)`
  * ([ref] src/stockfish.rs:359-376).  variant: FNNUE_VARIANT_* (host replay). */
 #define FNNUE_END_NO_MOVES 1
 #define FNNUE_END_CHECK 2
 #define FNNUE_END_EXTINCT 4
+#define FNNUE_END_VARIANT 8
 int fnnue_game_end(int variant, const char *fen, const char *moves, int *flags);
 /* Seeded random playouts from the start position (splitmix64; L ~ U[min,max]
  * plies of uniformly random legal moves, stopping at mate, stalemate or the

@@ -121,6 +121,12 @@ typedef struct {
  * freed after the call. */
 int fnnue_backend_channel_nets(const fnnue_backend_nets *nets, int device, const fnnue_backend_init *init,
                                fnnue_backend **out);
+/* Any set of nets, each going to the slot of its own variant
+ * (fnnue_net_variant: chess, crazyhouse, atomic, kingofthehill, racingkings;
+ * fnnue_backend_nets keeps its three members, its size being ABI).  n >= 1;
+ * two nets of one variant: FNNUE_E_ARG. */
+int fnnue_backend_channel_netv(const fnnue_net *const *nets, size_t n, int device, const fnnue_backend_init *init,
+                               fnnue_backend **out);
 /* The one-net form: the net goes to the slot of its variant. */
 int fnnue_backend_channel(const fnnue_net *net, int device, const fnnue_backend_init *init, fnnue_backend **out);
 /* Stops the actor (after the call in flight) and frees it.  Never waits for
