@@ -19,7 +19,7 @@ ERRORS = {
     -5: "FNNUE_E_DEVICE", -6: "FNNUE_E_POSITION", -7: "FNNUE_E_OOM", -8: "FNNUE_E_MOVE",
     -9: "FNNUE_E_FEN", -10: "FNNUE_E_CAPACITY", -11: "FNNUE_E_TIMEOUT",
 }
-SYNTH_LEB128, SYNTH_WRAP, SYNTH_FC1_PAD = 1, 2, 4
+SYNTH_LEB128, SYNTH_WRAP, SYNTH_FC1_PAD, SYNTH_HEAVY = 1, 2, 4, 8
 GROUP_CHAIN, GROUP_STAR = 0, 1
 TIMING_OFF, TIMING_ALL, TIMING_FT = 0, 1, 2  # fnnue_ctx_set_timing
 FT_SLICED, FT_GATHER, FT_AUTO = 0, 1, 2
@@ -93,6 +93,9 @@ SIGNATURES = {
     "fnnue_net_accumulator_bound": ([_vp, _P(C.c_int32)], _i32),
     "fnnue_ctx_swar": ([_vp, _P(_i32), _P(C.c_int32)], _i32),
     "fnnue_ctx_set_swar": ([_vp, _i32], _i32),
+    "fnnue_net_slice_bounds": ([_vp, _P(C.c_int32), _sz, _P(_sz)], _i32),
+    "fnnue_ctx_swar_slices": ([_vp, _P(_u64), _P(_u64), _P(_u32)], _i32),
+    "fnnue_ctx_set_swar_slices": ([_vp, _u64], _i32),
     "fnnue_ctx_timing_read": ([_vp, _P(_u32), _P(C.c_double), _P(C.c_double)], _i32),
     "fnnue_ctx_timing_phases": ([_vp, _P(_u32), _P(C.c_double), _P(C.c_double), _P(C.c_double)], _i32),
     "fnnue_build_batch_device": ([_vp, _vp, _vp, _vp, _sz, _i32, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),

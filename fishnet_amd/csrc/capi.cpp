@@ -238,8 +238,9 @@ int name_invalid(int rc, const fnnue_pos* pos, size_t n) {
 
 // Derives the LDS-tile layout of the FT weights from the (just uploaded) image.
 int finish_upload(fnnue_ctx* c) {
-  // May ft_slices sum rows as SWAR words?  Decided from the weights on the
-  // device (they may come from an RCCL broadcast): a one-off host copy.
+  // Which slices may ft_slices sum as SWAR words?  Decided per slice from the
+  // weights on the device (they may come from an RCCL broadcast): a one-off
+  // host copy.
   {
     const ImageLayout L = image_layout(c->hd, c->nfeat);
     std::vector<int16_t> w, b;
@@ -251,9 +252,16 @@ int finish_upload(fnnue_ctx* c) {
     }
     HIP_TRY(hipMemcpy(w.data(), c->image + L.ft_w, w.size() * 2, hipMemcpyDeviceToHost), "hipMemcpy(ft weights)");
     HIP_TRY(hipMemcpy(b.data(), c->image + L.ft_bias, b.size() * 2, hipMemcpyDeviceToHost), "hipMemcpy(ft bias)");
-    c->acc_bound = accumulator_bound(w.data(), b.data(), c->hd, c->variant);
+    int32_t sb[64];
+    slice_bounds(w.data(), b.data(), c->hd, c->variant, sb);
+    c->acc_bound = 0;
+    c->swar_eligible = 0;
+    for (uint32_t s = 0; s < c->hd / 64; ++s) {
+      c->acc_bound = std::max(c->acc_bound, sb[s]);
+      if (sb[s] < 32768) c->swar_eligible |= uint64_t(1) << s;
+    }
     const char* env = std::getenv("FNNUE_SWAR");
-    c->plan.swar = c->acc_bound < 32768 && !(env && env[0] == '0');
+    c->plan.swar = env && env[0] == '0' ? 0 : c->swar_eligible;
   }
   if (c->variant == kVariantChess)
     HIP_TRY(launch_relayout_sliced(c->hd, c->ptrs, c->plan.tiles, c->stream), "relayout launch");
@@ -381,7 +389,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.1: fnnue_backend_go_timeout, FNNUE_E_TIMEOUT
 // 3.2: FNNUE_VARIANT_KINGOFTHEHILL / FNNUE_VARIANT_RACINGKINGS accepted wherever a variant id is,
 //      FNNUE_END_VARIANT, fnnue_backend_channel_netv
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 2u; }
+// 3.3: SWAR decided per slice: fnnue_net_slice_bounds, fnnue_ctx_swar_slices, fnnue_ctx_set_swar_slices,
+//      FNNUE_SYNTH_HEAVY
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 3u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -628,9 +638,36 @@ int fnnue_ctx_swar(const fnnue_ctx* ctx, int* enabled, int32_t* bound) {
 
 int fnnue_ctx_set_swar(fnnue_ctx* ctx, int enable) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (enable && ctx->acc_bound >= 32768)
-    return fail(FNNUE_E_ARCH, "accumulator bound " + std::to_string(ctx->acc_bound) + " >= 2^15: SWAR rows not exact");
-  ctx->plan.swar = enable != 0;
+  if (enable && !ctx->swar_eligible)
+    return fail(FNNUE_E_ARCH, "accumulator bound " + std::to_string(ctx->acc_bound) +
+                                  " >= 2^15 in every slice: SWAR rows not exact");
+  ctx->plan.swar = enable ? ctx->swar_eligible : 0;
+  return FNNUE_OK;
+}
+
+int fnnue_ctx_swar_slices(const fnnue_ctx* ctx, uint64_t* eligible, uint64_t* enabled, uint32_t* nslices) {
+  if (!ctx || !eligible || !enabled || !nslices) return fail(FNNUE_E_ARG, "null argument");
+  *eligible = ctx->swar_eligible;
+  *enabled = ctx->plan.swar;
+  *nslices = ctx->hd / 64;
+  return FNNUE_OK;
+}
+
+int fnnue_ctx_set_swar_slices(fnnue_ctx* ctx, uint64_t mask) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  const uint32_t ns = ctx->hd / 64;
+  if (ns < 64 && (mask >> ns)) return fail(FNNUE_E_ARG, "the net has " + std::to_string(ns) + " slices");
+  if (mask & ~ctx->swar_eligible)
+    return fail(FNNUE_E_ARCH, "slice bound >= 2^15: SWAR rows not exact (eligible slices: fnnue_ctx_swar_slices)");
+  ctx->plan.swar = mask;
+  return FNNUE_OK;
+}
+
+int fnnue_net_slice_bounds(const fnnue_net* net, int32_t* bounds, size_t cap, size_t* nslices) {
+  if (!net || !bounds || !nslices) return fail(FNNUE_E_ARG, "null argument");
+  *nslices = net->net.hd / 64;
+  if (cap < *nslices) return fail(FNNUE_E_ARG, "bounds: room for " + std::to_string(*nslices) + " slices needed");
+  slice_bounds(net->net.ft_w.data(), net->net.ft_bias.data(), net->net.hd, net->net.variant, bounds);
   return FNNUE_OK;
 }
 
@@ -821,7 +858,7 @@ int eval_groups_dual_device(fnnue_ctx* a, fnnue_ctx* b, const fnnue_pos* d_pos, 
           "group_span launch");
   const uint2* span = static_cast<const uint2*>(a->seg.span);
   const uint32_t chunk = std::min(a->chunk, b->chunk);
-  // the small net over the big context's plan: its own tiles, SWAR flag and PSQT parts
+  // the small net over the big context's plan: its own tiles, SWAR mask and PSQT parts
   SlicedPlan pb = a->plan;
   pb.tiles = b->plan.tiles;
   pb.swar = b->plan.swar;

@@ -983,19 +983,20 @@ __device__ __forceinline__ void seg_task(SegLds<Fs>& L, const SegNet& net, int s
   }
 }
 
-template <int HD, bool kStar, bool kSwar, class Fs>
-__global__ __launch_bounds__(1024) void ft_segments_kernel(const uint4* __restrict__ tiles,
-                                                           const int16_t* __restrict__ ftb,
-                                                           const uint32_t* __restrict__ ctr,
-                                                           const int4* __restrict__ units,
-                                                           const uint4* __restrict__ items,
-                                                           const uint16_t* __restrict__ flist,
-                                                           const uint4* __restrict__ drec, uint32_t n,
-                                                           const int32_t* __restrict__ psqw,
-                                                           int32_t* __restrict__ psqt_part,
-                                                           uint8_t* __restrict__ x) {
+// Grid-stride over (unit, slice) tasks.  kSwar: 0 packed int16 rows, 1 SWAR
+// rows, 2 mixed: bit s of `swar` says which of the two slice s runs (a net
+// whose slices do not all pass the SWAR bound, slice_bounds in net.h); the
+// slice is the task's, so the branch is scalar, once per task.
+constexpr int kSwarMixed = 2;
+template <int HD, bool kStar, int kSwar, class Fs>
+__device__ __forceinline__ void ft_segments_body(SegLds<Fs>& L, const uint4* __restrict__ tiles,
+                                                 const int16_t* __restrict__ ftb, const uint32_t* __restrict__ ctr,
+                                                 const int4* __restrict__ units, const uint4* __restrict__ items,
+                                                 const uint16_t* __restrict__ flist, const uint4* __restrict__ drec,
+                                                 uint32_t n, const int32_t* __restrict__ psqw,
+                                                 int32_t* __restrict__ psqt_part, uint8_t* __restrict__ x,
+                                                 uint64_t swar) {
   constexpr int S = HD / 64;
-  __shared__ SegLds<Fs> L;
   const SegNet net = seg_net<HD>(tiles, ftb, psqw, psqt_part, x, n);
   const __amdgpu_buffer_rsrc_t items_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(items), 0, kBufferAll, kBufferFlags);
@@ -1011,8 +1012,48 @@ __global__ __launch_bounds__(1024) void ft_segments_kernel(const uint4* __restri
     const uint32_t j = w >> 3;
     const uint32_t unit = (j / S) * 8 + (w & 7);
     if (unit >= nunits) return;
-    seg_task<HD, kStar, kSwar, Fs>(L, net, (int)(j % S), units[unit], n, items_rsrc, flist_rsrc, drec_rsrc);
+    const int s = (int)(j % S);
+    if constexpr (kSwar == kSwarMixed) {
+      if ((swar >> s) & 1)
+        seg_task<HD, kStar, true, Fs>(L, net, s, units[unit], n, items_rsrc, flist_rsrc, drec_rsrc);
+      else
+        seg_task<HD, kStar, false, Fs>(L, net, s, units[unit], n, items_rsrc, flist_rsrc, drec_rsrc);
+    } else {
+      seg_task<HD, kStar, kSwar != 0, Fs>(L, net, s, units[unit], n, items_rsrc, flist_rsrc, drec_rsrc);
+    }
   }
+}
+
+template <int HD, bool kStar, bool kSwar, class Fs>
+__global__ __launch_bounds__(1024) void ft_segments_kernel(const uint4* __restrict__ tiles,
+                                                           const int16_t* __restrict__ ftb,
+                                                           const uint32_t* __restrict__ ctr,
+                                                           const int4* __restrict__ units,
+                                                           const uint4* __restrict__ items,
+                                                           const uint16_t* __restrict__ flist,
+                                                           const uint4* __restrict__ drec, uint32_t n,
+                                                           const int32_t* __restrict__ psqw,
+                                                           int32_t* __restrict__ psqt_part,
+                                                           uint8_t* __restrict__ x) {
+  __shared__ SegLds<Fs> L;
+  ft_segments_body<HD, kStar, kSwar ? 1 : 0, Fs>(L, tiles, ftb, ctr, units, items, flist, drec, n, psqw, psqt_part, x,
+                                                 0);
+}
+
+template <int HD, bool kStar, class Fs>
+__global__ __launch_bounds__(1024) void ft_segments_mixed_kernel(const uint4* __restrict__ tiles,
+                                                                 const int16_t* __restrict__ ftb,
+                                                                 const uint32_t* __restrict__ ctr,
+                                                                 const int4* __restrict__ units,
+                                                                 const uint4* __restrict__ items,
+                                                                 const uint16_t* __restrict__ flist,
+                                                                 const uint4* __restrict__ drec, uint32_t n,
+                                                                 const int32_t* __restrict__ psqw,
+                                                                 int32_t* __restrict__ psqt_part,
+                                                                 uint8_t* __restrict__ x, uint64_t swar) {
+  __shared__ SegLds<Fs> L;
+  ft_segments_body<HD, kStar, kSwarMixed, Fs>(L, tiles, ftb, ctr, units, items, flist, drec, n, psqw, psqt_part, x,
+                                              swar);
 }
 
 template <int HD, class Fs>
@@ -1021,15 +1062,21 @@ hipError_t ft_segments_t(const SegPlan& G, const SlicedPlan& P, const NetPtrs& n
   constexpr int S = HD / 64;
   // grid = 8 * S * G (see the kernel's grid stride); up to 8 * 64 units per sweep
   const uint32_t groups = min((max_units + 7) / 8, 64u);
-  auto launch = [&](auto kern) {
+  auto launch = [&](auto kern, auto... mask) {
     hipLaunchKernelGGL(kern, dim3(groups * 8 * S), dim3(1024), 0, stream, (const uint4*)P.tiles, net.ft_bias, P.ctr,
                        (const int4*)P.units, (const uint4*)G.items, P.flist, (const uint4*)G.drec, n, net.psqt_w,
-                       P.psqt_part, x);
+                       P.psqt_part, x, mask...);
   };
+  const uint64_t all = (uint64_t(1) << S) - 1;  // S <= 48
+  const int mode = (P.swar & all) == all ? 1 : (P.swar & all) == 0 ? 0 : kSwarMixed;
   if (star)
-    P.swar ? launch(ft_segments_kernel<HD, true, true, Fs>) : launch(ft_segments_kernel<HD, true, false, Fs>);
+    mode == 1   ? launch(ft_segments_kernel<HD, true, true, Fs>)
+    : mode == 0 ? launch(ft_segments_kernel<HD, true, false, Fs>)
+                : launch(ft_segments_mixed_kernel<HD, true, Fs>, P.swar);
   else
-    P.swar ? launch(ft_segments_kernel<HD, false, true, Fs>) : launch(ft_segments_kernel<HD, false, false, Fs>);
+    mode == 1   ? launch(ft_segments_kernel<HD, false, true, Fs>)
+    : mode == 0 ? launch(ft_segments_kernel<HD, false, false, Fs>)
+                : launch(ft_segments_mixed_kernel<HD, false, Fs>, P.swar);
   return hipGetLastError();
 }
 

@@ -168,26 +168,28 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
   }
 }
 
+// The LDS of a workgroup (tile, PSQT tile, one list buffer per wave), declared
+// by the kernel so that the mixed kernel's two bodies share one copy.
+#define FT_SLICES_LDS(G)                                                                                      \
+  __shared__ uint4 img[G::kTileU4];                                                                           \
+  __shared__ int32_t ptile[G::kTileRows * kPsqtBuckets]; /* slice 0 only: PSQT rows of the king block */      \
+  __shared__ uint2 lbuf[16][64];                         /* per wave: one pass's 8 feature lists */
+
 // One workgroup = one (unit, slice).  16 waves x 8 items per pass; records and
 // lists are fetched two passes ahead while the current pass reads the LDS tile.
 // Items of a unit are sorted by piece count, so a pass's longest list is that
 // of its item 7 (clamped into the unit).  kSwar: the tile is converted to SWAR
 // words on its way into LDS and rows are summed as 32-bit words (swar_tile_words).
-template <int HD, bool kSwar, class G = ChessGeom>
-__global__ __launch_bounds__(1024) void ft_slices_kernel(const uint4* __restrict__ tiles,
-                                                         const int16_t* __restrict__ ftb,
-                                                         const uint32_t* __restrict__ ctr,
-                                                         const int4* __restrict__ units,
-                                                         const uint32_t* __restrict__ items,
-                                                         const uint16_t* __restrict__ flist,
-                                                         const int32_t* __restrict__ psqw,
-                                                         int32_t* __restrict__ psqt_part,
-                                                         uint8_t* __restrict__ x) {
+// Tiles sit in HBM as plain int16 either way, so the choice is the slice's own.
+template <int HD, bool kSwar, class G>
+__device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2 (*lbuf)[64],
+                                               const uint4* __restrict__ tiles,
+                                               const int16_t* __restrict__ ftb, const uint32_t* __restrict__ ctr,
+                                               const int4* __restrict__ units, const uint32_t* __restrict__ items,
+                                               const uint16_t* __restrict__ flist, const int32_t* __restrict__ psqw,
+                                               int32_t* __restrict__ psqt_part, uint8_t* __restrict__ x) {
   constexpr int S = HD / 64;
   constexpr int kTileU4 = G::kTileU4;
-  __shared__ uint4 img[kTileU4];
-  __shared__ int32_t ptile[G::kTileRows * kPsqtBuckets];  // slice 0 only: PSQT rows of the king block
-  __shared__ uint2 lbuf[16][64];                       // per wave: one pass's 8 feature lists
   const uint32_t w = blockIdx.x;
   const uint32_t j = w >> 3;
   const uint32_t unit = (j / S) * 8 + (w & 7);
@@ -281,6 +283,42 @@ __global__ __launch_bounds__(1024) void ft_slices_kernel(const uint4* __restrict
     run(std::false_type{});
 }
 
+template <int HD, bool kSwar, class G = ChessGeom>
+__global__ __launch_bounds__(1024) void ft_slices_kernel(const uint4* __restrict__ tiles,
+                                                         const int16_t* __restrict__ ftb,
+                                                         const uint32_t* __restrict__ ctr,
+                                                         const int4* __restrict__ units,
+                                                         const uint32_t* __restrict__ items,
+                                                         const uint16_t* __restrict__ flist,
+                                                         const int32_t* __restrict__ psqw,
+                                                         int32_t* __restrict__ psqt_part,
+                                                         uint8_t* __restrict__ x) {
+  FT_SLICES_LDS(G)
+  ft_slices_body<HD, kSwar, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+}
+
+// A net whose slices do not all pass the SWAR bound (slice_bounds in net.h):
+// bit s of `swar` says which body slice s runs.  The slice is the workgroup's,
+// so the branch is scalar and taken once; both bodies work in the same LDS.
+template <int HD, class G = ChessGeom>
+__global__ __launch_bounds__(1024) void ft_slices_mixed_kernel(const uint4* __restrict__ tiles,
+                                                               const int16_t* __restrict__ ftb,
+                                                               const uint32_t* __restrict__ ctr,
+                                                               const int4* __restrict__ units,
+                                                               const uint32_t* __restrict__ items,
+                                                               const uint16_t* __restrict__ flist,
+                                                               const int32_t* __restrict__ psqw,
+                                                               int32_t* __restrict__ psqt_part,
+                                                               uint8_t* __restrict__ x, uint64_t swar) {
+  constexpr int S = HD / 64;
+  FT_SLICES_LDS(G)
+  const uint32_t s = (blockIdx.x >> 3) % S;
+  if ((swar >> s) & 1)
+    ft_slices_body<HD, true, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+  else
+    ft_slices_body<HD, false, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+}
+
 template <int HD>
 hipError_t relayout_t(const NetPtrs& net, void* tiles, hipStream_t stream) {
   hipLaunchKernelGGL((relayout_kernel<HD>), dim3(2048), dim3(256), 0, stream, net.ft_w, (uint4*)tiles);
@@ -291,14 +329,19 @@ template <int HD, class G = ChessGeom>
 hipError_t ft_slices_t(const SlicedPlan& P, const NetPtrs& net, uint8_t* x, uint32_t max_units, hipStream_t stream) {
   constexpr int S = HD / 64;
   const uint32_t groups = (max_units + 7) / 8;
-  if (P.swar)
+  const uint64_t all = (uint64_t(1) << S) - 1;  // S <= 48
+  if ((P.swar & all) == all)
     hipLaunchKernelGGL((ft_slices_kernel<HD, true, G>), dim3(groups * 8 * S), dim3(1024), 0, stream,
                        (const uint4*)P.tiles, net.ft_bias, P.ctr, (const int4*)P.units, P.items, P.flist, net.psqt_w,
                        P.psqt_part, x);
-  else
+  else if ((P.swar & all) == 0)
     hipLaunchKernelGGL((ft_slices_kernel<HD, false, G>), dim3(groups * 8 * S), dim3(1024), 0, stream,
                        (const uint4*)P.tiles, net.ft_bias, P.ctr, (const int4*)P.units, P.items, P.flist, net.psqt_w,
                        P.psqt_part, x);
+  else
+    hipLaunchKernelGGL((ft_slices_mixed_kernel<HD, G>), dim3(groups * 8 * S), dim3(1024), 0, stream,
+                       (const uint4*)P.tiles, net.ft_bias, P.ctr, (const int4*)P.units, P.items, P.flist, net.psqt_w,
+                       P.psqt_part, x, P.swar);
   return hipGetLastError();
 }
 

@@ -41,7 +41,8 @@ struct fnnue_ctx {
   size_t btext_cap = 0;
   fnnue::BuilderScratch bscratch;  // the device batch builder's temporaries, grow-only
   int ft_impl = FNNUE_FT_AUTO;
-  int32_t acc_bound = 0;       // accumulator_bound of the net (SWAR rows allowed below 2^15)
+  int32_t acc_bound = 0;       // accumulator_bound of the net (the largest slice bound)
+  uint64_t swar_eligible = 0;  // bit s: slice s's bound < 2^15, SWAR rows allowed (plan.swar: the enabled ones)
   fnnue::SlicedPlan plan{};
   fnnue::SegPlan seg{};                // incremental sliced path for groups (allocated on first use)
   int timing = 0;  // FNNUE_TIMING_*: 0 off, 1 every phase, 2 the FT main kernel only

@@ -62,7 +62,7 @@ struct SlicedPlan {
   uint16_t* flist;   // [2 * chunk][32] feature rows relative to the king block
   uint32_t* perm;    // [chunk] bucket-sorted slot -> position index
   int32_t* psqt_part;// [chunk][2] per-slot PSQT sums of the stm / nstm perspective
-  bool swar;          // ft_slices may sum rows as SWAR words (accumulator_bound < 2^15)
+  uint64_t swar;     // bit s: slice s sums rows as SWAR words (slice_bounds[s] < 2^15); the others packed int16
 };
 size_t sliced_tiles_bytes(uint32_t hd);
 size_t sliced_ctr_words();
@@ -135,7 +135,7 @@ hipError_t launch_ft_segments(uint32_t hd, int variant, const void* pos, uint32_
 // Its two halves.  The plan depends on the positions, the groups and the
 // feature set only, not on the net: a second net of the same feature set (the
 // small net beside the big one) runs its main kernel over the same plan
-// (P.ctr / units / flist and G), with its own tiles, swar flag, psqt_part, x.
+// (P.ctr / units / flist and G), with its own tiles, swar mask, psqt_part, x.
 // A grouped call of at most seg_small_plan_max() positions: spans, offset
 // check and the whole plan of its one chunk in one workgroup (then
 // launch_seg_ft).

@@ -236,6 +236,24 @@ void synthesize_net(uint64_t seed, uint32_t hd, uint32_t flags, Net& net, int va
     s.b2 = (int32_t)g.range(-2000, 2000);
     for (auto& w : s.w2) w = clampT<int8_t>(g.gauss() * 40.0, -128, 127);
   }
+  if (flags & FNNUE_SYNTH_HEAVY) {
+    // A heavy tail: every third slice (s % 3 == 1) gets one column of same-sign
+    // weights over all rows and a zero bias, from a generator of its own (a
+    // function of seed and hd), so every other column is the ordinary net's.
+    // Heavy slices alternate between a second-half column (|w| 520..540: a full
+    // board passes 2^14, the doubled column wraps in a SWAR word) and an even
+    // first-half column (|w| 1100..1300: the int16 accumulator itself wraps).
+    Rng h{(seed ^ 0x48454156595F4654ull) * 0x9E3779B97F4A7C15ull + hd};
+    uint32_t k = 0;
+    for (uint32_t s = 1; s < hd / 64; s += 3, ++k) {
+      const bool second = k % 2 == 0;
+      const uint32_t col = second ? hd / 2 + 32 * s + (uint32_t)h.range(0, 31) : 32 * s + 2 * (uint32_t)h.range(0, 15);
+      const int sign = h.next() & 1 ? -1 : 1;
+      net.ft_bias[col] = 0;
+      for (uint32_t r = 0; r < net.nfeat; ++r)
+        net.ft_w[(size_t)r * hd + col] = (int16_t)(sign * (second ? h.range(520, 540) : h.range(1100, 1300)));
+    }
+  }
 }
 
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -274,7 +292,7 @@ void pack_image(const Net& net, uint8_t* dst) {
   }
 }
 
-int32_t accumulator_bound(const int16_t* ft_w, const int16_t* ft_bias, uint32_t hd, int variant) {
+void slice_bounds(const int16_t* ft_w, const int16_t* ft_bias, uint32_t hd, int variant, int32_t* bounds) {
   const int kRows = (int)(variant == kVariantChess ? kFeatures / 32 : variant_rows(variant));  // rows per king block
   const int kBlocks = variant == kVariantChess ? 32 : 64;
   // Columns a SWAR word's exactness depends on: the first half's even columns
@@ -284,7 +302,7 @@ int32_t accumulator_bound(const int16_t* ft_w, const int16_t* ft_bias, uint32_t 
   for (uint32_t c = 0; c < hd / 2; c += 2) cols.push_back(c);
   for (uint32_t c = hd / 2; c < hd; ++c) cols.push_back(c);
   const size_t ncol = cols.size();
-  int64_t worst = 0;
+  std::vector<int64_t> worst(hd / 64, 0);
   std::vector<int32_t> mag(ncol * kRows);  // [column][row], |w|
   for (int kb = 0; kb < kBlocks; ++kb) {
     // own-king row of king block kb: plane 10, oriented king square on files e-h
@@ -300,10 +318,19 @@ int32_t accumulator_bound(const int16_t* ft_w, const int16_t* ft_bias, uint32_t 
       std::nth_element(m, m + 31, m + kRows, std::greater<int32_t>());
       int64_t b = std::abs((int32_t)ft_bias[cols[i]] + (int32_t)blk[(size_t)krow * hd + cols[i]]);
       for (int k = 0; k < 31; ++k) b += m[k];
-      worst = std::max(worst, cols[i] < hd / 2 ? b : 2 * b);
+      // slice s: columns [32s, 32s + 32) of each half (ft_sliced.hip)
+      const bool first = cols[i] < hd / 2;
+      int64_t& w = worst[(first ? cols[i] : cols[i] - hd / 2) / 32];
+      w = std::max(w, first ? b : 2 * b);
     }
   }
-  return (int32_t)std::min<int64_t>(worst, INT32_MAX);
+  for (uint32_t s = 0; s < hd / 64; ++s) bounds[s] = (int32_t)std::min<int64_t>(worst[s], INT32_MAX);
+}
+
+int32_t accumulator_bound(const int16_t* ft_w, const int16_t* ft_bias, uint32_t hd, int variant) {
+  std::vector<int32_t> b(hd / 64);
+  slice_bounds(ft_w, ft_bias, hd, variant, b.data());
+  return *std::max_element(b.begin(), b.end());
 }
 
 }  // namespace fnnue

@@ -107,6 +107,11 @@ void pack_image(const Net& net, uint8_t* dst);  // dst has image_layout(hd).tota
 // rows / blocks: the feature set's rows per own-king block and block count
 // (chess: 704 x 32, own king row 640 + KingBuckets order; variants: rows x 64,
 // own king row 640 + oriented king square).
+// slice_bounds: that maximum per 64-column slice s of ft_slices (columns
+// [32s, 32s + 32) of each half; hd / 64 values written to bounds).  A SWAR
+// word holds two columns of one slice, so a slice below 2^15 may run SWAR
+// rows whatever the others do.  accumulator_bound: the largest slice bound.
+void slice_bounds(const int16_t* ft_w, const int16_t* ft_bias, uint32_t hd, int variant, int32_t* bounds);
 int32_t accumulator_bound(const int16_t* ft_w, const int16_t* ft_bias, uint32_t hd, int variant = kVariantChess);
 
 }  // namespace fnnue

@@ -86,6 +86,14 @@ class Net:
         N.check(N.lib.fnnue_net_accumulator_bound(self._h, C.byref(b)))
         return b.value
 
+    def slice_bounds(self) -> np.ndarray:
+        """The accumulator bound of every 64-column slice (int32, hd / 64 values; their
+        maximum is accumulator_bound()).  A slice below 2^15 runs SWAR rows."""
+        out = np.zeros(64, dtype=np.int32)
+        n = C.c_size_t()
+        N.check(N.lib.fnnue_net_slice_bounds(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
     def image(self) -> np.ndarray:
         size = C.c_size_t()
         N.check(N.lib.fnnue_net_image_size(self._h, C.byref(size)))
@@ -379,6 +387,16 @@ class Evaluator:
 
     def set_swar(self, enable: bool) -> None:
         N.check(N.lib.fnnue_ctx_set_swar(self._h, 1 if enable else 0))
+
+    def swar_slices(self) -> tuple[int, int, int]:
+        """(eligible, enabled, nslices): bit s of the masks is slice s (64 columns)."""
+        el, en, ns = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        N.check(N.lib.fnnue_ctx_swar_slices(self._h, C.byref(el), C.byref(en), C.byref(ns)))
+        return el.value, en.value, ns.value
+
+    def set_swar_slices(self, mask: int) -> None:
+        """Run SWAR rows in exactly the slices of `mask` (a subset of the eligible ones)."""
+        N.check(N.lib.fnnue_ctx_set_swar_slices(self._h, mask))
 
     def set_timing(self, enable, ft_only: bool = False) -> None:
         """Events around every phase (plan / FT kernel / stacks), or with ft_only

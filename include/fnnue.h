@@ -106,6 +106,8 @@ void fnnue_net_free(fnnue_net *net);
 #define FNNUE_SYNTH_LEB128 1u     /* write tensors COMPRESSED_LEB128                  */
 #define FNNUE_SYNTH_WRAP 2u       /* large FT weights: int16 accumulators wrap around */
 #define FNNUE_SYNTH_FC1_PAD 4u    /* non-zero fc_1 padding weights (inputs 30,31)      */
+#define FNNUE_SYNTH_HEAVY 8u      /* a heavy column in every third slice (s % 3 == 1):
+                                   * those slices fail the SWAR bound, the others pass */
 int fnnue_net_synthesize(uint64_t seed, uint32_t hd, uint32_t flags, void **buf, size_t *len);
 void fnnue_buffer_free(void *buf);
 
@@ -423,6 +425,22 @@ int fnnue_ctx_set_ft_impl(fnnue_ctx *ctx, int impl);
 int fnnue_net_accumulator_bound(const fnnue_net *net, int32_t *bound);
 int fnnue_ctx_swar(const fnnue_ctx *ctx, int *enabled, int32_t *bound);
 int fnnue_ctx_set_swar(fnnue_ctx *ctx, int enable);
+/* The decision is made per 64-column slice (ABI 3.3).  Slice s of a net of
+ * width hd covers columns [32s, 32s + 32) of each half; a SWAR word never
+ * spans two slices, so every slice whose own bound is below 32768 runs SWAR
+ * rows and the others run packed int16 rows, in one launch.
+ * fnnue_net_slice_bounds writes the hd / 64 slice bounds (cap >= hd / 64, else
+ * FNNUE_E_ARG; *nslices is set either way); their maximum is
+ * fnnue_net_accumulator_bound.  fnnue_ctx_swar_slices reports bit masks over
+ * the slices (at most 48): eligible (bound < 32768) and enabled.  A new
+ * context enables every eligible slice (none with FNNUE_SWAR=0).
+ * fnnue_ctx_set_swar_slices sets the enabled mask: FNNUE_E_ARG for a bit
+ * >= nslices, FNNUE_E_ARCH for an ineligible slice.  fnnue_ctx_swar reports
+ * enabled != 0 and the net bound; fnnue_ctx_set_swar(1) enables every eligible
+ * slice (FNNUE_E_ARCH when there is none), (0) clears the mask. */
+int fnnue_net_slice_bounds(const fnnue_net *net, int32_t *bounds, size_t cap, size_t *nslices);
+int fnnue_ctx_swar_slices(const fnnue_ctx *ctx, uint64_t *eligible, uint64_t *enabled, uint32_t *nslices);
+int fnnue_ctx_set_swar_slices(fnnue_ctx *ctx, uint64_t mask);
 
 /* Kernel timing with HIP events on the launch stream: when enabled, every
  * chunk launched by a *_device call records events around the feature-
