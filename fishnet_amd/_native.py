@@ -28,6 +28,8 @@ PLAYOUT_FINAL, PLAYOUT_PLIES, PLAYOUT_CHILDREN = 0, 1, 2
 VARIANT_CHESS, VARIANT_CRAZYHOUSE, VARIANT_ATOMIC = 0, 1, 2
 VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature set, their own rules
 POS_BYTES = 36
+BEST_BYTES = 24  # fnnue_best
+BEST_NONE, BEST_CP, BEST_MATE = 0, 1, 2
 VPOS_BYTES = 48
 
 
@@ -137,7 +139,17 @@ SIGNATURES = {
     "fnnue_eval_vpositions_device": ([_vp, _vp, _sz, _vp, _vp, _vp], _i32),
     "fnnue_eval_vgroups": ([_vp, _vp, _sz, _vp, _sz, _i32, _vp, _vp], _i32),
     "fnnue_eval_vgroups_device": ([_vp, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _vp], _i32),
+    "fnnue_move_uci": ([C.c_uint16, C.c_char_p], _i32),
+    "fnnue_build_children_device": ([_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _P(_sz), _P(_sz), _vp],
+                                    _i32),
+    "fnnue_build_children": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _P(_sz), _P(_sz)],
+                             _i32),
+    "fnnue_best_children_device": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp], _i32),
+    "fnnue_best_children": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp], _i32),
+    "fnnue_search1_device": ([_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_search1": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
     # include/fnnue_backend.h
+    "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_channel_nets": ([_vp, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_channel_netv": ([_P(_vp), _sz, _i32, _vp, _P(_vp)], _i32),

@@ -226,6 +226,11 @@ class GpuEvalStub:
             res.append(rows)
         return res
 
+    def set_analysis_depth(self, depth: int) -> None:
+        """fnnue_backend_set_analysis_depth: 0 = a static evaluation per ply (the
+        default), 1 = a one-ply search per chess analysis ply (best move, pv)."""
+        N.check(N.lib.fnnue_backend_set_analysis_depth(self._actor._h, int(depth)))
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -252,12 +257,14 @@ class _Nets(C.Structure):
 
 
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
-            atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
+            atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0,
+            analysis_depth: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` theirs
     (fnnue_backend_channel_netv): each batch is evaluated by its variant's net.
-    `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316)."""
+    `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316).
+    `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None:
@@ -271,7 +278,10 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
                      atomic._h if atomic is not None else None)
         N.check(N.lib.fnnue_backend_channel_nets(C.byref(nets), device, C.byref(init), C.byref(h)))
     actor = GpuEvalActor(h)
-    return GpuEvalStub(actor), actor
+    stub = GpuEvalStub(actor)
+    if analysis_depth:
+        stub.set_analysis_depth(analysis_depth)
+    return stub, actor
 
 
 def into_analysis(responses: Sequence[PositionResponse]) -> str:

@@ -24,6 +24,12 @@
 // (device and pinned host), so a steady stream of calls allocates nothing.  A
 // failed batch costs a second pass for its piece only.  Large calls spread the
 // host work (text staging, response fill) over a few threads.
+//
+// Analysis at depth 1 (fnnue_backend_set_analysis_depth; chess nets): a piece's
+// replay also keeps the plies' boards, and instead of the CHAIN evaluation the
+// stream runs the children expansion with moves and end flags, their STAR
+// evaluation and the per-group reduction (stage_search); the piece brings back
+// one fnnue_best per ply, from which fill() writes best move, score, depth 1.
 #include "../../include/fnnue_backend.h"
 
 #include <algorithm>
@@ -294,8 +300,15 @@ struct Piece {
   bool kids = false;          // the net's move-work children ride in this piece
   uint32_t ng = 0, n = 0;     // games, plies
   size_t nk = 0;              // children
-  size_t o_fen = 0, o_mv = 0, o_ply = 0, o_kids = 0, o_res = 0, o_fin = 0, o_ps = 0, o_po = 0, end = 0;
+  size_t o_fen = 0, o_mv = 0, o_ply = 0, o_kids = 0, o_res = 0, o_fin = 0, o_ps = 0, o_po = 0, o_best = 0, end = 0;
   size_t up0 = 0, down0 = 0, dev0 = 0, pos0 = 0;  // where the piece lives in the net's buffers
+  // Analysis at depth 1 (chess): the results image ends with one fnnue_best per
+  // ply (o_best; psqt / positional then hold each ply's own terms), the plies'
+  // boards sit at st0 of the net's board buffer, and `searched` counts the
+  // children the piece's search evaluated.
+  bool depth1 = false;
+  size_t st0 = 0;
+  size_t searched = 0;
   bool pending = false;                           // evaluation enqueued, results not yet read
 };
 
@@ -320,6 +333,12 @@ struct NetWork {
   std::vector<hipEvent_t> ev_done;  // per piece: results and error word on the host
   DevBuf dev, pos;
   PinnedBuf up, down, scratch;      // scratch: a failing piece's positions, read back by recover()
+  // Analysis at depth 1: every piece's boards, and one piece's children at a
+  // time (records, counts and offsets, moves, end flags, psqt, positional; the
+  // pieces follow one another on the stream), with the builder's scan scratch.
+  DevBuf states, kid_pos, kid_cnt, kid_off, kid_moves, kid_end, kid_ps, kid_po;
+  PinnedBuf sizing;                 // the builder's error word and a piece's record count, read back
+  BuilderScratch bscratch;
   void clear() {
     games.clear();
     roots.clear();
@@ -346,6 +365,9 @@ struct NetWork {
     up.release();
     down.release();
     scratch.release();
+    for (DevBuf* b : {&states, &kid_pos, &kid_cnt, &kid_off, &kid_moves, &kid_end, &kid_ps, &kid_po}) b->release();
+    sizing.release();
+    bscratch.release();
     for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
     ev_done.clear();
   }
@@ -384,6 +406,7 @@ struct fnnue_backend {
   fnnue_ctx* ctx[kKinds] = {};  // one evaluator per net, all on one device
   int device = 0;
   int32_t norm = kNormalizeToPawnSf151;
+  int analysis_depth = 0;        // fnnue_backend_set_analysis_depth: 1 = a one-ply search per chess analysis ply
   size_t piece_plies = 524288;  // FNNUE_BACKEND_PIECE_PLIES
   bool any_order = true;         // FNNUE_BACKEND_ANY_ORDER=0: wait for the nets' pieces in net order
   size_t tail_plies = 0;         // FNNUE_BACKEND_TAIL_PLIES: a net's last piece cut to about this many
@@ -450,6 +473,7 @@ struct fnnue_backend {
   int plan(Job& j, int k);
   int stage_up(Job& j, int k, size_t pi);
   int stage_eval(int k, size_t pi);
+  int stage_search(int k, size_t pi);
   int finish(Job& j, int k, bool wait, bool* ready);
   int recover(Job& j, int k, size_t pi);
   void fill(Job& j, int k, const Piece& P);
@@ -591,7 +615,9 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.o_fin = P.o_res + 16;
   P.o_ps = align16(P.o_fin + ng);
   P.o_po = P.o_ps + 4 * (n + nk);
-  P.end = P.o_po + 4 * (n + nk);
+  P.o_best = align16(P.o_po + 4 * (n + nk));
+  P.depth1 = analysis_depth == 1 && k == kVariantChess && ng;
+  P.end = P.depth1 ? P.o_best + n * sizeof(fnnue_best) : P.o_po + 4 * (n + nk);
 }
 
 // Cuts the net's games into pieces and places them in its (grow-only) buffers.
@@ -599,9 +625,13 @@ int fnnue_backend::plan(Job& j, int k) {
   NetWork& W = net[k];
   W.pieces.clear();
   size_t acc = 0, plies = 0, text = 0;
+  // At depth 1 a ply brings about 35 children (at most 218) into the net's
+  // grow-only children buffers and the evaluator's workspace: pieces of a 32nd
+  // of the plies keep a piece's records where a depth-0 piece's plies are.
+  const size_t cut_plies = analysis_depth == 1 && k == kVariantChess ? std::max<size_t>(1024, piece_plies / 32) : piece_plies;
   for (size_t i : W.games) {
     const size_t t = (size_t)flen[i] + 1 + mlen[i];
-    if (W.pieces.empty() || acc >= piece_plies || text + t > kMaxPieceText) {
+    if (W.pieces.empty() || acc >= cut_plies || text + t > kMaxPieceText) {
       W.pieces.emplace_back();
       acc = 0;
       text = 0;
@@ -631,7 +661,7 @@ int fnnue_backend::plan(Job& j, int k) {
     if (W.pieces.empty()) W.pieces.emplace_back();
     W.pieces.back().kids = true;
   }
-  size_t up = 0, down = 0, dev = 0, pos = 0;
+  size_t up = 0, down = 0, dev = 0, pos = 0, st = 0;
   for (Piece& P : W.pieces) {
     layout(j, k, P);
     if (P.o_fen >= (1ull << 31)) return fail(FNNUE_E_ARG, "batch text too large");
@@ -639,6 +669,8 @@ int fnnue_backend::plan(Job& j, int k) {
     P.down0 = down;
     P.dev0 = dev;
     P.pos0 = pos;
+    P.st0 = st;
+    if (P.depth1) st = align256(st + (size_t)P.n * sizeof(DBoard));
     up = align256(up + P.o_res + 16);
     down = align256(down + P.end - P.o_res);
     dev = align256(dev + P.end);
@@ -649,6 +681,8 @@ int fnnue_backend::plan(Job& j, int k) {
   if (int rc = W.down.reserve(down)) return rc;
   if (pos)
     if (int rc = W.pos.reserve(pos)) return rc;
+  if (st)
+    if (int rc = W.states.reserve(st)) return rc;
   return W.events(W.pieces.size());
 }
 
@@ -688,7 +722,14 @@ int fnnue_backend::stage_up(Job& j, int k, size_t pi) {
   char* dimg = W.dev.at<char>(P.dev0);
   hipStream_t us = ctx[k]->stream;
   HIP_TRY(hipMemcpyAsync(dimg, img, P.o_res + 16, hipMemcpyHostToDevice, us), "H2D(batch image)");
-  if (P.ng)
+  if (P.depth1)
+    HIP_TRY(replay_chess_states_device(dimg, reinterpret_cast<uint32_t*>(dimg + P.o_fen),
+                                       reinterpret_cast<uint32_t*>(dimg + P.o_mv),
+                                       reinterpret_cast<uint32_t*>(dimg + P.o_ply), P.ng, W.pos.at<fnnue_pos>(P.pos0),
+                                       W.states.at<DBoard>(P.st0), reinterpret_cast<uint8_t*>(dimg + P.o_fin),
+                                       reinterpret_cast<uint32_t*>(dimg + P.o_res), us),
+            "batch replay launch");
+  else if (P.ng)
     HIP_TRY(replay_games_device(k, dimg, reinterpret_cast<uint32_t*>(dimg + P.o_fen),
                                 reinterpret_cast<uint32_t*>(dimg + P.o_mv), reinterpret_cast<uint32_t*>(dimg + P.o_ply),
                                 P.ng, W.pos.at<char>(P.pos0), reinterpret_cast<uint8_t*>(dimg + P.o_fin),
@@ -716,7 +757,10 @@ int fnnue_backend::stage_eval(int k, size_t pi) {
     ~ErrWord() { c->err = saved; }
   } ew{c, c->err};
   c->err = reinterpret_cast<uint32_t*>(dimg + P.o_res) + 3;
-  if (P.ng) {
+  P.searched = 0;
+  if (P.depth1) {
+    if (int rc = stage_search(k, pi)) return rc;
+  } else if (P.ng) {
     const uint32_t* d_off = reinterpret_cast<const uint32_t*>(dimg + P.o_ply);
     const void* d_pos = W.pos.at<char>(P.pos0);
     const int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(d_pos), d_off, P.ng, P.n,
@@ -738,6 +782,59 @@ int fnnue_backend::stage_eval(int k, size_t pi) {
   HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(results)");
   P.pending = true;
   mark("eval", k, (long)pi);
+  return FNNUE_OK;
+}
+
+// Analysis at depth 1, a chess piece: behind its replay the children of every
+// ply are counted and the count read back (the builder's sizing read-back,
+// with the replay's error word: a piece with a rejected game skips the search
+// and goes to recover() as it is); then the children with their moves and end
+// flags, their STAR evaluation, the reduction into the results image and each
+// ply's own terms (a ply without a legal move reports them, as at depth 0).
+// The wait is bounded by the call's deadline.
+int fnnue_backend::stage_search(int k, size_t pi) {
+  NetWork& W = net[k];
+  Piece& P = W.pieces[pi];
+  fnnue_ctx* c = ctx[k];
+  hipStream_t s = c->stream;
+  char* dimg = W.dev.at<char>(P.dev0);
+  const uint32_t n = P.n;
+  const DBoard* states = W.states.at<DBoard>(P.st0);
+  if (int rc = W.kid_cnt.reserve((size_t)(n + 1) * 4)) return rc;
+  if (int rc = W.kid_off.reserve((size_t)(n + 1) * 4)) return rc;
+  if (int rc = W.sizing.reserve(8)) return rc;
+  uint32_t* coff = W.kid_off.at<uint32_t>(0);
+  HIP_TRY(children_count_device(states, n, W.kid_cnt.at<uint32_t>(0), coff, s, W.bscratch), "children count launch");
+  uint32_t* hs = W.sizing.at<uint32_t>(0);
+  HIP_TRY(hipMemcpyAsync(hs, dimg + P.o_res, 4, hipMemcpyDeviceToHost, s), "D2H(builder error)");
+  HIP_TRY(hipMemcpyAsync(hs + 1, coff + n, 4, hipMemcpyDeviceToHost, s), "D2H(children count)");
+  HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(children count)");
+  const auto tw = Clock::now();
+  const int rcw = wait_event(W.ev_done[pi], "sizing a piece's children");
+  wait_ms += ms_since(tw);
+  ++syncs;
+  if (rcw) return rcw;
+  if (hs[0]) return FNNUE_OK;  // a rejected game: its boards are not those of a game
+  const size_t total = hs[1];
+  if (int rc = W.kid_pos.reserve(total * sizeof(fnnue_pos))) return rc;
+  if (int rc = W.kid_moves.reserve(total * 2)) return rc;
+  if (int rc = W.kid_end.reserve(total)) return rc;
+  if (int rc = W.kid_ps.reserve(total * 4)) return rc;
+  if (int rc = W.kid_po.reserve(total * 4)) return rc;
+  fnnue_pos* kp = W.kid_pos.at<fnnue_pos>(0);
+  uint16_t* km = W.kid_moves.at<uint16_t>(0);
+  uint8_t* ke = W.kid_end.at<uint8_t>(0);
+  int32_t* kps = W.kid_ps.at<int32_t>(0);
+  int32_t* kpo = W.kid_po.at<int32_t>(0);
+  HIP_TRY(children_write_device(states, n, coff, (uint32_t)total, kp, km, ke, s), "children launch");
+  if (int rc = fnnue_eval_groups_device(c, kp, coff, n, total, FNNUE_GROUP_STAR, kps, kpo, s)) return rc;
+  HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
+                               s),
+          "best_children launch");
+  HIP_TRY(launch_gather_parents(kps, kpo, coff, n, (uint32_t)total, reinterpret_cast<int32_t*>(dimg + P.o_ps),
+                                reinterpret_cast<int32_t*>(dimg + P.o_po), s),
+          "gather_parents launch");
+  P.searched = total - n;
   return FNNUE_OK;
 }
 
@@ -868,7 +965,8 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const int32_t* ps = reinterpret_cast<const int32_t*>(res + (P.o_ps - P.o_res));
   const int32_t* po = reinterpret_cast<const int32_t*>(res + (P.o_po - P.o_res));
   const uint32_t* ply = W.up.at<uint32_t>(P.up0 + P.o_ply);
-  filled += P.n + P.nk;
+  filled += P.n + P.nk + P.searched;
+  const fnnue_best* best = P.depth1 ? reinterpret_cast<const fnnue_best*>(res + (P.o_best - P.o_res)) : nullptr;
   const double el = ms_since(t0);
   const uint64_t ms = (uint64_t)el;
   const uint32_t nps = el > 0 ? (uint32_t)std::min(4.0e9, (double)filled / (el * 1e-3)) : 0;
@@ -886,6 +984,44 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
       // be played from it): mate 0 / cp 0 instead of an evaluation.
       const bool ends = fin[g] & kFinalNoMoves;
       const uint8_t end_kind = (fin[g] & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+      if (best) {
+        // Depth 1: every ply from its fnnue_best.  A ply without a child is the
+        // game's last one without a legal move, answered as at depth 0.
+        const fnnue_best* gb = best + ply[g];
+        const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
+        for (uint32_t q = 0; q < len; ++q) {
+          const fnnue_best& B = gb[q];
+          const bool skipped = sk && skip[b + q];
+          const bool none = B.kind == FNNUE_BEST_NONE;
+          const bool mate = B.kind == FNNUE_BEST_MATE;
+          const uint8_t kind = none ? end_kind : mate ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+          const int64_t score = none ? 0 : mate ? 1 : (int64_t)B.value * 100 / nrm;
+          const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
+          if (j.cout) {
+            if (skipped)
+              put_compact(j.cout + b + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
+            else
+              put_compact(j.cout + b + q, rps, rpo, (int32_t)score, kind, none ? 0 : 1,
+                          none ? fl | FNNUE_COMPACT_NO_MOVES : fl);
+            continue;
+          }
+          fnnue_position_response* r = j.out + b + q;
+          if (skipped) {
+            put_response(r, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
+            continue;
+          }
+          put_response(r, response_head(q, 0, kind, none ? 0 : 1, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
+          if (!none) (void)fnnue_move_uci(B.move, r->best_move);
+        }
+        if (j.cout) {
+          fnnue_batch_compact& B = j.bout[i];
+          B.time_ms = ms;
+          B.nps = nps;
+          B.nodes = 0;
+          std::memset(B.best_move, 0, sizeof(B.best_move));
+        }
+        continue;
+      }
       if (j.cout) {
         fnnue_position_compact* r = j.cout + b;
         const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
@@ -1449,6 +1585,14 @@ int fnnue_backend_go(fnnue_backend* b, const fnnue_acquired* batches, size_t nba
   return fnnue_backend_go_timeout(b, batches, nbatches, out, cap, off, batch_rc, 0);
 }
 
+int fnnue_backend_set_analysis_depth(fnnue_backend* b, int depth) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (depth != 0 && depth != 1) return fail(FNNUE_E_ARG, "analysis depth 0 or 1, not " + std::to_string(depth));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->analysis_depth = depth;
+  return FNNUE_OK;
+}
+
 int fnnue_backend_last_stats(fnnue_backend* b, fnnue_backend_stats* out) {
   if (!b || !out) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->stats_mu);
@@ -1470,14 +1614,30 @@ int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char
     // AnalysisPart::Matrix: pv / score matrices [multipv - 1][depth]; static
     // eval fills multipv 1 at depth 0 with an empty pv.
     const char* kind = r[i].score_kind == FNNUE_SCORE_MATE ? "mate" : "cp";
-    if (r[i].matrix)
-      std::snprintf(tmp, sizeof(tmp), "{\"pv\":[[[]]],\"score\":[[{\"%s\":%lld}]],\"depth\":%u,\"nodes\":%llu,"
-                    "\"time\":%llu", kind, (long long)r[i].score, (unsigned)r[i].depth, (unsigned long long)r[i].nodes,
-                    (unsigned long long)r[i].time_ms);
-    else
-      std::snprintf(tmp, sizeof(tmp), "{\"score\":{\"%s\":%lld},\"depth\":%u,\"nodes\":%llu,\"time\":%llu", kind,
+    // The pv is the best move (a one-ply search has no second one): Best omits
+    // an empty pv; Matrix::set puts its line at column `depth`, the columns
+    // before it null ([ref] src/ipc.rs:77-86).
+    char pv[8];
+    std::memcpy(pv, r[i].best_move, 8);
+    pv[7] = 0;
+    for (char* c = pv; *c; ++c)
+      if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';  // never from this library
+    if (r[i].matrix) {
+      s += "{\"pv\":[[";
+      for (unsigned d = 0; d < r[i].depth; ++d) s += "null,";
+      s += pv[0] ? std::string("[\"") + pv + "\"]" : std::string("[]");
+      s += "]],\"score\":[[";
+      for (unsigned d = 0; d < r[i].depth; ++d) s += "null,";
+      std::snprintf(tmp, sizeof(tmp), "{\"%s\":%lld}]],\"depth\":%u,\"nodes\":%llu,\"time\":%llu", kind,
                     (long long)r[i].score, (unsigned)r[i].depth, (unsigned long long)r[i].nodes,
                     (unsigned long long)r[i].time_ms);
+    } else {
+      if (pv[0]) s += std::string("{\"pv\":\"") + pv + "\",";
+      else s += '{';
+      std::snprintf(tmp, sizeof(tmp), "\"score\":{\"%s\":%lld},\"depth\":%u,\"nodes\":%llu,\"time\":%llu", kind,
+                    (long long)r[i].score, (unsigned)r[i].depth, (unsigned long long)r[i].nodes,
+                    (unsigned long long)r[i].time_ms);
+    }
     s += tmp;
     if (r[i].nps) {
       std::snprintf(tmp, sizeof(tmp), ",\"nps\":%u", r[i].nps);

@@ -63,7 +63,11 @@ struct BuildResult {
 // temporary storage, per-ply boards and children counts.  A steady stream of
 // batches allocates nothing; buffers are freed by release() only.
 struct BuilderScratch {
-  enum { kPlies, kPlyOff, kErr, kScan, kStates, kCnt, kCoff, kSlots };
+  enum {
+    kPlies, kPlyOff, kErr, kScan, kStates, kCnt, kCoff,
+    kKids, kKidMoves, kKidEnd, kKidPsqt, kKidPositional,  // the one-ply search's children and their evaluation
+    kSlots
+  };
   void* p[kSlots] = {};
   size_t bytes[kSlots] = {};
   // p[slot] with at least `want` bytes (grows by a quarter beyond the request)
@@ -77,9 +81,52 @@ struct BuilderScratch {
 // followed by its legal children (Board::legal_moves order).  d_final
 // (optional, ngames bytes): kFinal* flags of each game's last position.
 // Sizes the outputs on the device and reads the sizes back: synchronises `s`.
+//
+// The one-ply search's form of the children expansion: with d_moves / d_end
+// (both, children only; cap entries each) every record also gets the move that
+// leads to it (fnnue_move; 0 for a ply's own record) and its own kFinalNoMoves /
+// kFinalCheck flags.  With `own` the outputs live in the scratch instead (d_out,
+// d_group_off, d_moves, d_end ignored; no capacity but own->max_groups plies,
+// checked before any ply is expanded) and `own` says where.
+struct ChildrenBufs {
+  size_t max_groups = 0;            // in: plies the caller has room for
+  fnnue_pos* pos = nullptr;         // out: records, group offsets (plies + 1), moves, end flags
+  const uint32_t* off = nullptr;
+  uint16_t* moves = nullptr;
+  uint8_t* end = nullptr;
+  const uint32_t* ply_off = nullptr;  // out: each game's first ply (ngames + 1)
+};
 BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                uint32_t ngames, bool children, fnnue_pos* d_out, size_t cap, uint32_t* d_group_off,
-                               size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final = nullptr);
+                               size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final = nullptr,
+                               uint16_t* d_moves = nullptr, uint8_t* d_end = nullptr, ChildrenBufs* own = nullptr);
+
+// The two halves of the children expansion over boards already replayed (the
+// backend's pieces): sizes (cnt and off: n + 1 words each; off[n] = records),
+// then the records with their moves and end flags.  Stream-ordered, no sync.
+hipError_t children_count_device(const DBoard* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off, hipStream_t s,
+                                 BuilderScratch& ws);
+hipError_t children_write_device(const DBoard* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                 fnnue_pos* d_out, uint16_t* d_moves, uint8_t* d_end, hipStream_t s);
+// Two forms of children_write_device, same output: one thread per record, each
+// regenerating its ply's moves up to its own (1, the default: as fast as the
+// other on 400k plies and three times faster on the backend's pieces), or one
+// thread per ply (0).  FNNUE_CHILDREN_IMPL=ply|record in the environment picks
+// one (measurements: DESIGN.md §4.14).
+int children_impl();
+
+// The chess replay with both outputs: the packed plies and their boards.
+hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+                                      const uint32_t* d_ply_off, uint32_t ngames, fnnue_pos* d_out, DBoard* d_states,
+                                      uint8_t* d_final, uint32_t* d_err, hipStream_t s);
+
+// search1.hip: the STAR-group reduction (fnnue_best_children_device) and the
+// gather of each group's first record's terms (the backend's terminal plies).
+hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
+                                const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
+                                fnnue_best* d_out, hipStream_t s);
+hipError_t launch_gather_parents(const int32_t* d_psqt, const int32_t* d_positional, const uint32_t* d_off,
+                                 uint32_t ngroups, uint32_t npos, int32_t* d_ps_out, int32_t* d_po_out, hipStream_t s);
 
 // Exclusive scan of cnt[0..n) into off[0..n], off[n] = total (hipcub, temporary
 // storage from ws); stream-ordered, no host sync.

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -67,6 +68,85 @@ __global__ void write_children_kernel(const DBoard* __restrict__ states, uint32_
     out[o++] = pack(c);
     return true;
   });
+}
+
+// ---- the one-ply search's children: records, moves, end flags ----
+
+// fnnue_move of m on b: Board::uci(m, b.chess960) as a code (a castling move's
+// destination is the king's unless the game needs Chess960 notation).
+__device__ __forceinline__ uint16_t move_code(const DBoard& b, const DMove& m) {
+  int to = m.to;
+  if (m.castle && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
+  return (uint16_t)((uint32_t)m.from | (uint32_t)to << 6 | (uint32_t)m.promo << 12);
+}
+
+// kFinalNoMoves / kFinalCheck of b: a second ply of move generation that
+// stops at the first legal move.
+__device__ __forceinline__ uint8_t end_of(const DBoard& b) {
+  bool any = false;
+  const DBoard c = b;  // a copy for the generator's reference (ChessRules::any_legal_from)
+  for_each_legal(c, [&](const DMove&) -> bool {
+    any = true;
+    return false;
+  });
+  return ChessRules::end_flags(b, any);
+}
+
+// One thread per ply: write_children_kernel plus each record's move and flags.
+__global__ __launch_bounds__(64) void write_children_ply_kernel(const DBoard* __restrict__ states, uint32_t n,
+                                          const uint32_t* __restrict__ off, fnnue_pos* __restrict__ out,
+                                          uint16_t* __restrict__ moves, uint8_t* __restrict__ end) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DBoard b = states[i];
+  const uint32_t o0 = off[i];
+  uint32_t o = o0;
+  out[o] = pack(b);
+  moves[o] = 0;
+  ++o;
+  for_each_legal(b, [&](const DMove& m) -> bool {
+    DBoard c = b;
+    do_move(c, m);
+    out[o] = pack(c);
+    moves[o] = move_code(b, m);
+    end[o] = end_of(c);
+    ++o;
+    return true;
+  });
+  end[o0] = ChessRules::end_flags(b, o > o0 + 1);
+}
+
+// One thread per record: record r belongs to the ply i with off[i] <= r <
+// off[i + 1]; r - off[i] = 0 is the ply itself, j > 0 its j-th legal move,
+// found by generating the ply's moves up to it.
+__global__ __launch_bounds__(64) void write_children_record_kernel(const DBoard* __restrict__ states, uint32_t n,
+                                             const uint32_t* __restrict__ off, uint32_t total,
+                                             fnnue_pos* __restrict__ out, uint16_t* __restrict__ moves,
+                                             uint8_t* __restrict__ end) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  uint32_t lo = 0, hi = n;  // off[lo] <= r < off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t o0 = off[lo], j = r - o0;
+  const DBoard b = states[lo];
+  DBoard c = b;
+  uint16_t mv = 0;
+  if (j) {
+    uint32_t k = 0;
+    for_each_legal(b, [&](const DMove& m) -> bool {
+      if (++k < j) return true;
+      do_move(c, m);
+      mv = move_code(b, m);
+      return false;
+    });
+  }
+  out[r] = pack(c);
+  moves[r] = mv;
+  end[r] = j ? end_of(c) : ChessRules::end_flags(b, off[lo + 1] - o0 > 1);
 }
 
 template <int D>
@@ -164,9 +244,47 @@ hipError_t replay_games_device(int variant, const char* d_text, const uint32_t* 
                              d_final, d_err, s);
 }
 
+hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+                                      const uint32_t* d_ply_off, uint32_t ngames, fnnue_pos* d_out, DBoard* d_states,
+                                      uint8_t* d_final, uint32_t* d_err, hipStream_t s) {
+  return launch_chess_replay(d_text, d_fen_off, d_mv_off, d_ply_off, ngames, d_out, d_states, d_final, d_err, s);
+}
+
+hipError_t children_count_device(const DBoard* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off, hipStream_t s,
+                                 BuilderScratch& ws) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(d_cnt + n, 0, 4, s)) != hipSuccess) return e;
+  const uint32_t bs = 64;
+  hipLaunchKernelGGL(count_children_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, d_states, n, d_cnt);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return builder_exclusive_scan(d_cnt, d_off, n, s, ws);
+}
+
+int children_impl() {
+  static const int impl = [] {
+    const char* e = std::getenv("FNNUE_CHILDREN_IMPL");
+    return e && std::strcmp(e, "ply") == 0 ? 0 : 1;
+  }();
+  return impl;
+}
+
+hipError_t children_write_device(const DBoard* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                 fnnue_pos* d_out, uint16_t* d_moves, uint8_t* d_end, hipStream_t s) {
+  if (n == 0 || total == 0) return hipSuccess;
+  const uint32_t bs = 64;
+  if (children_impl() == 1)
+    hipLaunchKernelGGL(write_children_record_kernel, dim3((total + bs - 1) / bs), dim3(bs), 0, s, d_states, n, d_off,
+                       total, d_out, d_moves, d_end);
+  else
+    hipLaunchKernelGGL(write_children_ply_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, d_states, n, d_off, d_out,
+                       d_moves, d_end);
+  return hipGetLastError();
+}
+
 BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                uint32_t ngames, bool children, fnnue_pos* d_out, size_t cap, uint32_t* d_group_off,
-                               size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final) {
+                               size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final, uint16_t* d_moves,
+                               uint8_t* d_end, ChildrenBufs* own) {
   BuildResult R;
   auto fail = [&](hipError_t e) {
     R.hip = e;
@@ -203,6 +321,11 @@ BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, co
         hipSuccess)
       return fail(e);
   } else {
+    if (own && total_plies > own->max_groups) {  // the search's capacity: one record per ply
+      R.n_groups = total_plies;
+      R.capacity = true;
+      return R;
+    }
     if ((e = ws.get(W::kStates, (size_t)total_plies * sizeof(DBoard), (void**)&states)) != hipSuccess) return fail(e);
     if ((e = ws.get(W::kCnt, (size_t)(total_plies + 1) * 4, (void**)&cnt)) != hipSuccess) return fail(e);
     if ((e = ws.get(W::kCoff, (size_t)(total_plies + 1) * 4, (void**)&coff)) != hipSuccess) return fail(e);
@@ -218,26 +341,38 @@ BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, co
       R.err_ply = herr[2];
       return R;
     }
-    if ((e = hipMemsetAsync(cnt + total_plies, 0, 4, s)) != hipSuccess) return fail(e);
-    hipLaunchKernelGGL(count_children_kernel, dim3((total_plies + bs - 1) / bs), dim3(bs), 0, s, states,
-                       total_plies, cnt);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    if ((e = builder_exclusive_scan(cnt, coff, total_plies, s, ws)) != hipSuccess) return fail(e);
+    if ((e = children_count_device(states, total_plies, cnt, coff, s, ws)) != hipSuccess) return fail(e);
     uint32_t total = 0;
     if ((e = hipMemcpyAsync(&total, coff + total_plies, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
     R.n_out = total;
     R.n_groups = total_plies;
-    if (cap < total || off_cap < (size_t)total_plies + 1 || !d_out || !d_group_off) {
-      R.capacity = true;
-      return R;
+    if (own) {
+      if ((e = ws.get(W::kKids, (size_t)total * sizeof(fnnue_pos), (void**)&own->pos)) != hipSuccess) return fail(e);
+      if ((e = ws.get(W::kKidMoves, (size_t)total * 2, (void**)&own->moves)) != hipSuccess) return fail(e);
+      if ((e = ws.get(W::kKidEnd, (size_t)total, (void**)&own->end)) != hipSuccess) return fail(e);
+      own->off = coff;
+      own->ply_off = ply_off;
+      if ((e = children_write_device(states, total_plies, coff, total, own->pos, own->moves, own->end, s)) !=
+          hipSuccess)
+        return fail(e);
+    } else {
+      if (cap < total || off_cap < (size_t)total_plies + 1 || !d_out || !d_group_off) {
+        R.capacity = true;
+        return R;
+      }
+      if (d_moves && d_end) {
+        if ((e = children_write_device(states, total_plies, coff, total, d_out, d_moves, d_end, s)) != hipSuccess)
+          return fail(e);
+      } else {
+        hipLaunchKernelGGL(write_children_kernel, dim3((total_plies + bs - 1) / bs), dim3(bs), 0, s, states,
+                           total_plies, coff, d_out);
+        if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+      }
+      if ((e = hipMemcpyAsync(d_group_off, coff, (size_t)(total_plies + 1) * 4, hipMemcpyDeviceToDevice, s)) !=
+          hipSuccess)
+        return fail(e);
     }
-    hipLaunchKernelGGL(write_children_kernel, dim3((total_plies + bs - 1) / bs), dim3(bs), 0, s, states,
-                       total_plies, coff, d_out);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_group_off, coff, (size_t)(total_plies + 1) * 4, hipMemcpyDeviceToDevice, s)) !=
-        hipSuccess)
-      return fail(e);
   }
   uint32_t herr[4];
   if ((e = hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);

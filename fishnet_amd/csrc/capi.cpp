@@ -391,7 +391,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      FNNUE_END_VARIANT, fnnue_backend_channel_netv
 // 3.3: SWAR decided per slice: fnnue_net_slice_bounds, fnnue_ctx_swar_slices, fnnue_ctx_set_swar_slices,
 //      FNNUE_SYNTH_HEAVY
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 3u; }
+// 3.4: the one-ply search: fnnue_move / fnnue_move_uci, fnnue_build_children[_device],
+//      fnnue_best / fnnue_best_children[_device], fnnue_search1[_device], fnnue_backend_set_analysis_depth
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 4u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1285,9 +1287,15 @@ int fnnue_selftest_mfma(int device) {
 }
 
 
-int fnnue_build_batch_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                             const uint32_t* d_moves_off, size_t ngames, int mode, fnnue_pos* d_out, size_t cap,
-                             uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// fnnue_build_batch_device, and with moves / end fnnue_build_children_device.
+int build_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                 size_t ngames, int mode, fnnue_pos* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
+                 uint16_t* d_moves, uint8_t* d_end, size_t* n_out, size_t* n_groups, void* stream,
+                 ChildrenBufs* own = nullptr) {
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   if (mode != FNNUE_PLAYOUT_PLIES && mode != FNNUE_PLAYOUT_CHILDREN) return fail(FNNUE_E_ARG, "bad build mode");
   *n_out = *n_groups = 0;
@@ -1298,7 +1306,7 @@ int fnnue_build_batch_device(fnnue_ctx* ctx, const char* d_text, const uint32_t*
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   const BuildResult R = build_batch_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames,
                                            mode == FNNUE_PLAYOUT_CHILDREN, d_out, cap, d_off, off_cap, s,
-                                           ctx->bscratch);
+                                           ctx->bscratch, nullptr, d_moves, d_end, own);
   if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
   *n_out = R.n_out;
   *n_groups = R.n_groups;
@@ -1309,6 +1317,212 @@ int fnnue_build_batch_device(fnnue_ctx* ctx, const char* d_text, const uint32_t*
                                   std::to_string(R.err_game));
   if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
   return FNNUE_OK;
+}
+
+// Stages a host game text (and its offsets) in the context's builder input.
+int stage_games(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
+                size_t ngames, char** d_text, uint32_t** d_fo, uint32_t** d_mo) {
+  if (fen_off[ngames] > text_len) return fail(FNNUE_E_ARG, "offsets exceed the text");
+  for (size_t i = 0; i < ngames; ++i)
+    if (fen_off[i] > moves_off[i] || moves_off[i] > fen_off[i + 1]) return fail(FNNUE_E_ARG, "offsets out of order");
+  const size_t text_bytes = (text_len + 255) / 256 * 256;
+  const size_t fo_bytes = (ngames + 1) * 4, mo_bytes = ngames * 4;
+  if (int rc = ensure_builder_input(ctx, text_bytes + fo_bytes + mo_bytes)) return rc;
+  *d_text = ctx->d_btext;
+  *d_fo = reinterpret_cast<uint32_t*>(ctx->d_btext + text_bytes);
+  *d_mo = *d_fo + (ngames + 1);
+  hipStream_t s = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(*d_text, text, text_len, hipMemcpyHostToDevice, s), "H2D");
+  HIP_TRY(hipMemcpyAsync(*d_fo, fen_off, fo_bytes, hipMemcpyHostToDevice, s), "H2D");
+  HIP_TRY(hipMemcpyAsync(*d_mo, moves_off, mo_bytes, hipMemcpyHostToDevice, s), "H2D");
+  return FNNUE_OK;
+}
+
+// A device buffer for the length of one host-buffer call.
+struct TempDev {
+  void* p = nullptr;
+  ~TempDev() {
+    if (p) (void)hipFree(p);
+  }
+  int get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? FNNUE_OK : fail(FNNUE_E_OOM, "device allocation"); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int fnnue_build_batch_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                             const uint32_t* d_moves_off, size_t ngames, int mode, fnnue_pos* d_out, size_t cap,
+                             uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  return build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, mode, d_out, cap, d_off, off_cap, nullptr, nullptr,
+                      n_out, n_groups, stream);
+}
+
+int fnnue_move_uci(fnnue_move m, char out[8]) {
+  if (!out) return fail(FNNUE_E_ARG, "null argument");
+  out[0] = 0;
+  const int from = m & 63, to = (m >> 6) & 63, promo = (m >> 12) & 7;
+  if ((m >> 15) || promo == 1 || promo > 5) return fail(FNNUE_E_ARG, "not a move code: " + std::to_string(m));
+  if (m == 0) return FNNUE_OK;
+  out[0] = (char)('a' + (from & 7));
+  out[1] = (char)('1' + (from >> 3));
+  out[2] = (char)('a' + (to & 7));
+  out[3] = (char)('1' + (to >> 3));
+  out[4] = promo ? " pnbrq"[promo] : 0;
+  out[5] = 0;
+  return FNNUE_OK;
+}
+
+int fnnue_build_children_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                                const uint32_t* d_moves_off, size_t ngames, fnnue_pos* d_out, size_t cap,
+                                uint32_t* d_off, size_t off_cap, fnnue_move* d_moves, uint8_t* d_end, size_t* n_out,
+                                size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  if (d_out && (!d_moves || !d_end)) return fail(FNNUE_E_ARG, "null moves / end buffer");
+  return build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, d_out, cap, d_off, off_cap,
+                      d_moves, d_end, n_out, n_groups, stream);
+}
+
+int fnnue_build_children(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                         const uint32_t* moves_off, size_t ngames, fnnue_pos* out, size_t cap, uint32_t* off,
+                         size_t off_cap, fnnue_move* moves, uint8_t* end, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  rc = fnnue_build_children_device(ctx, d_text, d_fo, d_mo, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr, n_out,
+                                   n_groups, s);
+  if (rc != FNNUE_E_CAPACITY) return rc;  // sizing pass: always "too small" with no outputs
+  if (!out || !off || !moves || !end || cap < *n_out || off_cap < *n_groups + 1)
+    return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  if ((rc = ensure_stage(ctx, *n_out, *n_groups + 1))) return rc;
+  TempDev extra;  // moves (2 B) then end (1 B) per record
+  const size_t nrec = *n_out;
+  if ((rc = extra.get(nrec * 3))) return rc;
+  fnnue_move* d_moves = static_cast<fnnue_move*>(extra.p);
+  uint8_t* d_end = static_cast<uint8_t*>(extra.p) + nrec * 2;
+  rc = fnnue_build_children_device(ctx, d_text, d_fo, d_mo, ngames, ctx->d_pos, nrec, ctx->d_off, *n_groups + 1,
+                                   d_moves, d_end, n_out, n_groups, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, ctx->d_pos, *n_out * sizeof(fnnue_pos), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(off, ctx->d_off, (*n_groups + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(moves, d_moves, *n_out * 2, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(end, d_end, *n_out, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
+int fnnue_best_children_device(fnnue_ctx* ctx, const int32_t* d_psqt, const int32_t* d_positional,
+                               const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off, size_t ngroups,
+                               size_t npos, fnnue_best* d_out, void* stream) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!d_psqt || !d_positional || !d_end || !d_off || !d_out) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  HIP_TRY(launch_best_children(d_psqt, d_positional, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_out,
+                               s),
+          "best_children launch");
+  return FNNUE_OK;
+}
+
+int fnnue_best_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* positional, const uint8_t* end,
+                        const fnnue_move* moves, const uint32_t* off, size_t ngroups, size_t npos, fnnue_best* out) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!off || !out || (npos && (!psqt || !positional || !end))) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  DeviceGuard g(ctx->device);
+  // [psqt | positional | off | out | moves | end]: 4-byte parts first
+  const size_t n4 = npos * 4, o_off = 2 * n4, o_out = o_off + (ngroups + 1) * 4;
+  const size_t o_mv = o_out + ngroups * sizeof(fnnue_best), o_end = o_mv + npos * 2;
+  TempDev buf;
+  if (int rc = buf.get(o_end + npos)) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  if (npos) {
+    HIP_TRY(hipMemcpyAsync(d, psqt, n4, hipMemcpyHostToDevice, s), "H2D");
+    HIP_TRY(hipMemcpyAsync(d + n4, positional, n4, hipMemcpyHostToDevice, s), "H2D");
+    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
+    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  const int rc = fnnue_best_children_device(
+      ctx, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + n4), reinterpret_cast<uint8_t*>(d + o_end),
+      moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr, reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
+      reinterpret_cast<fnnue_best*>(d + o_out), s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d + o_out, ngroups * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
+int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                         size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
+                         size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // the children and their terms live in the context's scratch: ordered like its workspace
+  int rc = order_workspace(ctx, s);
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  ChildrenBufs kids;
+  kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  size_t nrec = 0, nply = 0;
+  rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
+                    nullptr, nullptr, &nrec, &nply, s, &kids);
+  *n_out = nply;
+  *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
+  if (rc) return rc;
+  int32_t *ps = nullptr, *po = nullptr;
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPsqt, nrec * 4, (void**)&ps), "device allocation (search scratch)");
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPositional, nrec * 4, (void**)&po),
+          "device allocation (search scratch)");
+  if ((rc = fnnue_eval_groups_device(ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s))) return rc;
+  HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
+          "best_children launch");
+  HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
+  return FNNUE_OK;
+}
+
+int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                  const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
+                  size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  const bool room = out && off && off_cap >= ngames + 1;
+  TempDev buf;
+  const size_t o_off = cap * sizeof(fnnue_best);
+  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  rc = fnnue_search1_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
+                            room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
+                            room ? off_cap : 0, n_out, n_groups, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return latched(ctx);
 }
 
 int fnnue_build_batch(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,

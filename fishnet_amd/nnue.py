@@ -216,6 +216,24 @@ def random_vgames(seed: int, variant: int, count: int, max_plies: int = 160, thr
     return out[: n.value], off[: g.value + 1]
 
 
+class Best(C.Structure):
+    """fnnue_best: the result of a one-ply search over one position's children."""
+    _fields_ = [("psqt", C.c_int32), ("positional", C.c_int32), ("value", C.c_int32), ("nodes", C.c_uint32),
+                ("best", C.c_uint32), ("move", C.c_uint16), ("kind", C.c_uint8), ("end", C.c_uint8)]
+
+
+BEST_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("best", "<u4"),
+                       ("move", "<u2"), ("kind", "u1"), ("end", "u1")])
+BEST_NONE, BEST_CP, BEST_MATE = N.BEST_NONE, N.BEST_CP, N.BEST_MATE
+
+
+def move_uci(code: int) -> str:
+    """A fnnue_move code as UCI text ("" for 0); FnnueError FNNUE_E_ARG for a code that is no move."""
+    buf = C.create_string_buffer(8)
+    N.check(N.lib.fnnue_move_uci(int(code), buf))
+    return buf.value.decode()
+
+
 def device_count() -> int:
     n = C.c_int()
     N.check(N.lib.fnnue_device_count(C.byref(n)))
@@ -367,6 +385,76 @@ class Evaluator:
                                          len(games), mode, N.ptr(out), len(out), N.ptr(off), len(off), C.byref(n),
                                          C.byref(g)))
         return out[: n.value], off[: g.value + 1]
+
+    # The one-ply search (ABI 3.4): games = [(fen, "uci uci ..."), ...].
+    def build_children(self, games):
+        """fnnue_build_children: (records, STAR offsets, move codes, end flags) of every ply and its children."""
+        text, fen_off, mv_off = pack_games(games)
+        n, g = C.c_size_t(), C.c_size_t()
+        rc = N.lib.fnnue_build_children(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), None, 0,
+                                        None, 0, None, None, C.byref(n), C.byref(g))
+        if rc != -10:
+            N.check(rc)
+            return N.positions_array(0), np.zeros(1, dtype=np.uint32), np.zeros(0, np.uint16), np.zeros(0, np.uint8)
+        out = N.positions_array(n.value)
+        off = np.zeros(g.value + 1, dtype=np.uint32)
+        moves = np.zeros(n.value, dtype=np.uint16)
+        end = np.zeros(n.value, dtype=np.uint8)
+        N.check(N.lib.fnnue_build_children(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                           N.ptr(out), len(out), N.ptr(off), len(off), N.ptr(moves), N.ptr(end),
+                                           C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1], moves[: n.value], end[: n.value]
+
+    def build_children_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int, cap: int,
+                              d_off: int, off_cap: int, d_moves: int, d_end: int, stream: int | None):
+        """fnnue_build_children_device -> (rc, records, groups); rc is FNNUE_E_CAPACITY (-10) on a sizing call."""
+        n, g = C.c_size_t(), C.c_size_t()
+        rc = N.lib.fnnue_build_children_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                               C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap,
+                                               C.c_void_p(d_off), off_cap, C.c_void_p(d_moves), C.c_void_p(d_end),
+                                               C.byref(n), C.byref(g), C.c_void_p(stream))
+        if rc != -10:
+            N.check(rc)
+        return rc, n.value, g.value
+
+    def best_children(self, psqt, positional, end, moves, off) -> np.ndarray:
+        """fnnue_best_children: one BEST_DTYPE record per STAR group (moves may be None)."""
+        psqt = np.ascontiguousarray(psqt, dtype=np.int32)
+        positional = np.ascontiguousarray(positional, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        if moves is not None:
+            moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        out = np.zeros(len(off) - 1, dtype=BEST_DTYPE)
+        N.check(N.lib.fnnue_best_children(self._h, N.ptr(psqt), N.ptr(positional), N.ptr(end), N.ptr(moves),
+                                          N.ptr(off), len(off) - 1, len(psqt), N.ptr(out)))
+        return out
+
+    def best_children_device(self, d_psqt: int, d_positional: int, d_end: int, d_moves: int | None, d_off: int,
+                             ngroups: int, npos: int, d_out: int, stream: int | None):
+        N.check(N.lib.fnnue_best_children_device(self._h, C.c_void_p(d_psqt), C.c_void_p(d_positional),
+                                                 C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off), ngroups,
+                                                 npos, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def search1(self, games) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_search1: a one-ply search per ply -> (BEST_DTYPE records, CHAIN offsets per game)."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search1(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), N.ptr(out),
+                                    cap, N.ptr(off), len(off), C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1]
+
+    def search1_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int, cap: int,
+                       d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_search1_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search1_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
+                                           ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n),
+                                           C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
 
     def perft_device(self, fen: str, depth: int) -> int:
         nodes = C.c_uint64()

@@ -392,6 +392,77 @@ int fnnue_perft_device(fnnue_ctx *ctx, const char *fen, int depth, uint64_t *nod
  * needs it), NUL-terminated; *len = string length.  Test-input generator. */
 int fnnue_random_game(uint64_t seed, const char *fen, uint32_t plies, char *moves, size_t cap, size_t *len);
 
+/* ---- one-ply search on the device (ABI 3.4) ----
+ * What a search over a position's children needs beyond their records: the
+ * move that leads to each child and whether the child is checkmated or
+ * stalemated; then, per STAR group, the best child.  Chess nets only
+ * (standard, chess960, fromPosition): the Fairy-Stockfish variants keep their
+ * host-side one-ply search for move work, and the end-flag byte leaves bits
+ * FNNUE_END_EXTINCT / FNNUE_END_VARIANT (and 0x40, "won by the side to move")
+ * free for their rules.
+ *
+ * A move code: from | to << 6 | promo << 12 (squares A1 = 0 .. H8 = 63; promo 0
+ * or the piece type 2..5 = n b r q).  Castling carries the squares the game's
+ * notation spells: the king's destination, or the rook's square when the game
+ * needs Chess960 notation, so the code prints without its board.  0: no move. */
+typedef uint16_t fnnue_move;
+/* "e2e4", "e7e8q" (NUL-terminated, at most 6 bytes); the code 0 prints as "".
+ * FNNUE_E_ARG for promo 1, 6 or 7 or a set bit 15.  Host only. */
+int fnnue_move_uci(fnnue_move m, char out[8]);
+/* fnnue_build_batch[_device] in FNNUE_PLAYOUT_CHILDREN mode (records and
+ * offsets byte for byte, same capacity protocol, same errors) plus two arrays
+ * parallel to the records (cap entries each): moves[r] the move that leads to
+ * record r (0 for a ply's own record), end[r] the FNNUE_END_NO_MOVES /
+ * FNNUE_END_CHECK flags of record r itself, plies and children alike. */
+int fnnue_build_children_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off,
+                                const uint32_t *d_moves_off, size_t ngames, fnnue_pos *d_out, size_t cap,
+                                uint32_t *d_off, size_t off_cap, fnnue_move *d_moves, uint8_t *d_end, size_t *n_out,
+                                size_t *n_groups, void *stream);
+int fnnue_build_children(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                         const uint32_t *moves_off, size_t ngames, fnnue_pos *out, size_t cap, uint32_t *off,
+                         size_t off_cap, fnnue_move *moves, uint8_t *end, size_t *n_out, size_t *n_groups);
+/* The best child of a STAR group [off[g], off[g + 1]) (its first record is the
+ * parent), by the rule of the backend's move work: a child with NO_MOVES |
+ * CHECK is a mate in one and beats everything; a child with NO_MOVES alone is
+ * worth 0; any other child -(((int64)psqt + positional) / 16) (C truncation);
+ * the first maximum (the lowest index) wins.  An empty group gives an
+ * all-zero record. */
+#define FNNUE_BEST_NONE 0 /* no child: `end` says mate 0 (NO_MOVES | CHECK) or cp 0 */
+#define FNNUE_BEST_CP 1
+#define FNNUE_BEST_MATE 2 /* mate in 1 */
+typedef struct {
+  int32_t psqt, positional; /* of the best child, negated (as move work reports them); 0 when none */
+  int32_t value;            /* Stockfish internal units, side to move of the parent; 0 for mate / none */
+  uint32_t nodes;           /* children */
+  uint32_t best;            /* index of the best child within the group (1-based record index), 0 when none */
+  fnnue_move move;          /* 0 when none (or without a moves array) */
+  uint8_t kind;             /* FNNUE_BEST_* */
+  uint8_t end;              /* the parent's FNNUE_END_* flags */
+} fnnue_best;
+/* The reduction alone, one kernel on `stream` (no atomics, no host
+ * synchronisation): psqt / positional / end (and moves, which may be NULL)
+ * hold npos entries, off ngroups + 1 (offsets beyond npos are clamped), out
+ * ngroups records.  Any net. */
+int fnnue_best_children_device(fnnue_ctx *ctx, const int32_t *d_psqt, const int32_t *d_positional,
+                               const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                               size_t ngroups, size_t npos, fnnue_best *d_out, void *stream);
+int fnnue_best_children(fnnue_ctx *ctx, const int32_t *psqt, const int32_t *positional, const uint8_t *end,
+                        const fnnue_move *moves, const uint32_t *off, size_t ngroups, size_t npos, fnnue_best *out);
+/* Depth 1 for every ply of every game (text in the builder's layout): the
+ * children expansion, their STAR evaluation and the reduction, in the
+ * context's grow-only scratch.  out: one record per ply (cap records), off:
+ * CHAIN offsets per game (ngames + 1 entries); *n_out = plies, *n_groups =
+ * games, set also with FNNUE_E_CAPACITY (before any ply is expanded).  The
+ * builder's sizing read-backs synchronise `stream`; the evaluation and the
+ * reduction are enqueued behind them (fnnue_ctx_check reports a position the
+ * evaluator rejects).  A chess net's context; FNNUE_E_ARCH otherwise. */
+int fnnue_search1_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off, const uint32_t *d_moves_off,
+                         size_t ngames, fnnue_best *d_out, size_t cap, uint32_t *d_off, size_t off_cap,
+                         size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_search1(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                  const uint32_t *moves_off, size_t ngames, fnnue_best *out, size_t cap, uint32_t *off,
+                  size_t off_cap, size_t *n_out, size_t *n_groups);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

@@ -38,7 +38,9 @@
  *   cp = v * 100 / normalize_to_pawn         UCI::value's normalisation (upstream
  *                                             uci.cpp; 361 in SF 15.1 as recalled,
  *                                             a parameter because it is unpinned)
- * Analysis work: one response per ply, depth 0, nodes 1, no pv / best move.
+ * Analysis work: one response per ply, depth 0, nodes 1, no pv / best move
+ * (the default; fnnue_backend_set_analysis_depth(b, 1) answers chess batches
+ * with a one-ply search per ply instead, see there).
  * A position with no legal move (it can only be a game's last ply) is
  * answered as the engine answers it — `info depth 0 score mate 0` when the
  * side to move is checkmated (atomic: its king exploded), `score cp 0` when
@@ -104,7 +106,7 @@ typedef struct {
   uint64_t nodes;
   uint64_t time_ms;      /* wall time of the go() call until this position's piece was back on the host */
   uint32_t nps;          /* positions evaluated by then, per second */
-  char best_move[8];     /* UCI, NUL-terminated; "" for analysis */
+  char best_move[8];     /* UCI, NUL-terminated; "" for analysis at depth 0 */
 } fnnue_position_response;
 
 /* The nets of one backend, by the batches they evaluate.  Any may be NULL
@@ -134,6 +136,32 @@ int fnnue_backend_channel(const fnnue_net *net, int device, const fnnue_backend_
  * streams, its buffers are released later (by a later channel() or free()),
  * once the streams have drained. */
 void fnnue_backend_free(fnnue_backend *b);
+
+/* Analysis depth of the channel: 0 (the default: a static evaluation per ply)
+ * or 1; anything else is FNNUE_E_ARG.  A setter because the size of
+ * fnnue_backend_init is ABI.  Takes effect with the next go().
+ * At depth 1 every non-skipped ply of a chess analysis batch (standard,
+ * chess960, fromPosition) is answered by a one-ply search over its legal
+ * children on the device (fnnue_search1_device's three steps per piece: the
+ * children with their moves and end flags, their STAR evaluation, the
+ * reduction to a fnnue_best), by the rule of move work: an evaluated best child
+ * gives Score::Cp(value * 100 / normalize_to_pawn), a mating child
+ * Score::Mate(1); depth 1, nodes = the children, best_move = the pv's one move
+ * ([ref] AnalysisPart::Best::pv, src/api.rs:359-369), psqt / positional the best
+ * child's, negated.  A ply without a legal move is answered exactly as at
+ * depth 0 (mate 0 / cp 0, depth 0, nodes 0, no move); skipped ids stay
+ * skipped; move work is unchanged.  Variant batches (crazyhouse, atomic,
+ * kingOfTheHill, racingKings) are answered at depth 0 exactly as on a depth-0
+ * channel: their rules' end flags (FNNUE_END_EXTINCT, FNNUE_END_VARIANT) are
+ * not part of the device search yet.
+ * Pieces are cut at a 32nd of FNNUE_BACKEND_PIECE_PLIES, so that a piece's
+ * children (about 35 per ply) take the room a depth-0 piece's plies do; each
+ * piece reads its children count back once (a bounded wait inside the call's
+ * budget).  fnnue_backend_stats.positions counts plies plus children.
+ * fnnue_backend_go_compact on a depth-1 channel gives the depth-1 score and
+ * depth = 1 but no move and no node count: the 16-byte record has no room for
+ * them (nodes reads as 1, as at depth 0). */
+int fnnue_backend_set_analysis_depth(fnnue_backend *b, int depth);
 
 /* Number of responses batch `a` expands to (IncomingBatch::from_acquired):
  * analysis = moves + 1, move = 1.  Host only; FNNUE_E_ARG on a bad work type. */
@@ -231,7 +259,12 @@ int fnnue_backend_last_stats(fnnue_backend *b, fnnue_backend_stats *out);
  * serialisation, api.rs:355-388): {"skipped":true} or {"score":{"cp":..},
  * "depth":..,"nodes":..,"time":..,"nps":..} per position, or for a MultiPV
  * batch the matrix form {"pv":[[[]]],"score":[[{"cp":..}]],"depth":0,...}
- * (Matrix::set(multipv 1, depth 0): one row, one column), as JSON.  Writes
+ * (Matrix::set(multipv 1, depth 0): one row, one column), as JSON.  A
+ * response with a best move (analysis at depth 1) carries it as its pv:
+ * {"pv":"e2e4","score":{..},..} (AnalysisPart::Best: space-separated, omitted
+ * when empty), and the matrix form puts its one line at column `depth`
+ * (Matrix::set, [ref] src/ipc.rs:77-86): {"pv":[[null,["e2e4"]]],
+ * "score":[[null,{"cp":..}]],"depth":1,...}.  Writes
  * at most cap bytes including the NUL; *len = the full length (without NUL);
  * FNNUE_E_CAPACITY when it did not fit. */
 int fnnue_backend_analysis_json(const fnnue_position_response *r, size_t n, char *buf, size_t cap, size_t *len);

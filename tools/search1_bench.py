@@ -1,0 +1,223 @@
+"""Phase times of the one-ply search (fnnue_search1_device) on config 4's
+shape: N random games (L ~ U[0, 160] plies) with every legal child, HD 1024.
+GPU box only.  One JSON line per measurement.
+
+    python tools/search1_bench.py [--games 5000] [--hd 1024] [--runs 3] [--lib PATH] [--actor] [--base-only]
+
+The phases are timed with HIP events on the launch stream, after the workload
+ran untimed for 0.3 s:
+  children  fnnue_build_children_device (records + moves + end flags)
+  eval      fnnue_eval_groups_device(STAR)
+  reduce    fnnue_best_children_device
+  search1   fnnue_search1_device, the three in one call
+  build     fnnue_build_batch_device(CHILDREN): the expansion without moves / flags
+`--lib` loads another build of the library (the parent commit's, which has
+only `build` and `eval`): the tool binds the few symbols it needs itself, so
+the two builds can alternate on one box (`--base-only` runs just those two on
+either build: the same work per iteration, for comparing the evaluation
+phase).  FNNUE_CHILDREN_IMPL=ply|record in
+the environment picks the children kernel (A/B).  `--actor` adds the engine
+actor at depth 0 and 1 for 1, 64 and 1024 lichess-shaped batches.
+"""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+START = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
+HBM_READ_TBPS = 6.8  # whole 1 KiB rows stream at 6.7-6.9 TB/s
+vp, sz = C.c_void_p, C.c_size_t
+
+
+def bind(path):
+    import torch  # noqa: F401  (its HIP runtime first, as fishnet_amd._native does)
+    lib = C.CDLL(path)
+    P = C.POINTER
+    sig = {
+        "fnnue_last_error": ([], C.c_char_p),
+        "fnnue_net_synthesize": ([C.c_uint64, C.c_uint32, C.c_uint32, P(vp), P(sz)], C.c_int),
+        "fnnue_net_load_mem": ([vp, sz, P(vp)], C.c_int),
+        "fnnue_ctx_create": ([vp, C.c_int, P(vp)], C.c_int),
+        "fnnue_ctx_check": ([vp], C.c_int),
+        "fnnue_random_game": ([C.c_uint64, C.c_char_p, C.c_uint32, C.c_char_p, sz, P(sz)], C.c_int),
+        "fnnue_build_batch_device": ([vp, vp, vp, vp, sz, C.c_int, vp, sz, vp, sz, P(sz), P(sz), vp], C.c_int),
+        "fnnue_eval_groups_device": ([vp, vp, vp, sz, sz, C.c_int, vp, vp, vp], C.c_int),
+    }
+    new = {
+        "fnnue_build_children_device": ([vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp, P(sz), P(sz), vp], C.c_int),
+        "fnnue_best_children_device": ([vp, vp, vp, vp, vp, vp, sz, sz, vp, vp], C.c_int),
+        "fnnue_search1_device": ([vp, vp, vp, vp, sz, vp, sz, vp, sz, P(sz), P(sz), vp], C.c_int),
+    }
+    has_new = all(hasattr(lib, n) for n in new)
+    for name, (a, r) in {**sig, **(new if has_new else {})}.items():
+        f = getattr(lib, name)
+        f.argtypes, f.restype = a, r
+    return lib, has_new
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=5000)
+    ap.add_argument("--hd", type=int, default=1024)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=4)
+    ap.add_argument("--lib", default=os.path.join(ROOT, "fishnet_amd", "libfnnue.so"))
+    ap.add_argument("--label", default="")
+    ap.add_argument("--actor", action="store_true")
+    ap.add_argument("--base-only", action="store_true", help="only build + eval, whatever the library has")
+    a = ap.parse_args()
+    import torch
+    lib, has_new = bind(a.lib)
+    label = a.label or ("tree" if has_new else "parent")
+    impl = os.environ.get("FNNUE_CHILDREN_IMPL", "record")
+
+    def ok(rc, allow=()):
+        if rc and rc not in allow:
+            raise RuntimeError(f"rc {rc}: {(lib.fnnue_last_error() or b'').decode()}")
+        return rc
+
+    # the text: N games, L ~ U[0, 160] random legal plies each
+    rng = np.random.default_rng(a.seed)
+    buf, n = C.create_string_buffer(8 * 160 + 16), sz()
+    parts, fen_off, mv_off, at = [], [], [], 0
+    for i in range(a.games):
+        ok(lib.fnnue_random_game(a.seed * 1_000_003 + i, START.encode(), int(rng.integers(0, 161)), buf, len(buf),
+                                 C.byref(n)))
+        f, m = START.encode(), b" " + buf.value
+        fen_off.append(at)
+        mv_off.append(at + len(f))
+        parts += [f, m]
+        at += len(f) + len(m)
+    fen_off.append(at)
+    text = b"".join(parts)
+    dev = torch.device("cuda", 0)
+    d_text = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev)
+    d_fo = torch.tensor(fen_off, dtype=torch.int32, device=dev)
+    d_mo = torch.tensor(mv_off, dtype=torch.int32, device=dev)
+    T, FO, MO = vp(d_text.data_ptr()), vp(d_fo.data_ptr()), vp(d_mo.data_ptr())
+
+    nb, nl, net, ctx = vp(), sz(), vp(), vp()
+    ok(lib.fnnue_net_synthesize(1, a.hd, 0, C.byref(nb), C.byref(nl)))
+    ok(lib.fnnue_net_load_mem(nb, nl, C.byref(net)))
+    ok(lib.fnnue_ctx_create(net, 0, C.byref(ctx)))
+
+    stream = torch.cuda.Stream(dev)
+    S = vp(stream.cuda_stream)
+    nrec, ngrp = sz(), sz()
+    ok(lib.fnnue_build_batch_device(ctx, T, FO, MO, a.games, 2, None, 0, None, 0, C.byref(nrec), C.byref(ngrp), S),
+       allow=(-10,))
+    R, G = nrec.value, ngrp.value
+    d_pos = torch.empty((R, 36), dtype=torch.uint8, device=dev)
+    d_off = torch.empty(G + 1, dtype=torch.int32, device=dev)
+    d_mv = torch.empty(R, dtype=torch.int16, device=dev)
+    d_end = torch.empty(R, dtype=torch.uint8, device=dev)
+    d_ps = torch.empty(R, dtype=torch.int32, device=dev)
+    d_po = torch.empty(R, dtype=torch.int32, device=dev)
+    d_best = torch.zeros((G, 24), dtype=torch.uint8, device=dev)
+    d_best2 = torch.zeros((G, 24), dtype=torch.uint8, device=dev)
+    d_goff = torch.empty(a.games + 1, dtype=torch.int32, device=dev)
+    PO, OF, MV, EN = vp(d_pos.data_ptr()), vp(d_off.data_ptr()), vp(d_mv.data_ptr()), vp(d_end.data_ptr())
+    PS, PP = vp(d_ps.data_ptr()), vp(d_po.data_ptr())
+    torch.cuda.synchronize(dev)
+
+    def build():
+        ok(lib.fnnue_build_batch_device(ctx, T, FO, MO, a.games, 2, PO, R, OF, G + 1, C.byref(nrec), C.byref(ngrp), S))
+
+    def children():
+        ok(lib.fnnue_build_children_device(ctx, T, FO, MO, a.games, PO, R, OF, G + 1, MV, EN, C.byref(nrec),
+                                           C.byref(ngrp), S))
+
+    def evaluate():
+        ok(lib.fnnue_eval_groups_device(ctx, PO, OF, G, R, 1, PS, PP, S))
+
+    def reduce():
+        ok(lib.fnnue_best_children_device(ctx, PS, PP, EN, MV, OF, G, R, vp(d_best.data_ptr()), S))
+
+    def search1():
+        ok(lib.fnnue_search1_device(ctx, T, FO, MO, a.games, vp(d_best2.data_ptr()), G, vp(d_goff.data_ptr()),
+                                    a.games + 1, C.byref(nrec), C.byref(ngrp), S))
+
+    phases = [("build", build), ("eval", evaluate)]
+    if has_new and not a.base_only:
+        # eval right behind build, as on a parent build; children rewrites the same records
+        phases = [("build", build), ("eval", evaluate), ("children", children), ("reduce", reduce), ("search1", search1)]
+
+    def once(timed):
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)] if timed else None
+        with torch.cuda.stream(stream):
+            for k, (_, fn) in enumerate(phases):
+                if timed:
+                    evs[k].record(stream)
+                fn()
+            if timed:
+                evs[-1].record(stream)
+        stream.synchronize()
+        ok(lib.fnnue_ctx_check(ctx))
+        return [evs[k].elapsed_time(evs[k + 1]) for k in range(len(phases))] if timed else None
+
+    t0 = time.perf_counter()
+    once(False)
+    while time.perf_counter() - t0 < 0.3:
+        once(False)
+    runs = [once(True) for _ in range(a.runs)]
+    base = {"lib": label, "children_impl": impl if has_new else None, "games": a.games, "hd": a.hd, "plies": G,
+            "records": R}
+    for k, (name, _) in enumerate(phases):
+        ms = sorted(r[k] for r in runs)
+        line = dict(base, phase=name, ms=[round(x, 4) for x in ms], median_ms=round(ms[len(ms) // 2], 4),
+                    records_per_s=round(R / (ms[len(ms) // 2] * 1e-3)))
+        if name == "reduce":
+            lo, hi = (9 * R + 24 * G) / (HBM_READ_TBPS * 1e9), (11 * R + 24 * G) / (HBM_READ_TBPS * 1e9)
+            line["byte_floor_ms"] = [round(lo, 4), round(hi, 4)]
+            line["times_floor"] = round(ms[len(ms) // 2] / hi, 2)
+        print(json.dumps(line), flush=True)
+    if has_new and not a.base_only:
+        same = bool(torch.equal(d_best, d_best2))
+        digest = hashlib.sha256(d_best2.cpu().numpy().tobytes()).hexdigest()[:16]
+        print(json.dumps(dict(base, check="search1 == children + eval + reduce", ok=same, best_sha256=digest)),
+              flush=True)
+        if not same:
+            sys.exit(1)
+    if a.actor and has_new:
+        actor_lines(a)
+
+
+def actor_lines(a):
+    """The engine actor at depth 0 and 1 on the same lichess-shaped chess batches."""
+    sys.path.insert(0, ROOT)
+    import fishnet_amd as F
+    from fishnet_amd import backend as B
+    import bench
+    net = F.Net.from_bytes(F.synthesize_net(1, a.hd, 0))
+    for nb in (1, 64, 1024):
+        bodies = bench.lichess_batches(F, 11, nb, variants=0.0)
+        plies = sum(len(b.moves.split()) + 1 for b in bodies)
+        for depth in (0, 1):
+            stub, actor = B.channel(net, 0, analysis_depth=depth)
+            t0 = time.perf_counter()
+            stub.go(bodies)
+            while time.perf_counter() - t0 < 0.3:
+                stub.go(bodies)
+            calls, stats = [], None
+            for _ in range(a.runs):
+                stub.go(bodies)
+                calls.append(stub.last_call_s * 1e3)
+                stats = B.last_stats(actor)
+            calls.sort()
+            med = calls[len(calls) // 2]
+            print(json.dumps({"actor_depth": depth, "batches": nb, "plies": plies, "positions": stats["positions"],
+                              "ms_per_call": [round(x, 3) for x in calls], "median_ms": round(med, 3),
+                              "plies_per_s": round(plies / (med * 1e-3)),
+                              "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
+                  flush=True)
+            actor.close()
+
+
+if __name__ == "__main__":
+    main()
