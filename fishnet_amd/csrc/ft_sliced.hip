@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kScatterPositions) void plan_scatter_kernel(const f
 // the end of the unit holds the clamped last item and rewrites its identical
 // values (a store skipped on some path would make hipcc's vmcnt bookkeeping
 // wait for every store before the next pass's rows).
-template <int HD, bool kSwar, bool kPsqt>
+template <int HD, bool kSwar, bool kPsqt, int kPStride>
 __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict__ lb, int lane, int it_in_wave, int s,
                                            int q, const char* base, u16x4 b_lo, u16x4 b_hi, int krow,
                                            const int32_t* ptile, __amdgpu_buffer_rsrc_t psqt_rsrc,
@@ -156,9 +156,11 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
     const uint32_t li = (uint32_t)lane >> 3;
     const int src = (int)(((li & 4u) << 3) + ((0x10041400u >> (8u * (li & 3u))) & 0xFFu));
     const uint32_t reci = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)rec);
+    // The tile is bucket-major (psqt_tile.h): a pass's items nearly always
+    // share one bucket, whose rows spread over all 32 banks.
     const int bk = (int)((reci >> 21) & 7u);
-    auto pw = [&](uint32_t en) { return (uint32_t)ptile[(en >> 4) * kPsqtBuckets + bk]; };
-    uint32_t a2 = (lane & 7) == 0 ? (uint32_t)ptile[krow * kPsqtBuckets + bk] : 0u;  // own king
+    auto pw = [&](uint32_t en) { return (uint32_t)ptile[psqt_tile_word((int)(en >> 4), bk, kPStride)]; };
+    uint32_t a2 = (lane & 7) == 0 ? (uint32_t)ptile[psqt_tile_word(krow, bk, kPStride)] : 0u;  // own king
     a2 += pw(f.lst.x & 0xFFFFu) + pw(f.lst.x >> 16) + pw(f.lst.y & 0xFFFFu) + pw(f.lst.y >> 16);
     a2 += (uint32_t)__builtin_amdgcn_mov_dpp((int)a2, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
     a2 += (uint32_t)__builtin_amdgcn_mov_dpp((int)a2, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
@@ -172,7 +174,7 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
 // by the kernel so that the mixed kernel's two bodies share one copy.
 #define FT_SLICES_LDS(G)                                                                                      \
   __shared__ uint4 img[G::kTileU4];                                                                           \
-  __shared__ int32_t ptile[G::kTileRows * kPsqtBuckets]; /* slice 0 only: PSQT rows of the king block */      \
+  __shared__ int32_t ptile[psqt_tile_words(G::kTileRows)]; /* slice 0 only: PSQT rows, bucket-major */        \
   __shared__ uint2 lbuf[16][64];                         /* per wave: one pass's 8 feature lists */
 
 // One workgroup = one (unit, slice).  16 waves x 8 items per pass; records and
@@ -204,8 +206,10 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
   // store, and the first passes' lists behind them, so the fetch costs one
   // round trip instead of one per 16 KiB.
   constexpr int kTileLoads = (kTileU4 + 1023) / 1024;
-  constexpr int kPtileU4 = G::kTileRows * kPsqtBuckets / 4, kPtileRealU4 = G::kRows * kPsqtBuckets / 4;
+  constexpr int kPStride = psqt_tile_stride(G::kTileRows);
+  constexpr int kPtileU4 = psqt_fill_chunks(G::kTileRows), kPtileRealU4 = G::kRows * kPsqtBuckets / 4;
   static_assert(kPtileU4 <= 2048, "PSQT tile loads: two per thread");
+  static_assert(kPStride % 32 == 4, "bucket b's rows start on bank 4 b");
   const uint4* src = tiles + ((size_t)u.x * S + s) * kTileU4;
   uint4 t[kTileLoads];
 #pragma unroll
@@ -239,12 +243,18 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
       if constexpr (kSwar) v = swar_tile_words(v);
       img[threadIdx.x + 1024 * k] = v;
     }
-  if (s == 0) {
-    uint4* pdst = reinterpret_cast<uint4*>(ptile);
+  if (s == 0) {  // transposed on the way in (psqt_tile.h): four conflict-free ds_write_b32 per chunk
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int i = (int)threadIdx.x + 1024 * k;
-      if (i < kPtileU4) pdst[i] = i < kPtileRealU4 ? pt[k] : make_uint4(0, 0, 0, 0);
+      if (i < kPtileU4) {
+        const uint4 v = i < kPtileRealU4 ? pt[k] : make_uint4(0, 0, 0, 0);
+        const int r = psqt_fill_row(i);
+        ptile[psqt_tile_word(r, psqt_fill_bucket(i, 0), kPStride)] = (int32_t)v.x;
+        ptile[psqt_tile_word(r, psqt_fill_bucket(i, 1), kPStride)] = (int32_t)v.y;
+        ptile[psqt_tile_word(r, psqt_fill_bucket(i, 2), kPStride)] = (int32_t)v.z;
+        ptile[psqt_tile_word(r, psqt_fill_bucket(i, 3), kPStride)] = (int32_t)v.w;
+      }
     }
   }
   __syncthreads();
@@ -267,13 +277,14 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
     while (base < u.z) {
       const PassFetch cur = fa;
       fa = fetch_pass(items_rsrc, flist_rsrc, base + 256, last, lane, it_in_wave);
-      slice_pass<HD, kSwar, kPsqt>(cur, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile, psqt_rsrc, x_rsrc);
+      slice_pass<HD, kSwar, kPsqt, kPStride>(cur, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile, psqt_rsrc,
+                                             x_rsrc);
       base += 128;
       if (base >= u.z) break;
       const PassFetch cur2 = fb;
       fb = fetch_pass(items_rsrc, flist_rsrc, base + 256, last, lane, it_in_wave);
-      slice_pass<HD, kSwar, kPsqt>(cur2, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile, psqt_rsrc,
-                                   x_rsrc);
+      slice_pass<HD, kSwar, kPsqt, kPStride>(cur2, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile,
+                                             psqt_rsrc, x_rsrc);
       base += 128;
     }
   };

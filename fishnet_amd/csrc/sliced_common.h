@@ -8,10 +8,13 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "net.h"
+#include "psqt_tile.h"
 #include "slice_units.h"
 
 namespace fnnue {
 namespace {
+
+static_assert(kPsqtTileBuckets == kPsqtBuckets, "psqt_tile.h lays out the net's PSQT buckets");
 
 constexpr int kRowsPerBlock = 704;            // PS_NB: rows per king block
 constexpr int kTileRows = kRowsPerBlock + 1;  // + one zero row

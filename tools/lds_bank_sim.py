@@ -22,7 +22,16 @@ Also reported: rows per item-step (padding: a pass walks its longest list) and
 the resulting LDS cycles per useful row.  The shipped layout's prediction is
 checked against the measured SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.
 
+PSQT tile (DESIGN §4.2 "PSQT tile"): `--psqt` prices the four ds_read_b32
+gathers of a slice-0 wave-pass on the same lists for the row-major tile
+([row][8 buckets]) and the bucket-major one ([bucket][stride],
+csrc/psqt_tile.h).  Lane l holds entries 4 (l & 7) .. + 3 of pass item l >> 3
+(fetch_pass), gather j reads entry 4 (l & 7) + j; ds_read_b32 counts 32 banks
+per 32-lane half, and a half costs as many cycles as its busiest bank has
+distinct addresses.  8 cycles per pass are conflict-free.
+
 usage: python tools/lds_bank_sim.py [positions]
+       python tools/lds_bank_sim.py --psqt [positions]     (default 8000)
 """
 import sys
 
@@ -88,7 +97,76 @@ def simulate(items, lanes_per_item: int):
     return cycles, steps, useful
 
 
+PSQT_LAYOUTS = ("row-major", "bucket-major")
+
+
+def psqt_stride(rows: int) -> int:
+    """psqt_tile_stride: the tile's rows (feature rows + the zero row) rounded up to a multiple of 4."""
+    return (rows + 1 + 3) & ~3
+
+
+def psqt_pass_cycles(lists: np.ndarray, buckets: np.ndarray, layout: str, stride: int = 708) -> int:
+    """LDS-array cycles of the four PSQT gathers of one wave-pass.  lists: 8 x 32 rows (padded with
+    the zero row), buckets: the 8 items' buckets."""
+    b = np.asarray(buckets, np.int64)[:, None]
+    words = 8 * lists + b if layout == "row-major" else b * stride + lists
+    cycles = 0
+    for j in range(4):
+        w = words[:, j::4]  # item x its 8 lanes
+        for h in (0, 1):
+            addr = np.unique(w[4 * h:4 * h + 4])
+            cycles += int(np.bincount(addr % 32, minlength=32).max())
+    return cycles
+
+
+def psqt_passes(items, zero_row: int = 704):
+    """The wave-passes of the plan: items sorted by (king block, length), 8 per pass from the block's
+    start, parity-ordered lists (write_rows) padded to 32 entries; bucket = (pieces - 1) / 4."""
+    by_kb = {}
+    for kb, rows in items:
+        by_kb.setdefault(kb, []).append(rows)
+    for kb, lst in by_kb.items():
+        lst.sort(key=len)
+        for p0 in range(0, len(lst), 8):
+            pas = lst[p0:p0 + 8]
+            pas = pas + [pas[-1]] * (8 - len(pas))  # clamped lanes repeat the unit's last item
+            m = np.full((8, 32), zero_row, np.int64)
+            for j, rows in enumerate(pas):
+                first = (p0 + j) & 1
+                m[j, :len(rows)] = np.concatenate([rows[rows % 2 == first], rows[rows % 2 != first]])
+            yield m, np.array([len(r) // 4 for r in pas])  # len(r) = pieces - 1
+
+
+def psqt_main(n: int):
+    pos = F.random_playouts(1, n, threads=8)
+    tot = {k: 0 for k in PSQT_LAYOUTS}
+    by_rows = {}
+    passes = mixed = 0
+    for m, bk in psqt_passes(lists_of(pos)):
+        passes += 1
+        mixed += len(set(bk.tolist())) > 1
+        real = int((m != 704).sum(axis=1).max())
+        for k in PSQT_LAYOUTS:
+            c = psqt_pass_cycles(m, bk, k)
+            tot[k] += c
+            e = by_rows.setdefault(real, {"n": 0, **{x: 0 for x in PSQT_LAYOUTS}})
+            e[k] += c
+        by_rows[real]["n"] += 1
+    print(f"PSQT gathers of slice 0: {n} positions (random_playouts seed 1), {passes} wave-passes, "
+          f"{mixed} with more than one bucket; LDS-array cycles per wave-pass (8 = conflict-free)")
+    for k in PSQT_LAYOUTS:
+        print(f"  {k:13s} {tot[k] / passes:6.2f}")
+    print(f"  saved per pass {(tot['row-major'] - tot['bucket-major']) / passes:.2f}")
+    print("  by the pass's longest list (rows):  rows passes row-major bucket-major")
+    for r in sorted(by_rows):
+        e = by_rows[r]
+        print(f"    {r:2d} {e['n']:5d} {e['row-major'] / e['n']:6.2f} {e['bucket-major'] / e['n']:6.2f}")
+
+
 def main():
+    if "--psqt" in sys.argv:
+        rest = [a for a in sys.argv[1:] if a != "--psqt"]
+        return psqt_main(int(rest[0]) if rest else 8000)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     pos = F.random_playouts(1, n, threads=8)
     items = lists_of(pos)
