@@ -30,6 +30,9 @@ VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature
 POS_BYTES = 36
 BEST_BYTES = 24  # fnnue_best
 BEST_NONE, BEST_CP, BEST_MATE = 0, 1, 2
+LINE_BYTES = 20  # fnnue_line
+PV_LINE_BYTES = 24  # fnnue_pv_line
+MAX_CHILDREN = 218  # FNNUE_MAX_CHILDREN
 VPOS_BYTES = 48
 
 
@@ -148,6 +151,12 @@ SIGNATURES = {
     "fnnue_best_children": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp], _i32),
     "fnnue_search1_device": ([_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
     "fnnue_search1": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_topk_children_device": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp], _i32),
+    "fnnue_topk_children": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz], _i32),
+    "fnnue_search1_lines_device": ([_vp, _vp, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp],
+                                   _i32),
+    "fnnue_search1_lines": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                             _P(_sz)], _i32),
     # include/fnnue_backend.h
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),
@@ -160,6 +169,9 @@ SIGNATURES = {
     "fnnue_backend_go_compact": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32], _i32),
     "fnnue_backend_analysis_json": ([_vp, _sz, C.c_char_p, _sz, _P(_sz)], _i32),
     "fnnue_backend_last_stats": ([_vp, _vp], _i32),
+    "fnnue_backend_lines_bound": ([_vp, _sz, _P(_sz)], _i32),
+    "fnnue_backend_go_lines": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _u32], _i32),
+    "fnnue_backend_analysis_json_lines": ([_vp, _sz, _vp, _vp, C.c_char_p, _sz, _P(_sz)], _i32),
 }
 
 for _name, (_args, _res) in SIGNATURES.items():

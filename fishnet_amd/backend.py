@@ -43,6 +43,11 @@ class _Response(C.Structure):
                 ("best_move", C.c_char * 8)]
 
 
+class _PvLine(C.Structure):
+    _fields_ = [("score", C.c_int64), ("psqt", C.c_int32), ("positional", C.c_int32), ("move", C.c_char * 7),
+                ("score_kind", C.c_uint8)]
+
+
 class _Compact(C.Structure):
     _fields_ = [("psqt", C.c_int32), ("positional", C.c_int32), ("score", C.c_int32), ("score_kind", C.c_uint8),
                 ("depth", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8)]
@@ -74,6 +79,15 @@ class Score:
 
 
 @dataclass
+class PvLine:
+    """One MultiPV line of a response (fnnue_pv_line): its score and its pv, one move."""
+    score: Score
+    move: str
+    psqt: int = 0
+    positional: int = 0
+
+
+@dataclass
 class PositionResponse:
     position_id: int
     score: Score | None               # None for Skip::Skip
@@ -86,6 +100,7 @@ class PositionResponse:
     best_move: str | None = None
     skipped: bool = False
     matrix: bool = False              # AnalysisPart::Matrix (the batch asked for multipv)
+    lines: list[PvLine] | None = None  # go_lines: the MultiPV lines, best first (None: go() / no line)
 
 
 @dataclass
@@ -103,6 +118,14 @@ def batch_size(body: AcquireResponseBody) -> int:
     a, _keep = _acquired([body])
     n = C.c_size_t()
     N.check(N.lib.fnnue_backend_batch_size(C.byref(a[0]), C.byref(n)))
+    return n.value
+
+
+def lines_bound(bodies: Sequence[AcquireResponseBody]) -> int:
+    """fnnue_backend_lines_bound: the lines a go_lines() over these batches may write."""
+    a, _keep = _acquired(bodies)
+    n = C.c_size_t()
+    N.check(N.lib.fnnue_backend_lines_bound(a, len(bodies), C.byref(n)))
     return n.value
 
 
@@ -149,6 +172,18 @@ class GpuEvalStub:
         budget).  A call that overruns it raises FnnueError FNNUE_E_TIMEOUT and
         breaks the channel (fnnue_backend_go_timeout); `last_batch_rc` then
         says which batches had been answered."""
+        return self._go(bodies, timeout_ms, None)
+
+    def go_lines(self, bodies: Sequence[AcquireResponseBody], timeout_ms: int = 0,
+                 lines_cap: int | None = None) -> list[list[PositionResponse] | PositionFailed]:
+        """go() with the MultiPV lines (fnnue_backend_go_lines): on a depth-1
+        channel every non-skipped ply with a legal move of a chess analysis
+        batch with multipv = k carries `lines`, its min(k, nodes) best moves,
+        best first; every other response has lines = None.  `lines_cap`: the
+        line buffer's size (default: lines_bound(bodies))."""
+        return self._go(bodies, timeout_ms, lines_bound(bodies) if lines_cap is None else int(lines_cap))
+
+    def _go(self, bodies, timeout_ms, lines_cap):
         nb = len(bodies)
         if nb == 0:
             return []
@@ -162,7 +197,15 @@ class GpuEvalStub:
         rc = np.zeros(nb, dtype=np.int32)
         self.last_batch_rc = rc
         t0 = time.perf_counter()
-        ret = N.lib.fnnue_backend_go_timeout(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc), int(timeout_ms))
+        if lines_cap is None:
+            ret = N.lib.fnnue_backend_go_timeout(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc),
+                                                 int(timeout_ms))
+        else:
+            pv = (_PvLine * max(1, lines_cap))()
+            loff = np.zeros(cap + 1, dtype=np.uint32)
+            t0 = time.perf_counter()
+            ret = N.lib.fnnue_backend_go_lines(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc), pv, lines_cap,
+                                               N.ptr(loff), int(timeout_ms))
         self.last_call_s = time.perf_counter() - t0  # the C call alone (not the ctypes marshalling around it)
         N.check(ret)
         res: list[list[PositionResponse] | PositionFailed] = []
@@ -180,6 +223,10 @@ class GpuEvalStub:
                     r.position_id, Score("mate" if r.score_kind == SCORE_MATE else "cp", int(r.score)), r.psqt,
                     r.positional, r.depth, r.nodes, r.time_ms, r.nps, r.best_move.decode() or None,
                     matrix=bool(r.matrix)))
+                if lines_cap is not None and loff[k + 1] > loff[k]:
+                    rows[-1].lines = [
+                        PvLine(Score("mate" if l.score_kind == SCORE_MATE else "cp", int(l.score)), l.move.decode(),
+                               l.psqt, l.positional) for l in pv[int(loff[k]):int(loff[k + 1])]]
             res.append(rows)
         return res
 
@@ -285,7 +332,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
 
 
 def into_analysis(responses: Sequence[PositionResponse]) -> str:
-    """The `analysis` JSON array of a completed analysis batch (fnnue_backend_analysis_json)."""
+    """The `analysis` JSON array of a completed analysis batch (fnnue_backend_analysis_json; with
+    MultiPV lines, fnnue_backend_analysis_json_lines)."""
     arr = (_Response * max(1, len(responses)))()
     for i, r in enumerate(responses):
         if r.skipped:
@@ -295,6 +343,21 @@ def into_analysis(responses: Sequence[PositionResponse]) -> str:
         arr[i] = _Response(r.position_id, 0, kind, r.depth, 1 if r.matrix else 0, r.score.value, r.psqt,
                            r.positional, r.nodes, r.time_ms, r.nps, (r.best_move or "").encode())
     n = C.c_size_t()
+    if any(r.lines for r in responses):  # MultiPV: the matrix with one row per line
+        loff = np.zeros(len(responses) + 1, dtype=np.uint32)
+        loff[1:] = np.cumsum([len(r.lines or ()) for r in responses])
+        pv = (_PvLine * max(1, int(loff[-1])))()
+        at = 0
+        for r in responses:
+            for l in r.lines or ():
+                pv[at] = _PvLine(l.score.value, l.psqt, l.positional, l.move.encode(),
+                                 SCORE_MATE if l.score.kind == "mate" else SCORE_CP)
+                at += 1
+        N.lib.fnnue_backend_analysis_json_lines(arr, len(responses), pv, N.ptr(loff), None, 0, C.byref(n))
+        buf = C.create_string_buffer(n.value + 1)
+        N.check(N.lib.fnnue_backend_analysis_json_lines(arr, len(responses), pv, N.ptr(loff), buf, len(buf),
+                                                        C.byref(n)))
+        return buf.value.decode()
     N.lib.fnnue_backend_analysis_json(arr, len(responses), None, 0, C.byref(n))
     buf = C.create_string_buffer(n.value + 1)
     N.check(N.lib.fnnue_backend_analysis_json(arr, len(responses), buf, len(buf), C.byref(n)))

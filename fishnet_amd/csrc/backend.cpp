@@ -30,6 +30,13 @@
 // stream runs the children expansion with moves and end flags, their STAR
 // evaluation and the per-group reduction (stage_search); the piece brings back
 // one fnnue_best per ply, from which fill() writes best move, score, depth 1.
+//
+// MultiPV (fnnue_backend_go_lines, a depth-1 channel): a piece with a batch
+// that asked for k lines carries every ply's slot offsets up (after ply_off)
+// and one more kernel, fnnue_topk_children_device's, ranks the children that
+// are on the device anyway into a `lines` section behind the fnnue_best
+// records; fill() converts each ply's first min(k, nodes) lines.  go() and
+// go_compact() stage no slots and launch exactly what they did before.
 #include "../../include/fnnue_backend.h"
 
 #include <algorithm>
@@ -84,6 +91,9 @@ struct Job {
   uint32_t* off = nullptr;
   int32_t* rc = nullptr;
   uint32_t timeout_ms = 0;  // the call's budget (0: the channel's)
+  // fnnue_backend_go_lines: the MultiPV lines beside `out`, line_off per response
+  fnnue_pv_line* lines = nullptr;
+  uint32_t* line_off = nullptr;
   int ret = 0;
   std::string err;  // fnnue_last_error of a failed call
 };
@@ -166,6 +176,15 @@ void terminal_response(fnnue_position_response& r, uint8_t fin) {
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// MultiPV slots per ply of an analysis batch: Some(k) asks for k lines, and a
+// ply has at most FNNUE_MAX_CHILDREN legal moves.
+uint32_t line_slots(const fnnue_acquired& a) {
+  return a.work == FNNUE_WORK_ANALYSIS && a.multipv >= 1 ? (uint32_t)std::min(a.multipv, FNNUE_MAX_CHILDREN) : 0u;
+}
+static_assert(sizeof(fnnue_pv_line) == 24 && offsetof(fnnue_pv_line, move) == 16 &&
+                  offsetof(fnnue_pv_line, score_kind) == 23,
+              "fnnue_pv_line layout");
 
 // A full response written in place as four stores — bytes 0-15 (position id,
 // the four flag bytes, score), 16-31 (psqt, positional, nodes), 32-47 and
@@ -309,6 +328,10 @@ struct Piece {
   bool depth1 = false;
   size_t st0 = 0;
   size_t searched = 0;
+  // MultiPV (fnnue_backend_go_lines at depth 1): the plies' slot offsets go up
+  // at o_loff (n + 1 words: min(multipv, 218) slots for every ply of a batch
+  // that asked), and the results image ends with the nslots fnnue_line slots.
+  size_t nslots = 0, o_loff = 0, o_lines = 0;
   bool pending = false;                           // evaluation enqueued, results not yet read
 };
 
@@ -436,6 +459,7 @@ struct fnnue_backend {
   std::vector<int8_t> kind;          // per batch: its net slot
   std::vector<uint8_t> bskip;        // per batch: has skipPositions
   std::vector<uint8_t> skip;         // per response of such a batch: skipped
+  std::vector<size_t> lbase;         // go_lines: per batch, where fill() puts its lines before close_lines() packs them
   std::mutex stats_mu;
   fnnue_backend_stats stats{};
   // per go(): its clock, positions written so far, host time spent writing / waiting
@@ -479,6 +503,7 @@ struct fnnue_backend {
   void fill(Job& j, int k, const Piece& P);
   void fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint32_t nps);
   void fill_hostonly(Job& j, const std::vector<size_t>& all_skipped);
+  void close_lines(Job& j);
 };
 
 int fnnue_backend::timed_out(const char* where) {
@@ -607,17 +632,22 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.n = (uint32_t)plies;
   P.nk = P.kids ? W.nk : 0;
   const size_t ng = P.ng, n = P.n, nk = P.nk;
+  P.depth1 = analysis_depth == 1 && k == kVariantChess && ng;
+  P.nslots = 0;
+  if (j.lines && P.depth1)
+    for (size_t i : P.games) P.nslots += (size_t)(j.off[i + 1] - j.off[i]) * line_slots(j.batches[i]);
   P.o_fen = align16(text);
   P.o_mv = P.o_fen + 4 * (ng + 1);
   P.o_ply = P.o_mv + 4 * ng;
-  P.o_kids = align16(P.o_ply + 4 * (ng + 1));
+  P.o_loff = P.o_ply + 4 * (ng + 1);
+  P.o_kids = align16(P.o_loff + (P.nslots ? 4 * (n + 1) : 0));
   P.o_res = align16(P.o_kids + nk * W.rec);
   P.o_fin = P.o_res + 16;
   P.o_ps = align16(P.o_fin + ng);
   P.o_po = P.o_ps + 4 * (n + nk);
   P.o_best = align16(P.o_po + 4 * (n + nk));
-  P.depth1 = analysis_depth == 1 && k == kVariantChess && ng;
-  P.end = P.depth1 ? P.o_best + n * sizeof(fnnue_best) : P.o_po + 4 * (n + nk);
+  P.o_lines = P.o_best + n * sizeof(fnnue_best);
+  P.end = P.depth1 ? P.o_lines + P.nslots * sizeof(fnnue_line) : P.o_po + 4 * (n + nk);
 }
 
 // Cuts the net's games into pieces and places them in its (grow-only) buffers.
@@ -665,6 +695,7 @@ int fnnue_backend::plan(Job& j, int k) {
   for (Piece& P : W.pieces) {
     layout(j, k, P);
     if (P.o_fen >= (1ull << 31)) return fail(FNNUE_E_ARG, "batch text too large");
+    if (P.nslots > UINT32_MAX) return fail(FNNUE_E_ARG, "too many MultiPV lines in one piece");
     P.up0 = up;
     P.down0 = down;
     P.dev0 = dev;
@@ -706,6 +737,16 @@ int fnnue_backend::stage_up(Job& j, int k, size_t pi) {
   }
   fo[P.ng] = text;
   po[P.ng] = acc;
+  if (P.nslots) {  // MultiPV: every ply's slots, in ply order
+    uint32_t* lo = reinterpret_cast<uint32_t*>(img + P.o_loff);
+    uint32_t slot = 0, p = 0;
+    for (uint32_t g = 0; g < P.ng; ++g) {
+      const size_t i = P.games[g];
+      const uint32_t kk = line_slots(j.batches[i]);
+      for (uint32_t q = j.off[i + 1] - j.off[i]; q; --q, slot += kk) lo[p++] = slot;
+    }
+    lo[p] = slot;
+  }
   pool.run(P.ng, stage_grain, [&](size_t lo, size_t hi) {
     for (size_t g = lo; g < hi; ++g) {
       const size_t i = P.games[g];
@@ -831,6 +872,11 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
                                s),
           "best_children launch");
+  if (P.nslots)  // a go_lines() call whose piece has a batch that asked for MultiPV
+    HIP_TRY(launch_topk_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
+                                 reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
+                                 reinterpret_cast<fnnue_line*>(dimg + P.o_lines), P.nslots, s),
+            "topk_children launch");
   HIP_TRY(launch_gather_parents(kps, kpo, coff, n, (uint32_t)total, reinterpret_cast<int32_t*>(dimg + P.o_ps),
                                 reinterpret_cast<int32_t*>(dimg + P.o_po), s),
           "gather_parents launch");
@@ -967,6 +1013,9 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const uint32_t* ply = W.up.at<uint32_t>(P.up0 + P.o_ply);
   filled += P.n + P.nk + P.searched;
   const fnnue_best* best = P.depth1 ? reinterpret_cast<const fnnue_best*>(res + (P.o_best - P.o_res)) : nullptr;
+  const bool with_lines = P.depth1 && P.nslots && j.lines;
+  const fnnue_line* dlines = with_lines ? reinterpret_cast<const fnnue_line*>(res + (P.o_lines - P.o_res)) : nullptr;
+  const uint32_t* loff = with_lines ? W.up.at<uint32_t>(P.up0 + P.o_loff) : nullptr;
   const double el = ms_since(t0);
   const uint64_t ms = (uint64_t)el;
   const uint32_t nps = el > 0 ? (uint32_t)std::min(4.0e9, (double)filled / (el * 1e-3)) : 0;
@@ -989,6 +1038,7 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
         // game's last one without a legal move, answered as at depth 0.
         const fnnue_best* gb = best + ply[g];
         const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
+        const uint32_t kk = dlines ? line_slots(j.batches[i]) : 0;
         for (uint32_t q = 0; q < len; ++q) {
           const fnnue_best& B = gb[q];
           const bool skipped = sk && skip[b + q];
@@ -1012,6 +1062,26 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           }
           put_response(r, response_head(q, 0, kind, none ? 0 : 1, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
           if (!none) (void)fnnue_move_uci(B.move, r->best_move);
+          if (none || !kk) continue;
+          // MultiPV: the first min(slots, nodes) lines of the ply, at the
+          // batch's provisional place (close_lines() packs them afterwards)
+          const uint32_t nl = std::min(kk, B.nodes);
+          const fnnue_line* src = dlines + loff[ply[g] + q];
+          fnnue_pv_line* dst = j.lines + lbase[i] + (size_t)q * kk;
+          for (uint32_t l = 0; l < nl; ++l) {
+            const fnnue_line& L = src[l];
+            const bool lm = L.kind == FNNUE_BEST_MATE;
+            char mv[8];
+            (void)fnnue_move_uci(L.move, mv);
+            fnnue_pv_line out{};
+            out.score = lm ? 1 : (int64_t)L.value * 100 / nrm;
+            out.psqt = L.psqt;
+            out.positional = L.positional;
+            std::memcpy(out.move, mv, 6);  // at most "e7e8q" and its NUL
+            out.score_kind = lm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+            dst[l] = out;
+          }
+          j.line_off[b + q + 1] = nl;  // a count for now
         }
         if (j.cout) {
           fnnue_batch_compact& B = j.bout[i];
@@ -1167,6 +1237,26 @@ void fnnue_backend::fill_hostonly(Job& j, const std::vector<size_t>& all_skipped
   }
 }
 
+// go_lines: fill() left every response's lines at its batch's provisional
+// place (lbase: the bound's own prefix sums, so they never overlap) and its
+// count in line_off; here the lines are packed in response order and the
+// counts become offsets.  A batch that failed keeps an empty range.
+void fnnue_backend::close_lines(Job& j) {
+  if (!j.lines) return;
+  size_t w = 0;
+  j.line_off[0] = 0;
+  for (size_t i = 0; i < j.nb; ++i) {
+    const uint32_t kk = line_slots(j.batches[i]);
+    for (uint32_t r = j.off[i]; r < j.off[i + 1]; ++r) {
+      const uint32_t nl = j.rc[i] ? 0 : j.line_off[r + 1];
+      const size_t from = lbase[i] + (size_t)(r - j.off[i]) * kk;
+      if (nl && from != w) std::memmove(j.lines + w, j.lines + from, nl * sizeof(fnnue_pv_line));
+      w += nl;
+      j.line_off[r + 1] = (uint32_t)w;
+    }
+  }
+}
+
 void fnnue_backend::run(Job& j) {
   t0 = Clock::now();
   deadline = t0 + std::chrono::milliseconds(j.timeout_ms ? j.timeout_ms : timeout_ms);
@@ -1236,6 +1326,15 @@ void fnnue_backend::run(Job& j) {
     return;
   }
   for (NetWork& W : net) W.clear();
+  if (j.lines) {  // every response without lines until fill() says otherwise
+    std::memset(j.line_off, 0, ((size_t)j.off[nb] + 1) * sizeof(uint32_t));
+    lbase.resize(nb);
+    size_t at = 0;
+    for (size_t i = 0; i < nb; ++i) {
+      lbase[i] = at;
+      at += (size_t)(j.off[i + 1] - j.off[i]) * line_slots(j.batches[i]);
+    }
+  }
   if (skip.size() < j.off[nb]) skip.resize(j.off[nb]);  // read only for batches with bskip set
   std::vector<size_t> all_skipped;
   for (size_t i = 0; i < nb; ++i) {
@@ -1346,6 +1445,7 @@ void fnnue_backend::run(Job& j) {
     // the answers that need no device (roots without a legal move, batches
     // whose every position is skipped) are written: they are valid
     fill_hostonly(j, all_skipped);
+    close_lines(j);
     j.ret = rc;
     j.err = g_err;
     return;
@@ -1358,6 +1458,7 @@ void fnnue_backend::run(Job& j) {
     return;
   }
   fill_hostonly(j, all_skipped);
+  close_lines(j);
   uint32_t npieces = 0;
   for (const NetWork& W : net) npieces += (uint32_t)W.pieces.size();
   j.ret = FNNUE_OK;
@@ -1580,6 +1681,35 @@ int fnnue_backend_go_compact(fnnue_backend* b, const fnnue_acquired* batches, si
   return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
 }
 
+int fnnue_backend_lines_bound(const fnnue_acquired* batches, size_t nbatches, size_t* n) {
+  if (!n || (nbatches && !batches)) return fail(FNNUE_E_ARG, "null argument");
+  size_t total = 0;
+  for (size_t i = 0; i < nbatches; ++i)
+    if (const uint32_t kk = line_slots(batches[i])) total += (count_moves(batches[i].moves) + 1) * kk;
+  *n = total;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_go_lines(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches,
+                           fnnue_position_response* out, size_t cap, uint32_t* off, int32_t* batch_rc,
+                           fnnue_pv_line* lines, size_t lines_cap, uint32_t* line_off, uint32_t timeout_ms) {
+  if (!b || !off || !batch_rc || !line_off || (nbatches && !batches) || (cap && !out) || (lines_cap && !lines))
+    return fail(FNNUE_E_ARG, "null argument");
+  if (nbatches > (1u << 24)) return fail(FNNUE_E_ARG, "too many batches");
+  size_t bound = 0;
+  if (int rc = fnnue_backend_lines_bound(batches, nbatches, &bound)) return rc;
+  if (bound > UINT32_MAX) return fail(FNNUE_E_ARG, "the batches ask for more than 2^32 - 1 lines");
+  if (lines_cap < bound)
+    return fail(FNNUE_E_CAPACITY, "line buffer holds " + std::to_string(lines_cap) + ", batches may need " +
+                                      std::to_string(bound));
+  fnnue_pv_line none;  // a call that can have no line still runs as a go_lines() call
+  Job j;
+  j.out = out;
+  j.lines = lines ? lines : &none;
+  j.line_off = line_off;
+  return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
+}
+
 int fnnue_backend_go(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches, fnnue_position_response* out,
                      size_t cap, uint32_t* off, int32_t* batch_rc) {
   return fnnue_backend_go_timeout(b, batches, nbatches, out, cap, off, batch_rc, 0);
@@ -1600,8 +1730,12 @@ int fnnue_backend_last_stats(fnnue_backend* b, fnnue_backend_stats* out) {
   return FNNUE_OK;
 }
 
-int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char* buf, size_t cap, size_t* len) {
-  if ((n && !r) || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
+}  // extern "C"
+
+namespace {
+// Both JSON forms: without `lines` every response has its own one line.
+int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_line* lines, const uint32_t* line_off,
+                  char* buf, size_t cap, size_t* len) {
   std::string s = "[";
   char tmp[192];
   for (size_t i = 0; i < n; ++i) {
@@ -1622,7 +1756,30 @@ int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char
     pv[7] = 0;
     for (char* c = pv; *c; ++c)
       if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';  // never from this library
-    if (r[i].matrix) {
+    const size_t nl = line_off && r[i].matrix ? line_off[i + 1] - line_off[i] : 0;  // lines are rows of the matrix form
+    if (nl) {
+      // Matrix::set per line: row l is `depth` nulls and then the entry
+      const fnnue_pv_line* L = lines + (line_off[i] - line_off[0]);
+      std::string nulls;
+      for (unsigned d = 0; d < r[i].depth; ++d) nulls += "null,";
+      s += "{\"pv\":[";
+      for (size_t l = 0; l < nl; ++l) {
+        char mv[8] = {0};
+        std::memcpy(mv, L[l].move, 7);
+        mv[6] = 0;
+        for (char* c = mv; *c; ++c)
+          if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';
+        s += (l ? ",[" : "[") + nulls + (mv[0] ? std::string("[\"") + mv + "\"]" : std::string("[]")) + "]";
+      }
+      s += "],\"score\":[";
+      for (size_t l = 0; l < nl; ++l) {
+        std::snprintf(tmp, sizeof(tmp), "{\"%s\":%lld}]", L[l].score_kind == FNNUE_SCORE_MATE ? "mate" : "cp",
+                      (long long)L[l].score);
+        s += (l ? ",[" : "[") + nulls + tmp;
+      }
+      std::snprintf(tmp, sizeof(tmp), "],\"depth\":%u,\"nodes\":%llu,\"time\":%llu", (unsigned)r[i].depth,
+                    (unsigned long long)r[i].nodes, (unsigned long long)r[i].time_ms);
+    } else if (r[i].matrix) {
       s += "{\"pv\":[[";
       for (unsigned d = 0; d < r[i].depth; ++d) s += "null,";
       s += pv[0] ? std::string("[\"") + pv + "\"]" : std::string("[]");
@@ -1653,6 +1810,23 @@ int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char
   }
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return FNNUE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char* buf, size_t cap, size_t* len) {
+  if ((n && !r) || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
+  return analysis_json(r, n, nullptr, nullptr, buf, cap, len);
+}
+
+int fnnue_backend_analysis_json_lines(const fnnue_position_response* r, size_t n, const fnnue_pv_line* lines,
+                                      const uint32_t* line_off, char* buf, size_t cap, size_t* len) {
+  if ((n && !r) || !line_off || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
+  if (line_off[n] != line_off[0] && !lines) return fail(FNNUE_E_ARG, "null argument");
+  for (size_t i = 0; i < n; ++i)
+    if (line_off[i] > line_off[i + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
+  return analysis_json(r, n, lines, line_off, buf, cap, len);
 }
 
 }  // extern "C"

@@ -125,6 +125,13 @@ hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_
 hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
                                 const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
                                 fnnue_best* d_out, hipStream_t s);
+// The k best children of every group as fnnue_line records: group g's slots are
+// [d_line_off[g], d_line_off[g + 1]), or [g * uniform_k, (g + 1) * uniform_k)
+// when d_line_off is null; nothing is written at or beyond lines_cap.
+hipError_t launch_topk_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
+                                const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
+                                const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line* d_lines, size_t lines_cap,
+                                hipStream_t s);
 hipError_t launch_gather_parents(const int32_t* d_psqt, const int32_t* d_positional, const uint32_t* d_off,
                                  uint32_t ngroups, uint32_t npos, int32_t* d_ps_out, int32_t* d_po_out, hipStream_t s);
 

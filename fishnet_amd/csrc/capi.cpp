@@ -393,7 +393,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      FNNUE_SYNTH_HEAVY
 // 3.4: the one-ply search: fnnue_move / fnnue_move_uci, fnnue_build_children[_device],
 //      fnnue_best / fnnue_best_children[_device], fnnue_search1[_device], fnnue_backend_set_analysis_depth
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 4u; }
+// 3.5: MultiPV at depth 1: fnnue_line / fnnue_topk_children[_device], fnnue_search1_lines[_device],
+//      fnnue_pv_line / fnnue_backend_go_lines, fnnue_backend_lines_bound, fnnue_backend_analysis_json_lines
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 5u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1464,9 +1466,74 @@ int fnnue_best_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* posi
   return FNNUE_OK;
 }
 
-int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                         size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
-                         size_t* n_groups, void* stream) {
+int fnnue_topk_children_device(fnnue_ctx* ctx, const int32_t* d_psqt, const int32_t* d_positional,
+                               const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off, size_t ngroups,
+                               size_t npos, const uint32_t* d_line_off, fnnue_line* d_lines, size_t lines_cap,
+                               void* stream) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!d_psqt || !d_positional || !d_end || !d_off || !d_line_off || (lines_cap && !d_lines))
+    return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  if (lines_cap == 0) return FNNUE_OK;  // no slot may be written
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  HIP_TRY(launch_topk_children(d_psqt, d_positional, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos,
+                               d_line_off, 0, d_lines, lines_cap, s),
+          "topk_children launch");
+  return FNNUE_OK;
+}
+
+int fnnue_topk_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* positional, const uint8_t* end,
+                        const fnnue_move* moves, const uint32_t* off, size_t ngroups, size_t npos,
+                        const uint32_t* line_off, fnnue_line* lines, size_t lines_cap) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!off || !line_off || (npos && (!psqt || !positional || !end))) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  for (size_t g = 0; g < ngroups; ++g)
+    if (line_off[g] > line_off[g + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
+  const size_t nl = line_off[ngroups];
+  if (nl > lines_cap) return fail(FNNUE_E_CAPACITY, "line buffer too small");
+  if (nl && !lines) return fail(FNNUE_E_ARG, "null buffer");
+  if (nl == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  // [psqt | positional | off | line_off | lines | moves | end]: 4-byte parts first
+  const size_t n4 = npos * 4, o_off = 2 * n4, o_loff = o_off + (ngroups + 1) * 4, o_lines = o_loff + (ngroups + 1) * 4;
+  const size_t o_mv = o_lines + nl * sizeof(fnnue_line), o_end = o_mv + npos * 2;
+  TempDev buf;
+  if (int rc = buf.get(o_end + npos)) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  if (npos) {
+    HIP_TRY(hipMemcpyAsync(d, psqt, n4, hipMemcpyHostToDevice, s), "H2D");
+    HIP_TRY(hipMemcpyAsync(d + n4, positional, n4, hipMemcpyHostToDevice, s), "H2D");
+    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
+    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  HIP_TRY(hipMemcpyAsync(d + o_loff, line_off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  // the caller's lines go up first, so that slots no group writes (empty groups) come back as they were
+  HIP_TRY(hipMemcpyAsync(d + o_lines, lines, nl * sizeof(fnnue_line), hipMemcpyHostToDevice, s), "H2D");
+  const int rc = fnnue_topk_children_device(
+      ctx, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + n4), reinterpret_cast<uint8_t*>(d + o_end),
+      moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr, reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
+      reinterpret_cast<uint32_t*>(d + o_loff), reinterpret_cast<fnnue_line*>(d + o_lines), nl, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(lines, d + o_lines, nl * sizeof(fnnue_line), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// fnnue_search1_device, and with k >= 1 fnnue_search1_lines_device: ply p's k
+// best children at d_lines[p * k ..] from the same scratch, behind the reduction.
+int search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                   size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
+                   fnnue_line* d_lines, size_t lines_cap, size_t* n_out, size_t* n_groups, void* stream) {
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
   if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
@@ -1479,6 +1546,7 @@ int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_f
   WorkspaceUse use{ctx, s};
   ChildrenBufs kids;
   kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  if (k) kids.max_groups = d_lines ? std::min(kids.max_groups, lines_cap / k) : 0;
   size_t nrec = 0, nply = 0;
   rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
                     nullptr, nullptr, &nrec, &nply, s, &kids);
@@ -1492,13 +1560,18 @@ int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_f
   if ((rc = fnnue_eval_groups_device(ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s))) return rc;
   HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
           "best_children launch");
+  if (k)
+    HIP_TRY(launch_topk_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, nullptr, k,
+                                 d_lines, lines_cap, s),
+            "topk_children launch");
   HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
   return FNNUE_OK;
 }
 
-int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                  const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
-                  size_t* n_out, size_t* n_groups) {
+// The host-buffer forms: staged through the ctx's stream.
+int search1_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
+                 size_t ngames, uint32_t k, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
+                 fnnue_line* lines, size_t lines_cap, size_t* n_out, size_t* n_groups) {
   if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
     return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
@@ -1509,20 +1582,60 @@ int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint3
   uint32_t *d_fo = nullptr, *d_mo = nullptr;
   int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
   if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1;
+  const bool room = out && off && off_cap >= ngames + 1 && (!k || lines);
+  // [best | lines | off]: the lines' room is cut to whole plies the records have room for
+  const size_t nl = k ? std::min(lines_cap / k, cap) * k : 0;
   TempDev buf;
-  const size_t o_off = cap * sizeof(fnnue_best);
+  const size_t o_lines = cap * sizeof(fnnue_best), o_off = o_lines + nl * sizeof(fnnue_line);
   if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
   char* d = static_cast<char*>(buf.p);
   hipStream_t s = ctx->stream;
-  rc = fnnue_search1_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
-                            room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
-                            room ? off_cap : 0, n_out, n_groups, s);
+  rc = search1_device(ctx, d_text, d_fo, d_mo, ngames, k, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
+                      room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
+                      room && k ? reinterpret_cast<fnnue_line*>(d + o_lines) : nullptr, room ? nl : 0, n_out,
+                      n_groups, s);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
+  if (k) HIP_TRY(hipMemcpyAsync(lines, d + o_lines, *n_out * k * sizeof(fnnue_line), hipMemcpyDeviceToHost, s), "D2H");
   HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return latched(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                         size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
+                         size_t* n_groups, void* stream) {
+  return search1_device(ctx, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr, 0, n_out,
+                        n_groups, stream);
+}
+
+int fnnue_search1_lines_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                               const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
+                               uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
+                               size_t* n_groups, void* stream) {
+  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
+  return search1_device(ctx, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines, lines_cap,
+                        n_out, n_groups, stream);
+}
+
+int fnnue_search1_lines(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                        const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap,
+                        uint32_t* off, size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out,
+                        size_t* n_groups) {
+  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
+  return search1_host(ctx, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines, lines_cap,
+                      n_out, n_groups);
+}
+
+int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                  const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
+                  size_t* n_out, size_t* n_groups) {
+  return search1_host(ctx, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0, n_out,
+                      n_groups);
 }
 
 int fnnue_build_batch(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,

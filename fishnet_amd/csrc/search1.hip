@@ -10,6 +10,8 @@
 // the first maximum whatever lane saw it; five xor-shuffles inside the half
 // wave leave it in every lane, and lanes 0-5 store one dword each of the
 // 24-byte record.  No atomics, no LDS, no host synchronisation.
+// The k best children of every group (fnnue_topk_children_device, MultiPV):
+// topk_children_kernel below, the same key ranked by counting in LDS.
 #include <hip/hip_runtime.h>
 
 #include "builder.h"
@@ -73,6 +75,117 @@ __global__ __launch_bounds__(kBlock) void best_children_kernel(
   if (live && lane < 6) out[(size_t)g * 6 + lane] = w;
 }
 
+// ---- the k best children per group (fnnue_topk_children_device, MultiPV) ----
+// The same half wave per group and the same key, extended to a total order:
+// the keys of a group are unique (~index), so the number of keys larger than a
+// child's own is its place in the descending order.  Rank by counting: each
+// half wave stages its keys once in LDS; every lane keeps up to kTopkRegs keys
+// of its own in registers (children lane + 1, lane + 33, ...: static indexing)
+// and reads each key of the group by a same-address ds_read_b64 (a broadcast:
+// no bank conflict), counting those above its own.  A child whose count is
+// below the group's slot count writes its own 20-byte line at that slot.  No
+// sorting network, no dependent reduction rounds, and the cost does not depend
+// on the slot count.  Groups beyond kTopkFast children (variant nets, hand-made
+// input) recompute every key from global memory instead: correct, not fast.
+constexpr uint32_t kTopkRegs = 8, kTopkFast = kGroupLanes * kTopkRegs, kTopkGroups = kBlock / kGroupLanes;
+static_assert(sizeof(fnnue_line) == 20, "fnnue_line is five dwords");
+static_assert(kTopkFast >= FNNUE_MAX_CHILDREN, "every chess ply takes the fast path");
+
+__device__ __forceinline__ unsigned long long child_key(const int32_t* __restrict__ psqt,
+                                                        const int32_t* __restrict__ positional,
+                                                        const uint8_t* __restrict__ end, uint32_t o, uint32_t c) {
+  const uint32_t x = o + c;
+  const uint32_t f = end[x];
+  uint32_t rank = 1;
+  int32_t v = 0;
+  if (f & kFinalNoMoves) {
+    rank = (f & kFinalCheck) ? 2u : 1u;
+  } else {
+    v = (int32_t)-(((long long)psqt[x] + (long long)positional[x]) / 16);
+  }
+  return (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+}
+
+__device__ __forceinline__ void write_line(uint32_t* __restrict__ lines, uint64_t slot, unsigned long long key,
+                                           const int32_t* __restrict__ psqt, const int32_t* __restrict__ positional,
+                                           const uint16_t* __restrict__ moves, uint32_t o) {
+  const uint32_t c = 0xFFFFFFFFu - (uint32_t)key;
+  const uint32_t kind = (uint32_t)(key >> 62) == 2 ? FNNUE_BEST_MATE : FNNUE_BEST_CP;
+  const int32_t value = (int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29);
+  uint32_t* w = lines + slot * 5;
+  w[0] = 0u - (uint32_t)psqt[o + c];  // negated, wrapping
+  w[1] = 0u - (uint32_t)positional[o + c];
+  w[2] = kind == FNNUE_BEST_CP ? (uint32_t)value : 0u;
+  w[3] = c;
+  w[4] = (moves ? (uint32_t)moves[o + c] : 0u) | kind << 16;
+}
+
+__global__ __launch_bounds__(kBlock) void topk_children_kernel(
+    const int32_t* __restrict__ psqt, const int32_t* __restrict__ positional, const uint8_t* __restrict__ end,
+    const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off, uint32_t ngroups, uint32_t npos,
+    const uint32_t* __restrict__ line_off, uint32_t uniform_k, uint32_t* __restrict__ lines, uint64_t lines_cap) {
+  __shared__ unsigned long long staged[kTopkGroups][kTopkFast];
+  const uint32_t hw = threadIdx.x / kGroupLanes, lane = threadIdx.x % kGroupLanes;
+  const uint64_t g64 = (uint64_t)blockIdx.x * kTopkGroups + hw;
+  const bool live = g64 < ngroups;  // no early return: the barrier below runs with the whole block
+  const uint32_t g = (uint32_t)g64;
+  uint32_t o = 0, e = 0;
+  uint64_t lo = 0, k = 0;  // the group's slots [lo, lo + k), cut at lines_cap
+  if (live) {
+    e = min(off[g + 1], npos);
+    o = min(off[g], e);
+    if (line_off) {
+      lo = line_off[g];
+      const uint64_t hi = line_off[g + 1];
+      k = hi > lo ? hi - lo : 0;
+    } else {
+      lo = (uint64_t)g * uniform_k;
+      k = uniform_k;
+    }
+    k = lo < lines_cap ? min(k, lines_cap - lo) : 0;
+  }
+  const uint32_t nrec = e - o;
+  const uint32_t nkids = nrec && k ? nrec - 1 : 0;  // nothing to rank without a slot
+  const bool fast = nkids <= kTopkFast;
+  unsigned long long key[kTopkRegs];
+#pragma unroll
+  for (uint32_t i = 0; i < kTopkRegs; ++i) {
+    const uint32_t q = lane + kGroupLanes * i;  // child q + 1
+    key[i] = 0;
+    if (fast && q < nkids) {
+      key[i] = child_key(psqt, positional, end, o, q + 1);
+      staged[hw][q] = key[i];
+    }
+  }
+  __syncthreads();
+  if (fast) {
+    uint32_t above[kTopkRegs];
+#pragma unroll
+    for (uint32_t i = 0; i < kTopkRegs; ++i) above[i] = 0;
+    for (uint32_t q = 0; q < nkids; ++q) {
+      const unsigned long long other = staged[hw][q];  // the same address in every lane of the half wave
+#pragma unroll
+      for (uint32_t i = 0; i < kTopkRegs; ++i) above[i] += other > key[i] ? 1u : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kTopkRegs; ++i)
+      if (key[i] && above[i] < k) write_line(lines, lo + above[i], key[i], psqt, positional, moves, o);
+  } else {
+    for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
+      const unsigned long long mine = child_key(psqt, positional, end, o, c);
+      uint32_t above = 0;
+      for (uint32_t q = 1; q < nrec; ++q) above += child_key(psqt, positional, end, o, q) > mine ? 1u : 0u;
+      if (above < k) write_line(lines, lo + above, mine, psqt, positional, moves, o);
+    }
+  }
+  // slots beyond the group's children: all zero (an empty group writes nothing)
+  if (nrec)
+    for (uint64_t j = (uint64_t)nkids + lane; j < k; j += kGroupLanes) {
+      uint32_t* w = lines + (lo + j) * 5;
+      w[0] = w[1] = w[2] = w[3] = w[4] = 0u;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void gather_parents_kernel(const int32_t* __restrict__ psqt,
                                                                 const int32_t* __restrict__ positional,
                                                                 const uint32_t* __restrict__ off, uint32_t ngroups,
@@ -95,6 +208,17 @@ hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_position
   const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
   hipLaunchKernelGGL(best_children_kernel, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                      d_psqt, d_positional, d_end, d_moves, d_off, ngroups, npos, reinterpret_cast<uint32_t*>(d_out));
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
+                                const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
+                                const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line* d_lines, size_t lines_cap,
+                                hipStream_t s) {
+  if (ngroups == 0) return hipSuccess;
+  hipLaunchKernelGGL(topk_children_kernel, dim3((uint32_t)(((uint64_t)ngroups + kTopkGroups - 1) / kTopkGroups)), dim3(kBlock), 0, s, d_psqt,
+                     d_positional, d_end, d_moves, d_off, ngroups, npos, d_line_off, uniform_k,
+                     reinterpret_cast<uint32_t*>(d_lines), (uint64_t)lines_cap);
   return hipGetLastError();
 }
 

@@ -227,6 +227,17 @@ BEST_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"),
 BEST_NONE, BEST_CP, BEST_MATE = N.BEST_NONE, N.BEST_CP, N.BEST_MATE
 
 
+class Line(C.Structure):
+    """fnnue_line: one of a group's k best children (MultiPV at depth 1); kind BEST_NONE = an unused slot."""
+    _fields_ = [("psqt", C.c_int32), ("positional", C.c_int32), ("value", C.c_int32), ("child", C.c_uint32),
+                ("move", C.c_uint16), ("kind", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+LINE_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"), ("move", "<u2"),
+                       ("kind", "u1"), ("reserved", "u1")])
+MAX_CHILDREN = N.MAX_CHILDREN
+
+
 def move_uci(code: int) -> str:
     """A fnnue_move code as UCI text ("" for 0); FnnueError FNNUE_E_ARG for a code that is no move."""
     buf = C.create_string_buffer(8)
@@ -454,6 +465,63 @@ class Evaluator:
         N.check(N.lib.fnnue_search1_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
                                            ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n),
                                            C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    # MultiPV at depth 1 (ABI 3.5)
+    def topk_children(self, psqt, positional, end, moves, off, k_or_line_off, lines_cap: int | None = None,
+                      fill: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_topk_children: the k best children of every STAR group -> (LINE_DTYPE slots, line_off).
+        `k_or_line_off`: one slot count for every group, or the ngroups + 1 slot offsets.  `lines_cap`
+        (default: line_off[-1]) sizes the buffer; its bytes start as `fill`, so that a caller can
+        see which slots were written."""
+        psqt = np.ascontiguousarray(psqt, dtype=np.int32)
+        positional = np.ascontiguousarray(positional, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        if moves is not None:
+            moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        ng = len(off) - 1
+        if np.ndim(k_or_line_off) == 0:
+            line_off = (np.arange(ng + 1, dtype=np.uint64) * int(k_or_line_off)).astype(np.uint32)
+        else:
+            line_off = np.ascontiguousarray(k_or_line_off, dtype=np.uint32)
+        cap = int(line_off[-1]) if lines_cap is None else int(lines_cap)
+        lines = np.full(max(cap, 1) * N.LINE_BYTES, fill, dtype=np.uint8).view(LINE_DTYPE)
+        N.check(N.lib.fnnue_topk_children(self._h, N.ptr(psqt), N.ptr(positional), N.ptr(end), N.ptr(moves),
+                                          N.ptr(off), ng, len(psqt), N.ptr(line_off), N.ptr(lines), cap))
+        return lines[:cap], line_off
+
+    def topk_children_device(self, d_psqt: int, d_positional: int, d_end: int, d_moves: int | None, d_off: int,
+                             ngroups: int, npos: int, d_line_off: int, d_lines: int, lines_cap: int,
+                             stream: int | None):
+        N.check(N.lib.fnnue_topk_children_device(self._h, C.c_void_p(d_psqt), C.c_void_p(d_positional),
+                                                 C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off), ngroups,
+                                                 npos, C.c_void_p(d_line_off), C.c_void_p(d_lines), lines_cap,
+                                                 C.c_void_p(stream)))
+
+    def search1_lines(self, games, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fnnue_search1_lines: search1 plus each ply's k best children ->
+        (BEST_DTYPE records, CHAIN offsets per game, LINE_DTYPE slots of shape (plies, k))."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        lines = np.zeros(max(cap * max(int(k), 0), 1), dtype=LINE_DTYPE)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search1_lines(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), int(k),
+                                          N.ptr(out), cap, N.ptr(off), len(off), N.ptr(lines), cap * int(k),
+                                          C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1], lines[: n.value * int(k)].reshape(n.value, int(k))
+
+    def search1_lines_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, k: int, d_out: int,
+                             cap: int, d_off: int, off_cap: int, d_lines: int, lines_cap: int,
+                             stream: int | None) -> tuple[int, int]:
+        """fnnue_search1_lines_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when a buffer is too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search1_lines_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                 C.c_void_p(d_moves_off), ngames, int(k), C.c_void_p(d_out), cap,
+                                                 C.c_void_p(d_off), off_cap, C.c_void_p(d_lines), lines_cap,
+                                                 C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
     def perft_device(self, fen: str, depth: int) -> int:

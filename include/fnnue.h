@@ -463,6 +463,53 @@ int fnnue_search1(fnnue_ctx *ctx, const char *text, size_t text_len, const uint3
                   const uint32_t *moves_off, size_t ngames, fnnue_best *out, size_t cap, uint32_t *off,
                   size_t off_cap, size_t *n_out, size_t *n_groups);
 
+/* ---- MultiPV at depth 1: the k best children of a group (ABI 3.5) ----
+ * fnnue_best_children's rule extended to a total order: the mates in one
+ * first, in index order; then the children by value (a stalemating child worth
+ * 0), descending; equal values by lower index.  A chess ply has at most
+ * FNNUE_MAX_CHILDREN children. */
+#define FNNUE_MAX_CHILDREN 218
+typedef struct {
+  int32_t psqt, positional; /* of this child, negated with wrap-around, as fnnue_best reports them */
+  int32_t value;            /* internal units, parent's side to move; 0 for a mate */
+  uint32_t child;           /* 1-based record index within the group */
+  fnnue_move move;          /* 0 without a moves array */
+  uint8_t kind;             /* FNNUE_BEST_CP / FNNUE_BEST_MATE; FNNUE_BEST_NONE = unused slot (all zero) */
+  uint8_t reserved;         /* 0 */
+} fnnue_line;
+/* Group g owns the slots [line_off[g], line_off[g + 1]) of `lines` (line_off:
+ * ngroups + 1 entries, non-decreasing; the slot count is the group's k and may
+ * differ from group to group).  Slot j receives the j-th child in the order
+ * above; slots beyond the group's children are written all-zero; a group
+ * without a slot, or an empty group, writes nothing.  Slot 0 equals the
+ * group's fnnue_best field by field (psqt, positional, value, best == child,
+ * move, kind).  The other arrays, the clamping of offsets beyond npos and the
+ * launch (one kernel on `stream`, no atomics, no host synchronisation) are
+ * fnnue_best_children_device's.  Any net.  The device form never writes at or
+ * beyond lines_cap; the host form refuses line_off[ngroups] > lines_cap with
+ * FNNUE_E_CAPACITY. */
+int fnnue_topk_children_device(fnnue_ctx *ctx, const int32_t *d_psqt, const int32_t *d_positional,
+                               const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                               size_t ngroups, size_t npos, const uint32_t *d_line_off, fnnue_line *d_lines,
+                               size_t lines_cap, void *stream);
+int fnnue_topk_children(fnnue_ctx *ctx, const int32_t *psqt, const int32_t *positional, const uint8_t *end,
+                        const fnnue_move *moves, const uint32_t *off, size_t ngroups, size_t npos,
+                        const uint32_t *line_off, fnnue_line *lines, size_t lines_cap);
+/* fnnue_search1[_device] plus, per ply, its k best children: ply p's k slots
+ * are lines[p * k .. p * k + k) (k in 1..FNNUE_MAX_CHILDREN, anything else
+ * FNNUE_E_ARG).  The fnnue_best records and the CHAIN offsets are those of
+ * fnnue_search1; same steps, same scratch, same capacity protocol, and
+ * lines_cap < plies * k is FNNUE_E_CAPACITY too (before any ply is expanded,
+ * *n_out set).  A chess net's context; FNNUE_E_ARCH otherwise. */
+int fnnue_search1_lines_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off,
+                               const uint32_t *d_moves_off, size_t ngames, uint32_t k, fnnue_best *d_out, size_t cap,
+                               uint32_t *d_off, size_t off_cap, fnnue_line *d_lines, size_t lines_cap, size_t *n_out,
+                               size_t *n_groups, void *stream);
+int fnnue_search1_lines(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                        const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best *out, size_t cap,
+                        uint32_t *off, size_t off_cap, fnnue_line *lines, size_t lines_cap, size_t *n_out,
+                        size_t *n_groups);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

@@ -83,8 +83,10 @@ typedef struct {
   const char *batch_id;            /* Work::id (BatchId), copied into logs / errors */
   int work;                        /* FNNUE_WORK_* */
   int multipv;                     /* Work::Analysis multipv: 0 = None; >= 1 = Some(k): the response is the
-                                      matrix form (AnalysisPart::Matrix, Work::matrix_wanted, api.rs:179-187)
-                                      with its one line (static eval has no second PV) at depth 0 */
+                                      matrix form (AnalysisPart::Matrix, Work::matrix_wanted, api.rs:179-187).
+                                      go() answers its one line (at depth 0 a static eval has no second PV);
+                                      on a depth-1 channel fnnue_backend_go_lines answers min(k, legal moves)
+                                      lines per ply */
   const char *position;            /* root FEN (X-FEN / Shredder castling accepted) */
   const char *variant;             /* "standard", "chess960", "fromPosition", NULL / "" = standard;
                                       "crazyhouse", "atomic" (variant nets); anything else: FNNUE_E_ARCH */
@@ -160,7 +162,13 @@ void fnnue_backend_free(fnnue_backend *b);
  * budget).  fnnue_backend_stats.positions counts plies plus children.
  * fnnue_backend_go_compact on a depth-1 channel gives the depth-1 score and
  * depth = 1 but no move and no node count: the 16-byte record has no room for
- * them (nodes reads as 1, as at depth 0). */
+ * them (nodes reads as 1, as at depth 0).
+ * MultiPV: every child of every ply is evaluated at depth 1, so a chess
+ * analysis batch with multipv = k >= 1 can be answered with its k best lines
+ * per ply.  go(), go_timeout() and go_compact() keep answering the best line
+ * alone (and launch nothing more than before); fnnue_backend_go_lines runs one
+ * more kernel per piece (fnnue_topk_children_device's) and returns the lines
+ * beside the responses. */
 int fnnue_backend_set_analysis_depth(fnnue_backend *b, int depth);
 
 /* Number of responses batch `a` expands to (IncomingBatch::from_acquired):
@@ -268,6 +276,56 @@ int fnnue_backend_last_stats(fnnue_backend *b, fnnue_backend_stats *out);
  * at most cap bytes including the NUL; *len = the full length (without NUL);
  * FNNUE_E_CAPACITY when it did not fit. */
 int fnnue_backend_analysis_json(const fnnue_position_response *r, size_t n, char *buf, size_t cap, size_t *len);
+
+/* ---- MultiPV at analysis depth 1 (ABI 3.5) ----
+ * One line of a response: the reference collects one score and one pv per
+ * MultiPV line into Matrix<Score> / Matrix<Vec<Uci>>, indexed [multipv - 1]
+ * [depth] ([ref] src/ipc.rs:68-93, src/stockfish.rs:350-445).  The sizes of
+ * fnnue_position_response and fnnue_best being ABI, the lines travel beside
+ * the responses. */
+typedef struct {
+  int64_t score;        /* centipawns or mate, as fnnue_position_response.score */
+  int32_t psqt;         /* this child's raw NNUE terms, negated */
+  int32_t positional;
+  char move[7];         /* UCI, NUL-terminated: the line's pv, one move */
+  uint8_t score_kind;   /* FNNUE_SCORE_* */
+} fnnue_pv_line;
+
+/* Lines a go_lines() over these batches may write: the sum over analysis
+ * batches with multipv >= 1 of (moves + 1) * min(multipv, FNNUE_MAX_CHILDREN)
+ * (skipped positions are not subtracted).  Host only; FNNUE_E_ARG on NULL. */
+int fnnue_backend_lines_bound(const fnnue_acquired *batches, size_t nbatches, size_t *n);
+
+/* fnnue_backend_go_timeout plus the lines: out, off and batch_rc are filled
+ * exactly as there (every response equals go()'s field by field but for
+ * time_ms / nps); response r's lines are lines[line_off[r] .. line_off[r + 1])
+ * (line_off: cap + 1 entries, off[nbatches] + 1 of them written).
+ * A response has lines iff the channel is at depth 1, it belongs to a chess
+ * analysis batch with multipv >= 1, it is not skipped and its ply has a legal
+ * move; it then has min(multipv, nodes) of them (as Stockfish answers a
+ * MultiPV beyond the legal moves), best first in fnnue_topk_children's order,
+ * line 0 being the response's own score, score_kind, best_move, psqt and
+ * positional.  Line j's score follows the depth-1 rule: Cp(value * 100 /
+ * normalize_to_pawn), Mate(1) for a mating child.  Every other response has
+ * none: a depth-0 channel, variant batches, move work, batches without
+ * multipv, skipped ids, plies without a legal move, failed batches.
+ * lines_cap < fnnue_backend_lines_bound(...) is FNNUE_E_CAPACITY before any
+ * work.  Budget and errors as fnnue_backend_go_timeout. */
+int fnnue_backend_go_lines(fnnue_backend *b, const fnnue_acquired *batches, size_t nbatches,
+                           fnnue_position_response *out, size_t cap, uint32_t *off, int32_t *batch_rc,
+                           fnnue_pv_line *lines, size_t lines_cap, uint32_t *line_off, uint32_t timeout_ms);
+
+/* fnnue_backend_analysis_json with the lines of a go_lines() (line_off: n + 1
+ * entries, relative to r[0]: response i's lines are lines[line_off[i] -
+ * line_off[0] ..)).  A response with L >= 1 lines at depth d is the matrix as
+ * Matrix::set builds it ([ref] src/ipc.rs:77-86), L rows of d nulls and the
+ * entry: {"pv":[[null,["e2e4"]],[null,["d2d4"]]],"score":[[null,{"cp":31}],
+ * [null,{"cp":28}]],"depth":1,...}.  A response without lines (or without
+ * `matrix`: lines are rows of the matrix form only) is serialised as
+ * fnnue_backend_analysis_json does it, so whenever every response has at most
+ * one line the two functions give the same bytes. */
+int fnnue_backend_analysis_json_lines(const fnnue_position_response *r, size_t n, const fnnue_pv_line *lines,
+                                      const uint32_t *line_off, char *buf, size_t cap, size_t *len);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@ shape: N random games (L ~ U[0, 160] plies) with every legal child, HD 1024.
 GPU box only.  One JSON line per measurement.
 
     python tools/search1_bench.py [--games 5000] [--hd 1024] [--runs 3] [--lib PATH] [--actor] [--base-only]
+                                  [--lines K[,K...]]
 
 The phases are timed with HIP events on the launch stream, after the workload
 ran untimed for 0.3 s:
@@ -11,13 +12,16 @@ ran untimed for 0.3 s:
   reduce    fnnue_best_children_device
   search1   fnnue_search1_device, the three in one call
   build     fnnue_build_batch_device(CHILDREN): the expansion without moves / flags
+  topk@K    fnnue_topk_children_device with K slots per group        (--lines)
+  lines@K   fnnue_search1_lines_device with k = K, all in one call   (--lines)
 `--lib` loads another build of the library (the parent commit's, which has
 only `build` and `eval`): the tool binds the few symbols it needs itself, so
 the two builds can alternate on one box (`--base-only` runs just those two on
 either build: the same work per iteration, for comparing the evaluation
 phase).  FNNUE_CHILDREN_IMPL=ply|record in
 the environment picks the children kernel (A/B).  `--actor` adds the engine
-actor at depth 0 and 1 for 1, 64 and 1024 lichess-shaped batches.
+actor at depth 0 and 1 for 1, 64 and 1024 lichess-shaped batches; with
+`--lines` also go_lines() at depth 1 with multipv = K for every K <= 5.
 """
 import argparse
 import ctypes as C
@@ -54,11 +58,17 @@ def bind(path):
         "fnnue_best_children_device": ([vp, vp, vp, vp, vp, vp, sz, sz, vp, vp], C.c_int),
         "fnnue_search1_device": ([vp, vp, vp, vp, sz, vp, sz, vp, sz, P(sz), P(sz), vp], C.c_int),
     }
+    lines = {
+        "fnnue_topk_children_device": ([vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, sz, vp], C.c_int),
+        "fnnue_search1_lines_device": ([vp, vp, vp, vp, sz, C.c_uint32, vp, sz, vp, sz, vp, sz, P(sz), P(sz), vp],
+                                       C.c_int),
+    }
     has_new = all(hasattr(lib, n) for n in new)
-    for name, (a, r) in {**sig, **(new if has_new else {})}.items():
+    has_lines = has_new and all(hasattr(lib, n) for n in lines)
+    for name, (a, r) in {**sig, **(new if has_new else {}), **(lines if has_lines else {})}.items():
         f = getattr(lib, name)
         f.argtypes, f.restype = a, r
-    return lib, has_new
+    return lib, has_new, has_lines
 
 
 def main():
@@ -71,9 +81,14 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--base-only", action="store_true", help="only build + eval, whatever the library has")
+    ap.add_argument("--lines", default="", help="slots per group, e.g. 1,3,5,218: also time the top-k kernel and "
+                                                "search1_lines (and go_lines with --actor)")
     a = ap.parse_args()
     import torch
-    lib, has_new = bind(a.lib)
+    lib, has_new, has_lines = bind(a.lib)
+    ks = [int(k) for k in a.lines.split(",") if k]
+    if ks and not has_lines:
+        raise SystemExit("--lines needs a library with fnnue_topk_children_device")
     label = a.label or ("tree" if has_new else "parent")
     impl = os.environ.get("FNNUE_CHILDREN_IMPL", "record")
 
@@ -143,10 +158,27 @@ def main():
         ok(lib.fnnue_search1_device(ctx, T, FO, MO, a.games, vp(d_best2.data_ptr()), G, vp(d_goff.data_ptr()),
                                     a.games + 1, C.byref(nrec), C.byref(ngrp), S))
 
+    kmax = max(ks, default=0)
+    d_lines = torch.zeros((max(G * kmax, 1), 20), dtype=torch.uint8, device=dev)
+    d_loff = {k: (torch.arange(G + 1, dtype=torch.int64, device=dev) * k).to(torch.int32) for k in ks}
+    torch.cuda.synchronize(dev)
+
+    def topk(k):
+        return lambda: ok(lib.fnnue_topk_children_device(ctx, PS, PP, EN, MV, OF, G, R, vp(d_loff[k].data_ptr()),
+                                                         vp(d_lines.data_ptr()), G * k, S))
+
+    def search1_lines(k):
+        return lambda: ok(lib.fnnue_search1_lines_device(ctx, T, FO, MO, a.games, k, vp(d_best2.data_ptr()), G,
+                                                         vp(d_goff.data_ptr()), a.games + 1, vp(d_lines.data_ptr()),
+                                                         G * k, C.byref(nrec), C.byref(ngrp), S))
+
     phases = [("build", build), ("eval", evaluate)]
     if has_new and not a.base_only:
         # eval right behind build, as on a parent build; children rewrites the same records
         phases = [("build", build), ("eval", evaluate), ("children", children), ("reduce", reduce), ("search1", search1)]
+        # the top-k kernel right behind the reduction's own arrays; search1 leaves the same d_best2 either way
+        phases[4:4] = [(f"topk@{k}", topk(k)) for k in ks]
+        phases += [(f"lines@{k}", search1_lines(k)) for k in ks]
 
     def once(timed):
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)] if timed else None
@@ -176,6 +208,12 @@ def main():
             lo, hi = (9 * R + 24 * G) / (HBM_READ_TBPS * 1e9), (11 * R + 24 * G) / (HBM_READ_TBPS * 1e9)
             line["byte_floor_ms"] = [round(lo, 4), round(hi, 4)]
             line["times_floor"] = round(ms[len(ms) // 2] / hi, 2)
+        if name.startswith("topk@"):  # the reduction's reads plus 20 B per written slot
+            k = int(name[5:])
+            lo, hi = ((9 * R + 8 * G + 20 * G * k) / (HBM_READ_TBPS * 1e9),
+                      (11 * R + 8 * G + 20 * G * k) / (HBM_READ_TBPS * 1e9))
+            line["byte_floor_ms"] = [round(lo, 4), round(hi, 4)]
+            line["times_floor"] = round(ms[len(ms) // 2] / hi, 2)
         print(json.dumps(line), flush=True)
     if has_new and not a.base_only:
         same = bool(torch.equal(d_best, d_best2))
@@ -185,11 +223,12 @@ def main():
         if not same:
             sys.exit(1)
     if a.actor and has_new:
-        actor_lines(a)
+        actor_lines(a, [k for k in ks if k <= 5])
 
 
-def actor_lines(a):
-    """The engine actor at depth 0 and 1 on the same lichess-shaped chess batches."""
+def actor_lines(a, multipvs=()):
+    """The engine actor at depth 0 and 1 on the same lichess-shaped chess batches; go_lines() at depth 1 with
+    every batch asking for multipv lines, for each of `multipvs`."""
     sys.path.insert(0, ROOT)
     import fishnet_amd as F
     from fishnet_amd import backend as B
@@ -198,20 +237,24 @@ def actor_lines(a):
     for nb in (1, 64, 1024):
         bodies = bench.lichess_batches(F, 11, nb, variants=0.0)
         plies = sum(len(b.moves.split()) + 1 for b in bodies)
-        for depth in (0, 1):
+        for depth, mpv in [(0, 0), (1, 0)] + [(1, m) for m in multipvs]:
             stub, actor = B.channel(net, 0, analysis_depth=depth)
+            for b in bodies:
+                b.multipv = mpv or None
+            go = stub.go_lines if mpv else stub.go
             t0 = time.perf_counter()
-            stub.go(bodies)
+            go(bodies)
             while time.perf_counter() - t0 < 0.3:
-                stub.go(bodies)
+                go(bodies)
             calls, stats = [], None
             for _ in range(a.runs):
-                stub.go(bodies)
+                go(bodies)
                 calls.append(stub.last_call_s * 1e3)
                 stats = B.last_stats(actor)
             calls.sort()
             med = calls[len(calls) // 2]
-            print(json.dumps({"actor_depth": depth, "batches": nb, "plies": plies, "positions": stats["positions"],
+            print(json.dumps({"actor_depth": depth, "go_lines_multipv": mpv, "batches": nb, "plies": plies,
+                              "line_bytes_per_ply": 20 * mpv, "positions": stats["positions"],
                               "ms_per_call": [round(x, 3) for x in calls], "median_ms": round(med, 3),
                               "plies_per_s": round(plies / (med * 1e-3)),
                               "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
