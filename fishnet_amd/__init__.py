@@ -4,7 +4,7 @@ from .nnue import (  # noqa: F401
     Evaluator, FnnueError, MultiEvaluator, Net, device_count, partition_groups, game_children, game_positions, perft, pos_from_fen,
     pack_games, random_game, random_playouts, random_vpositions, selftest_mfma, synthesize_net,
     synthesize_variant_net, vpos_from_fen, game_vpositions, game_vchildren, vperft, random_vgame, random_vgames,
-    game_end, END_NO_MOVES, END_CHECK, END_EXTINCT, END_VARIANT,
+    game_end, END_NO_MOVES, END_CHECK, END_EXTINCT, END_VARIANT, END_WON, BEST_LOST, vmove_uci,
     Best, BEST_DTYPE, BEST_NONE, BEST_CP, BEST_MATE, move_uci, Line, LINE_DTYPE, MAX_CHILDREN,
 )
 from ._native import (  # noqa: F401

@@ -29,7 +29,7 @@ VARIANT_CHESS, VARIANT_CRAZYHOUSE, VARIANT_ATOMIC = 0, 1, 2
 VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature set, their own rules
 POS_BYTES = 36
 BEST_BYTES = 24  # fnnue_best
-BEST_NONE, BEST_CP, BEST_MATE = 0, 1, 2
+BEST_NONE, BEST_CP, BEST_MATE, BEST_LOST = 0, 1, 2, 3
 LINE_BYTES = 20  # fnnue_line
 PV_LINE_BYTES = 24  # fnnue_pv_line
 MAX_CHILDREN = 218  # FNNUE_MAX_CHILDREN
@@ -157,8 +157,20 @@ SIGNATURES = {
                                    _i32),
     "fnnue_search1_lines": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
                              _P(_sz)], _i32),
+    "fnnue_vmove_uci": ([C.c_uint16, C.c_char_p], _i32),
+    "fnnue_build_vchildren_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _P(_sz), _P(_sz),
+                                      _vp], _i32),
+    "fnnue_build_vchildren": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _P(_sz),
+                               _P(_sz)], _i32),
+    "fnnue_vsearch1_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_vsearch1": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_vsearch1_lines_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                                     _P(_sz), _vp], _i32),
+    "fnnue_vsearch1_lines": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                              _P(_sz)], _i32),
     # include/fnnue_backend.h
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
+    "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_channel_nets": ([_vp, _i32, _vp, _P(_vp)], _i32),
     "fnnue_backend_channel_netv": ([_P(_vp), _sz, _i32, _vp, _P(_vp)], _i32),

@@ -177,7 +177,8 @@ class GpuEvalStub:
     def go_lines(self, bodies: Sequence[AcquireResponseBody], timeout_ms: int = 0,
                  lines_cap: int | None = None) -> list[list[PositionResponse] | PositionFailed]:
         """go() with the MultiPV lines (fnnue_backend_go_lines): on a depth-1
-        channel every non-skipped ply with a legal move of a chess analysis
+        channel (for variant batches: variant_analysis_depth 1) every
+        non-skipped ply with a legal move of an analysis
         batch with multipv = k carries `lines`, its min(k, nodes) best moves,
         best first; every other response has lines = None.  `lines_cap`: the
         line buffer's size (default: lines_bound(bodies))."""
@@ -278,6 +279,11 @@ class GpuEvalStub:
         default), 1 = a one-ply search per chess analysis ply (best move, pv)."""
         N.check(N.lib.fnnue_backend_set_analysis_depth(self._actor._h, int(depth)))
 
+    def set_variant_analysis_depth(self, depth: int) -> None:
+        """fnnue_backend_set_variant_analysis_depth: the same for crazyhouse, atomic, kingOfTheHill and
+        racingKings analysis batches (drops as "N@f3"); independent of set_analysis_depth."""
+        N.check(N.lib.fnnue_backend_set_variant_analysis_depth(self._actor._h, int(depth)))
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -305,13 +311,14 @@ class _Nets(C.Structure):
 
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
             atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0,
-            analysis_depth: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
+            analysis_depth: int = 0, variant_analysis_depth: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` theirs
     (fnnue_backend_channel_netv): each batch is evaluated by its variant's net.
     `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316).
-    `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth)."""
+    `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth); `variant_analysis_depth`: 0 or 1
+    for the variant nets' batches (GpuEvalStub.set_variant_analysis_depth)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None:
@@ -328,6 +335,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     stub = GpuEvalStub(actor)
     if analysis_depth:
         stub.set_analysis_depth(analysis_depth)
+    if variant_analysis_depth:
+        stub.set_variant_analysis_depth(variant_analysis_depth)
     return stub, actor
 
 

@@ -31,6 +31,12 @@
 // evaluation and the per-group reduction (stage_search); the piece brings back
 // one fnnue_best per ply, from which fill() writes best move, score, depth 1.
 //
+// The variant nets at depth 1 (fnnue_backend_set_variant_analysis_depth):
+// the same staging over the variant's boards (vbuilder.hip: VBoard, or DBoard
+// for kingofthehill / racingkings), children with variant move codes (drops)
+// and the variant's end flags, fnnue_eval_vgroups_device's STAR evaluation and
+// the same reduction, whose ranks know the variant flags.
+//
 // MultiPV (fnnue_backend_go_lines, a depth-1 channel): a piece with a batch
 // that asked for k lines carries every ply's slot offsets up (after ply_off)
 // and one more kernel, fnnue_topk_children_device's, ranks the children that
@@ -430,6 +436,8 @@ struct fnnue_backend {
   int device = 0;
   int32_t norm = kNormalizeToPawnSf151;
   int analysis_depth = 0;        // fnnue_backend_set_analysis_depth: 1 = a one-ply search per chess analysis ply
+  int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
+  bool depth1(int k) const { return (k == kVariantChess ? analysis_depth : variant_analysis_depth) == 1; }
   size_t piece_plies = 524288;  // FNNUE_BACKEND_PIECE_PLIES
   bool any_order = true;         // FNNUE_BACKEND_ANY_ORDER=0: wait for the nets' pieces in net order
   size_t tail_plies = 0;         // FNNUE_BACKEND_TAIL_PLIES: a net's last piece cut to about this many
@@ -632,7 +640,7 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.n = (uint32_t)plies;
   P.nk = P.kids ? W.nk : 0;
   const size_t ng = P.ng, n = P.n, nk = P.nk;
-  P.depth1 = analysis_depth == 1 && k == kVariantChess && ng;
+  P.depth1 = depth1(k) && ng;
   P.nslots = 0;
   if (j.lines && P.depth1)
     for (size_t i : P.games) P.nslots += (size_t)(j.off[i + 1] - j.off[i]) * line_slots(j.batches[i]);
@@ -658,7 +666,15 @@ int fnnue_backend::plan(Job& j, int k) {
   // At depth 1 a ply brings about 35 children (at most 218) into the net's
   // grow-only children buffers and the evaluator's workspace: pieces of a 32nd
   // of the plies keep a piece's records where a depth-0 piece's plies are.
-  const size_t cut_plies = analysis_depth == 1 && k == kVariantChess ? std::max<size_t>(1024, piece_plies / 32) : piece_plies;
+  // The variant nets' pieces are cut at an 8th: their children buffers are
+  // sized from the count each piece reads back, whatever a ply brings (a
+  // crazyhouse ply with full pockets several hundred), and every piece costs
+  // that read-back, so fewer and larger pieces measured faster (DESIGN.md
+  // §4.16: 1024 crazyhouse batches in 33.1 / 17.4 / 13.4 ms at a 128th / 32nd
+  // / 8th).
+  const size_t cut_plies = !depth1(k)           ? piece_plies
+                           : k == kVariantChess ? std::max<size_t>(1024, piece_plies / 32)
+                                                : std::max<size_t>(256, piece_plies / 8);
   for (size_t i : W.games) {
     const size_t t = (size_t)flen[i] + 1 + mlen[i];
     if (W.pieces.empty() || acc >= cut_plies || text + t > kMaxPieceText) {
@@ -701,7 +717,7 @@ int fnnue_backend::plan(Job& j, int k) {
     P.dev0 = dev;
     P.pos0 = pos;
     P.st0 = st;
-    if (P.depth1) st = align256(st + (size_t)P.n * sizeof(DBoard));
+    if (P.depth1) st = align256(st + (size_t)P.n * (k == kVariantChess ? sizeof(DBoard) : vstate_bytes(k)));
     up = align256(up + P.o_res + 16);
     down = align256(down + P.end - P.o_res);
     dev = align256(dev + P.end);
@@ -763,7 +779,14 @@ int fnnue_backend::stage_up(Job& j, int k, size_t pi) {
   char* dimg = W.dev.at<char>(P.dev0);
   hipStream_t us = ctx[k]->stream;
   HIP_TRY(hipMemcpyAsync(dimg, img, P.o_res + 16, hipMemcpyHostToDevice, us), "H2D(batch image)");
-  if (P.depth1)
+  if (P.depth1 && k != kVariantChess)
+    HIP_TRY(replay_vgames_device(k, dimg, reinterpret_cast<uint32_t*>(dimg + P.o_fen),
+                                 reinterpret_cast<uint32_t*>(dimg + P.o_mv), reinterpret_cast<uint32_t*>(dimg + P.o_ply),
+                                 P.ng, W.pos.at<fnnue_vpos>(P.pos0), W.states.at<char>(P.st0),
+                                 reinterpret_cast<uint8_t*>(dimg + P.o_fin), reinterpret_cast<uint32_t*>(dimg + P.o_res),
+                                 us),
+            "batch replay launch");
+  else if (P.depth1)
     HIP_TRY(replay_chess_states_device(dimg, reinterpret_cast<uint32_t*>(dimg + P.o_fen),
                                        reinterpret_cast<uint32_t*>(dimg + P.o_mv),
                                        reinterpret_cast<uint32_t*>(dimg + P.o_ply), P.ng, W.pos.at<fnnue_pos>(P.pos0),
@@ -826,7 +849,8 @@ int fnnue_backend::stage_eval(int k, size_t pi) {
   return FNNUE_OK;
 }
 
-// Analysis at depth 1, a chess piece: behind its replay the children of every
+// Analysis at depth 1, a piece of a net at depth 1 (chess, or a variant net
+// over its own boards and rules): behind its replay the children of every
 // ply are counted and the count read back (the builder's sizing read-back,
 // with the replay's error word: a piece with a rejected game skips the search
 // and goes to recover() as it is); then the children with their moves and end
@@ -840,12 +864,16 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   hipStream_t s = c->stream;
   char* dimg = W.dev.at<char>(P.dev0);
   const uint32_t n = P.n;
-  const DBoard* states = W.states.at<DBoard>(P.st0);
+  const bool chess = k == kVariantChess;
+  const void* states = W.states.at<char>(P.st0);
   if (int rc = W.kid_cnt.reserve((size_t)(n + 1) * 4)) return rc;
   if (int rc = W.kid_off.reserve((size_t)(n + 1) * 4)) return rc;
   if (int rc = W.sizing.reserve(8)) return rc;
   uint32_t* coff = W.kid_off.at<uint32_t>(0);
-  HIP_TRY(children_count_device(states, n, W.kid_cnt.at<uint32_t>(0), coff, s, W.bscratch), "children count launch");
+  HIP_TRY(chess ? children_count_device(static_cast<const DBoard*>(states), n, W.kid_cnt.at<uint32_t>(0), coff, s,
+                                        W.bscratch)
+                : vchildren_count_device(k, states, n, W.kid_cnt.at<uint32_t>(0), coff, s, W.bscratch),
+          "children count launch");
   uint32_t* hs = W.sizing.at<uint32_t>(0);
   HIP_TRY(hipMemcpyAsync(hs, dimg + P.o_res, 4, hipMemcpyDeviceToHost, s), "D2H(builder error)");
   HIP_TRY(hipMemcpyAsync(hs + 1, coff + n, 4, hipMemcpyDeviceToHost, s), "D2H(children count)");
@@ -857,18 +885,25 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   if (rcw) return rcw;
   if (hs[0]) return FNNUE_OK;  // a rejected game: its boards are not those of a game
   const size_t total = hs[1];
-  if (int rc = W.kid_pos.reserve(total * sizeof(fnnue_pos))) return rc;
+  if (int rc = W.kid_pos.reserve(total * W.rec)) return rc;
   if (int rc = W.kid_moves.reserve(total * 2)) return rc;
   if (int rc = W.kid_end.reserve(total)) return rc;
   if (int rc = W.kid_ps.reserve(total * 4)) return rc;
   if (int rc = W.kid_po.reserve(total * 4)) return rc;
-  fnnue_pos* kp = W.kid_pos.at<fnnue_pos>(0);
+  void* kp = W.kid_pos.at<char>(0);
   uint16_t* km = W.kid_moves.at<uint16_t>(0);
   uint8_t* ke = W.kid_end.at<uint8_t>(0);
   int32_t* kps = W.kid_ps.at<int32_t>(0);
   int32_t* kpo = W.kid_po.at<int32_t>(0);
-  HIP_TRY(children_write_device(states, n, coff, (uint32_t)total, kp, km, ke, s), "children launch");
-  if (int rc = fnnue_eval_groups_device(c, kp, coff, n, total, FNNUE_GROUP_STAR, kps, kpo, s)) return rc;
+  HIP_TRY(chess ? children_write_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total,
+                                        static_cast<fnnue_pos*>(kp), km, ke, s)
+                : vchildren_write_device(k, states, n, coff, (uint32_t)total, static_cast<fnnue_vpos*>(kp), km, ke, s),
+          "children launch");
+  if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(kp), coff, n, total, FNNUE_GROUP_STAR,
+                                                kps, kpo, s)
+                     : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(kp), coff, n, total,
+                                                 FNNUE_GROUP_STAR, kps, kpo, s))
+    return rc;
   HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
                                s),
           "best_children launch");
@@ -1043,9 +1078,10 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           const fnnue_best& B = gb[q];
           const bool skipped = sk && skip[b + q];
           const bool none = B.kind == FNNUE_BEST_NONE;
-          const bool mate = B.kind == FNNUE_BEST_MATE;
-          const uint8_t kind = none ? end_kind : mate ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-          const int64_t score = none ? 0 : mate ? 1 : (int64_t)B.value * 100 / nrm;
+          // a mate in one, or (variants) every move loses at once: Mate(1) / Mate(-1), as move work
+          const bool mate = B.kind == FNNUE_BEST_MATE, lost = B.kind == FNNUE_BEST_LOST;
+          const uint8_t kind = none ? end_kind : mate || lost ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+          const int64_t score = none ? 0 : mate ? 1 : lost ? -1 : (int64_t)B.value * 100 / nrm;
           const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
           if (j.cout) {
             if (skipped)
@@ -1061,7 +1097,7 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
             continue;
           }
           put_response(r, response_head(q, 0, kind, none ? 0 : 1, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
-          if (!none) (void)fnnue_move_uci(B.move, r->best_move);
+          if (!none) (void)(k == kVariantChess ? fnnue_move_uci(B.move, r->best_move) : fnnue_vmove_uci(B.move, r->best_move));
           if (none || !kk) continue;
           // MultiPV: the first min(slots, nodes) lines of the ply, at the
           // batch's provisional place (close_lines() packs them afterwards)
@@ -1070,15 +1106,15 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           fnnue_pv_line* dst = j.lines + lbase[i] + (size_t)q * kk;
           for (uint32_t l = 0; l < nl; ++l) {
             const fnnue_line& L = src[l];
-            const bool lm = L.kind == FNNUE_BEST_MATE;
+            const bool lm = L.kind == FNNUE_BEST_MATE, ll = L.kind == FNNUE_BEST_LOST;
             char mv[8];
-            (void)fnnue_move_uci(L.move, mv);
+            (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
             fnnue_pv_line out{};
-            out.score = lm ? 1 : (int64_t)L.value * 100 / nrm;
+            out.score = lm ? 1 : ll ? -1 : (int64_t)L.value * 100 / nrm;
             out.psqt = L.psqt;
             out.positional = L.positional;
             std::memcpy(out.move, mv, 6);  // at most "e7e8q" and its NUL
-            out.score_kind = lm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+            out.score_kind = lm || ll ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
             dst[l] = out;
           }
           j.line_off[b + q + 1] = nl;  // a count for now
@@ -1720,6 +1756,14 @@ int fnnue_backend_set_analysis_depth(fnnue_backend* b, int depth) {
   if (depth != 0 && depth != 1) return fail(FNNUE_E_ARG, "analysis depth 0 or 1, not " + std::to_string(depth));
   std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
   b->analysis_depth = depth;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_variant_analysis_depth(fnnue_backend* b, int depth) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (depth != 0 && depth != 1) return fail(FNNUE_E_ARG, "variant analysis depth 0 or 1, not " + std::to_string(depth));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->variant_analysis_depth = depth;
   return FNNUE_OK;
 }
 

@@ -44,10 +44,13 @@ constexpr uint8_t kFinalNoMoves = 1, kFinalCheck = 2, kFinalExtinct = 4;
 // hill; racingkings: one king on rank 8): `score mate 0`.  (The racingkings
 // draw with both kings on rank 8 is kFinalNoMoves alone.)
 constexpr uint8_t kFinalVariant = 8;
-// Host only (move work, backend.cpp): the decided game is won by the side to
-// move (racingkings: black missed its catch-up move).
+// On a child only (move work, the variant one-ply search): the decided game is
+// won by its side to move (racingkings: black missed its catch-up move), so
+// the parent's mover lost by playing it.
 constexpr uint8_t kFinalWon = 0x40;
-static_assert(kFinalNoMoves == FNNUE_END_NO_MOVES && kFinalVariant == FNNUE_END_VARIANT, "fnnue.h FNNUE_END_*");
+static_assert(kFinalNoMoves == FNNUE_END_NO_MOVES && kFinalVariant == FNNUE_END_VARIANT &&
+                  kFinalWon == FNNUE_END_WON,
+              "fnnue.h FNNUE_END_*");
 // A game the replay rejected: kFinalFailed | its kBuildErr* code (replay_games_device).
 constexpr uint8_t kFinalFailed = 0x80;
 
@@ -141,9 +144,30 @@ hipError_t builder_exclusive_scan(const uint32_t* cnt, uint32_t* off, uint32_t n
 
 // The same expansion for Fairy-Stockfish variants (vbuilder.hip, vboard.h):
 // crazyhouse / atomic FENs and UCI moves (drops "P@e4"), fnnue_vpos records.
+// The one-ply search's form, as build_batch_device's: with d_moves / d_end
+// every record also gets its move (fnnue_vmove_uci's codes: drops included) and
+// its own kFinal* flags under the variant's rules, a child with kFinalWon when
+// its side to move has already won; with `own` the outputs live in the scratch.
+struct VChildrenBufs {
+  size_t max_groups = 0;
+  fnnue_vpos* pos = nullptr;
+  const uint32_t* off = nullptr;
+  uint16_t* moves = nullptr;
+  uint8_t* end = nullptr;
+  const uint32_t* ply_off = nullptr;
+};
 BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                 uint32_t ngames, bool children, fnnue_vpos* d_out, size_t cap, uint32_t* d_group_off,
-                                size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final = nullptr);
+                                size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final = nullptr,
+                                uint16_t* d_moves = nullptr, uint8_t* d_end = nullptr, VChildrenBufs* own = nullptr);
+// children_count_device / children_write_device over a variant's boards
+// (vstate_bytes(variant) each: DBoard for kingofthehill / racingkings,
+// vb::VBoard otherwise), one thread per record.  Stream-ordered, no sync.
+size_t vstate_bytes(int variant);
+hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off,
+                                  hipStream_t s, BuilderScratch& ws);
+hipError_t vchildren_write_device(int variant, const void* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                  fnnue_vpos* d_out, uint16_t* d_moves, uint8_t* d_end, hipStream_t s);
 
 // Every ply of every game with offsets the caller already knows (ply_off:
 // ngames + 1 entries, ply_off[g + 1] - ply_off[g] = 1 + the game's move

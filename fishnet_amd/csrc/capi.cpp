@@ -395,7 +395,7 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      fnnue_best / fnnue_best_children[_device], fnnue_search1[_device], fnnue_backend_set_analysis_depth
 // 3.5: MultiPV at depth 1: fnnue_line / fnnue_topk_children[_device], fnnue_search1_lines[_device],
 //      fnnue_pv_line / fnnue_backend_go_lines, fnnue_backend_lines_bound, fnnue_backend_analysis_json_lines
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 5u; }
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 6u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1340,6 +1340,34 @@ int stage_games(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_
   return FNNUE_OK;
 }
 
+// fnnue_build_vchildren_device, and with `own` the variant search's children
+// in the context's scratch.
+int build_vdevice(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                  const uint32_t* d_moves_off, size_t ngames, fnnue_vpos* d_out, size_t cap, uint32_t* d_off,
+                  size_t off_cap, uint16_t* d_moves, uint8_t* d_end, size_t* n_out, size_t* n_groups, void* stream,
+                  VChildrenBufs* own = nullptr) {
+  *n_out = *n_groups = 0;
+  if (!variant_known(variant) || variant == kVariantChess)
+    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (ngames == 0) return FNNUE_OK;
+  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const BuildResult R = build_vbatch_device(variant, d_text, d_fen_off, d_moves_off, (uint32_t)ngames, true,
+                                            d_out, cap, d_off, off_cap, s, ctx->bscratch, nullptr, d_moves, d_end,
+                                            own);
+  if (R.hip != hipSuccess) return hip_fail(R.hip, "device variant batch builder");
+  *n_out = R.n_out;
+  *n_groups = R.n_groups;
+  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable variant FEN in game " + std::to_string(R.err_game));
+  if (R.err_code == kBuildErrMove)
+    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
+                                  std::to_string(R.err_game));
+  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  return FNNUE_OK;
+}
+
 // A device buffer for the length of one host-buffer call.
 struct TempDev {
   void* p = nullptr;
@@ -1529,14 +1557,27 @@ int fnnue_topk_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* posi
 
 namespace {
 
+// The net a one-ply search of `variant` needs: fnnue_search1* a chess net,
+// fnnue_vsearch1* one whose feature set and game-over records are the
+// variant's (its own net; the atomic net also for kingofthehill, racingkings).
+int search1_arch(const fnnue_ctx* ctx, int variant) {
+  if (variant == kVariantChess)
+    return ctx->variant == kVariantChess ? (int)FNNUE_OK : fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
+  if (!variant_known(variant)) return fail(FNNUE_E_ARCH, "unknown variant " + std::to_string(variant));
+  if (ctx->variant == variant || (ctx->variant == kVariantAtomic && variant_board_only(variant))) return FNNUE_OK;
+  return fail(FNNUE_E_ARCH, std::string("the context's net (") + variant_name(ctx->variant) + ") does not evaluate " +
+                                variant_name(variant));
+}
+
 // fnnue_search1_device, and with k >= 1 fnnue_search1_lines_device: ply p's k
 // best children at d_lines[p * k ..] from the same scratch, behind the reduction.
-int search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                   size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
-                   fnnue_line* d_lines, size_t lines_cap, size_t* n_out, size_t* n_groups, void* stream) {
+int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                   const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
+                   uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
+                   size_t* n_groups, void* stream) {
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
+  if (int rc = search1_arch(ctx, variant)) return rc;
   if (ngames == 0) return FNNUE_OK;
   DeviceGuard g(ctx->device);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
@@ -1545,11 +1586,17 @@ int search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   if (rc) return rc;
   WorkspaceUse use{ctx, s};
   ChildrenBufs kids;
+  VChildrenBufs vkids;
   kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
   if (k) kids.max_groups = d_lines ? std::min(kids.max_groups, lines_cap / k) : 0;
+  vkids.max_groups = kids.max_groups;
   size_t nrec = 0, nply = 0;
-  rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
-                    nullptr, nullptr, &nrec, &nply, s, &kids);
+  if (variant == kVariantChess)
+    rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
+                      nullptr, nullptr, &nrec, &nply, s, &kids);
+  else
+    rc = build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
+                       &nrec, &nply, s, &vkids);
   *n_out = nply;
   *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
   if (rc) return rc;
@@ -1557,7 +1604,16 @@ int search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPsqt, nrec * 4, (void**)&ps), "device allocation (search scratch)");
   HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPositional, nrec * 4, (void**)&po),
           "device allocation (search scratch)");
-  if ((rc = fnnue_eval_groups_device(ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s))) return rc;
+  if (variant == kVariantChess) {
+    rc = fnnue_eval_groups_device(ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s);
+  } else {
+    rc = fnnue_eval_vgroups_device(ctx, vkids.pos, vkids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s);
+    kids.off = vkids.off;
+    kids.moves = vkids.moves;
+    kids.end = vkids.end;
+    kids.ply_off = vkids.ply_off;
+  }
+  if (rc) return rc;
   HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
           "best_children launch");
   if (k)
@@ -1569,13 +1625,13 @@ int search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
 }
 
 // The host-buffer forms: staged through the ctx's stream.
-int search1_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
-                 size_t ngames, uint32_t k, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
-                 fnnue_line* lines, size_t lines_cap, size_t* n_out, size_t* n_groups) {
+int search1_host(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                 const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap, uint32_t* off,
+                 size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out, size_t* n_groups) {
   if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
     return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
+  if (int rc = search1_arch(ctx, variant)) return rc;
   if (ngames == 0) return FNNUE_OK;
   DeviceGuard g(ctx->device);
   char* d_text = nullptr;
@@ -1590,7 +1646,7 @@ int search1_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32
   if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
   char* d = static_cast<char*>(buf.p);
   hipStream_t s = ctx->stream;
-  rc = search1_device(ctx, d_text, d_fo, d_mo, ngames, k, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
+  rc = search1_device(ctx, variant, d_text, d_fo, d_mo, ngames, k, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
                       room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
                       room && k ? reinterpret_cast<fnnue_line*>(d + o_lines) : nullptr, room ? nl : 0, n_out,
                       n_groups, s);
@@ -1609,7 +1665,7 @@ extern "C" {
 int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
                          size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
                          size_t* n_groups, void* stream) {
-  return search1_device(ctx, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr, 0, n_out,
+  return search1_device(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr, 0, n_out,
                         n_groups, stream);
 }
 
@@ -1618,7 +1674,7 @@ int fnnue_search1_lines_device(fnnue_ctx* ctx, const char* d_text, const uint32_
                                uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
                                size_t* n_groups, void* stream) {
   if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_device(ctx, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines, lines_cap,
+  return search1_device(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines, lines_cap,
                         n_out, n_groups, stream);
 }
 
@@ -1627,15 +1683,112 @@ int fnnue_search1_lines(fnnue_ctx* ctx, const char* text, size_t text_len, const
                         uint32_t* off, size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out,
                         size_t* n_groups) {
   if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_host(ctx, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines, lines_cap,
+  return search1_host(ctx, kVariantChess, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines, lines_cap,
                       n_out, n_groups);
 }
 
 int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
                   const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
                   size_t* n_out, size_t* n_groups) {
-  return search1_host(ctx, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0, n_out,
+  return search1_host(ctx, kVariantChess, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0, n_out,
                       n_groups);
+}
+
+int fnnue_vmove_uci(fnnue_move m, char out[8]) {
+  if (!out) return fail(FNNUE_E_ARG, "null argument");
+  out[0] = 0;
+  const int from = m & 63, to = (m >> 6) & 63, promo = (m >> 12) & 7;
+  if (m == 0) return FNNUE_OK;
+  if ((m >> 15) || promo > 5 || (from == to ? promo == 0 : promo == 1))
+    return fail(FNNUE_E_ARG, "not a variant move code: " + std::to_string(m));
+  if (from == to) {  // a drop
+    out[0] = " PNBRQ"[promo];
+    out[1] = '@';
+    out[2] = (char)('a' + (to & 7));
+    out[3] = (char)('1' + (to >> 3));
+    out[4] = 0;
+    return FNNUE_OK;
+  }
+  return fnnue_move_uci(m, out);
+}
+
+int fnnue_build_vchildren_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                                 const uint32_t* d_moves_off, size_t ngames, fnnue_vpos* d_out, size_t cap,
+                                 uint32_t* d_off, size_t off_cap, fnnue_move* d_moves, uint8_t* d_end, size_t* n_out,
+                                 size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  if (d_out && (!d_moves || !d_end)) return fail(FNNUE_E_ARG, "null moves / end buffer");
+  return build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, d_moves,
+                       d_end, n_out, n_groups, stream);
+}
+
+int fnnue_build_vchildren(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                          const uint32_t* moves_off, size_t ngames, fnnue_vpos* out, size_t cap, uint32_t* off,
+                          size_t off_cap, fnnue_move* moves, uint8_t* end, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (!variant_net_id(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  rc = fnnue_build_vchildren_device(ctx, variant, d_text, d_fo, d_mo, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
+                                    n_out, n_groups, s);
+  if (rc != FNNUE_E_CAPACITY) return rc;  // sizing pass: always "too small" with no outputs
+  if (!out || !off || !moves || !end || cap < *n_out || off_cap < *n_groups + 1)
+    return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  const size_t nrec = *n_out, ng = *n_groups;
+  TempDev buf;  // [records | off | moves | end]
+  const size_t o_off = nrec * sizeof(fnnue_vpos), o_mv = o_off + (ng + 1) * 4, o_end = o_mv + nrec * 2;
+  if ((rc = buf.get(o_end + nrec))) return rc;
+  char* d = static_cast<char*>(buf.p);
+  rc = fnnue_build_vchildren_device(ctx, variant, d_text, d_fo, d_mo, ngames, reinterpret_cast<fnnue_vpos*>(d), nrec,
+                                    reinterpret_cast<uint32_t*>(d + o_off), ng + 1,
+                                    reinterpret_cast<fnnue_move*>(d + o_mv), reinterpret_cast<uint8_t*>(d + o_end),
+                                    n_out, n_groups, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_vpos), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(off, d + o_off, (*n_groups + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(moves, d + o_mv, *n_out * 2, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(end, d + o_end, *n_out, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
+int fnnue_vsearch1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                          const uint32_t* d_moves_off, size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off,
+                          size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  return search1_device(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr,
+                        0, n_out, n_groups, stream);
+}
+
+int fnnue_vsearch1_lines_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                                const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
+                                uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
+                                size_t* n_groups, void* stream) {
+  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
+  return search1_device(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines,
+                        lines_cap, n_out, n_groups, stream);
+}
+
+int fnnue_vsearch1_lines(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                         const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap,
+                         uint32_t* off, size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out,
+                         size_t* n_groups) {
+  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
+  return search1_host(ctx, variant, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines,
+                      lines_cap, n_out, n_groups);
+}
+
+int fnnue_vsearch1(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                   const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off,
+                   size_t off_cap, size_t* n_out, size_t* n_groups) {
+  return search1_host(ctx, variant, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0,
+                      n_out, n_groups);
 }
 
 int fnnue_build_batch(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,

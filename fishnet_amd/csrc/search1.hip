@@ -5,7 +5,8 @@
 // A group averages about 35 children and has at most 219 records, so a wave
 // per group would idle half its lanes: 32 lanes (half a wave) share a group.
 // Each lane folds the children lane, lane + 32, ... into one 64-bit key
-//   rank (2 mate in one, 1 everything else) << 62 | (value + 2^29) << 32 | ~index
+//   rank (2 mate in one, 1 everything else, 0 a child the mover has lost by
+//   playing: FNNUE_END_WON) << 62 | (value + 2^29) << 32 | ~index
 // (|value| <= 2^28: the sum of two int32 over 16), so that the largest key is
 // the first maximum whatever lane saw it; five xor-shuffles inside the half
 // wave leave it in every lane, and lanes 0-5 store one dword each of the
@@ -23,6 +24,31 @@ namespace {
 constexpr uint32_t kGroupLanes = 32, kBlock = 256;
 static_assert(sizeof(fnnue_best) == 24, "fnnue_best is six dwords");
 
+// A child's key by the rule of the backend's move work (backend.cpp
+// fill_roots): lost at once (rank 0, worth 0), no legal move and decided
+// (check, exploded king, the variant's rule: rank 2), no legal move alone
+// (worth 0), anything else its negated evaluation.  Never 0 (~index).
+__device__ __forceinline__ unsigned long long child_key(const int32_t* __restrict__ psqt,
+                                                        const int32_t* __restrict__ positional,
+                                                        const uint8_t* __restrict__ end, uint32_t o, uint32_t c) {
+  const uint32_t x = o + c;
+  const uint32_t f = end[x];
+  uint32_t rank = 1;
+  int32_t v = 0;
+  if (f & kFinalWon) {
+    rank = 0;
+  } else if (f & kFinalNoMoves) {
+    rank = (f & (kFinalCheck | kFinalExtinct | kFinalVariant)) ? 2u : 1u;  // mate in one / stalemate (worth 0)
+  } else {
+    v = (int32_t)-(((long long)psqt[x] + (long long)positional[x]) / 16);
+  }
+  return (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+}
+__device__ __forceinline__ uint32_t key_kind(unsigned long long key) {
+  const uint32_t rank = (uint32_t)(key >> 62);
+  return rank == 2 ? FNNUE_BEST_MATE : rank == 0 ? FNNUE_BEST_LOST : FNNUE_BEST_CP;
+}
+
 __global__ __launch_bounds__(kBlock) void best_children_kernel(
     const int32_t* __restrict__ psqt, const int32_t* __restrict__ positional, const uint8_t* __restrict__ end,
     const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off, uint32_t ngroups, uint32_t npos,
@@ -36,19 +62,9 @@ __global__ __launch_bounds__(kBlock) void best_children_kernel(
     o = min(off[g], e);
   }
   const uint32_t nrec = e - o;
-  unsigned long long key = 0;  // 0: no child (every child's rank is >= 1)
+  unsigned long long key = 0;  // 0: no child (a child's key is never 0: ~index)
   for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
-    const uint32_t x = o + c;
-    const uint32_t f = end[x];
-    uint32_t rank = 1;
-    int32_t v = 0;
-    if (f & kFinalNoMoves) {
-      rank = (f & kFinalCheck) ? 2u : 1u;  // mate in one / stalemate (worth 0)
-    } else {
-      v = (int32_t)-(((long long)psqt[x] + (long long)positional[x]) / 16);
-    }
-    const unsigned long long k = (unsigned long long)rank << 62 |
-                                 (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+    const unsigned long long k = child_key(psqt, positional, end, o, c);
     key = k > key ? k : key;
   }
 #pragma unroll
@@ -57,11 +73,10 @@ __global__ __launch_bounds__(kBlock) void best_children_kernel(
     key = other > key ? other : key;
   }
   const uint32_t best = key ? 0xFFFFFFFFu - (uint32_t)key : 0u;
-  const uint32_t rank = (uint32_t)(key >> 62);
   const int32_t value = (int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29);
   uint32_t w = 0;
   if (nrec) {  // an empty group: all zero
-    const uint32_t kind = !best ? FNNUE_BEST_NONE : rank == 2 ? FNNUE_BEST_MATE : FNNUE_BEST_CP;
+    const uint32_t kind = !best ? FNNUE_BEST_NONE : key_kind(key);
     switch (lane) {
       case 0: w = best ? 0u - (uint32_t)psqt[o + best] : 0u; break;        // negated, wrapping
       case 1: w = best ? 0u - (uint32_t)positional[o + best] : 0u; break;
@@ -91,26 +106,11 @@ constexpr uint32_t kTopkRegs = 8, kTopkFast = kGroupLanes * kTopkRegs, kTopkGrou
 static_assert(sizeof(fnnue_line) == 20, "fnnue_line is five dwords");
 static_assert(kTopkFast >= FNNUE_MAX_CHILDREN, "every chess ply takes the fast path");
 
-__device__ __forceinline__ unsigned long long child_key(const int32_t* __restrict__ psqt,
-                                                        const int32_t* __restrict__ positional,
-                                                        const uint8_t* __restrict__ end, uint32_t o, uint32_t c) {
-  const uint32_t x = o + c;
-  const uint32_t f = end[x];
-  uint32_t rank = 1;
-  int32_t v = 0;
-  if (f & kFinalNoMoves) {
-    rank = (f & kFinalCheck) ? 2u : 1u;
-  } else {
-    v = (int32_t)-(((long long)psqt[x] + (long long)positional[x]) / 16);
-  }
-  return (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
-}
-
 __device__ __forceinline__ void write_line(uint32_t* __restrict__ lines, uint64_t slot, unsigned long long key,
                                            const int32_t* __restrict__ psqt, const int32_t* __restrict__ positional,
                                            const uint16_t* __restrict__ moves, uint32_t o) {
   const uint32_t c = 0xFFFFFFFFu - (uint32_t)key;
-  const uint32_t kind = (uint32_t)(key >> 62) == 2 ? FNNUE_BEST_MATE : FNNUE_BEST_CP;
+  const uint32_t kind = key_kind(key);
   const int32_t value = (int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29);
   uint32_t* w = lines + slot * 5;
   w[0] = 0u - (uint32_t)psqt[o + c];  // negated, wrapping

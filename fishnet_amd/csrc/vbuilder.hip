@@ -9,7 +9,9 @@
 // pockets, explosions) with the rules of vboard.h — the same source the host replay
 // (fnnue_game_vpositions) runs, which the tests hold it to record for record —
 // writing one fnnue_vpos per ply; CHILDREN adds one thread per ply for its
-// legal children (drops included).
+// legal children (drops included), and the one-ply search's form of it
+// (fnnue_build_vchildren) one thread per record for the children with their
+// move codes and game-end flags.
 //
 // kingofthehill and racingkings play chess moves (no drops, no explosions), so
 // they replay on the chess rule set's lane-parallel chain (chess_rules.h
@@ -460,7 +462,156 @@ __global__ void vwrite_children_kernel(const vb::VBoard* __restrict__ states, ui
   });
 }
 
+// ---- the one-ply search's children: records, moves, end flags ----
+// As builder.hip's write_children_record_kernel: one thread per record, each
+// regenerating its ply's moves up to its own (a crazyhouse ply with full
+// pockets has several hundred children: one thread per ply would leave a piece
+// of a few thousand plies on a handful of waves).
+
+// fnnue_vmove_uci's code of m on b (vb::vuci): a drop is from == to with the
+// piece type in the promo field; castling carries the king's two-square step
+// unless the game needs Chess960 notation.
+__device__ __forceinline__ uint16_t vmove_code(const vb::VBoard& b, const vb::VMove& m) {
+  if (m.kind == 2) return (uint16_t)((uint32_t)m.to | (uint32_t)m.to << 6 | (uint32_t)m.piece << 12);
+  int to = m.to;
+  if (m.kind == 1 && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
+  return (uint16_t)((uint32_t)m.from | (uint32_t)to << 6 | (uint32_t)(m.kind == 0 ? m.piece : 0) << 12);
+}
+__device__ __forceinline__ uint16_t pmove_code(const DBoard& b, const DMove& m) {
+  int to = m.to;
+  if (m.castle && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
+  return (uint16_t)((uint32_t)m.from | (uint32_t)to << 6 | (uint32_t)m.promo << 12);
+}
+
+// Record r's ply: off[lo] <= r < off[lo + 1] (off[0] = 0, off[n] = total > r).
+__device__ __forceinline__ uint32_t ply_of_record(const uint32_t* __restrict__ off, uint32_t n, uint32_t r) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(64) void vwrite_children_record_kernel(
+    const vb::VBoard* __restrict__ states, uint32_t n, const uint32_t* __restrict__ off, uint32_t total,
+    fnnue_vpos* __restrict__ out, uint16_t* __restrict__ moves, uint8_t* __restrict__ end) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const uint32_t lo = ply_of_record(off, n, r);
+  const uint32_t o0 = off[lo], j = r - o0;
+  const vb::VBoard b = states[lo];
+  vb::VBoard c = b;
+  uint16_t mv = 0;
+  if (j) {
+    uint32_t k = 0;
+    vb::for_each_legal(b, [&](const vb::VMove& m) -> bool {
+      if (++k < j) return true;
+      vb::do_move(c, m);
+      mv = vmove_code(b, m);
+      return false;
+    });
+  }
+  out[r] = vb::pack(c);
+  moves[r] = mv;
+  uint8_t f;
+  if (j) {
+    // the child's own flags: a second ply of generation that stops at the first
+    // legal move; a child its side to move has already won loses for the mover
+    const vb::VBoard d = c;  // a copy for the by-reference generator
+    f = vb::final_state(d);
+    if (vb::variant_over(d) && vb::variant_won(d)) f |= kFinalWon;
+  } else {
+    f = vb::end_flags(b, off[lo + 1] - o0 > 1);
+  }
+  end[r] = f;
+}
+
+template <int V>
+__global__ __launch_bounds__(64) void pwrite_children_record_kernel(
+    const DBoard* __restrict__ states, uint32_t n, const uint32_t* __restrict__ off, uint32_t total,
+    fnnue_vpos* __restrict__ out, uint16_t* __restrict__ moves, uint8_t* __restrict__ end) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const uint32_t lo = ply_of_record(off, n, r);
+  const uint32_t o0 = off[lo], j = r - o0;
+  const DBoard b = states[lo];
+  DBoard c = b;
+  uint16_t mv = 0;
+  if (j) {
+    uint32_t k = 0;
+    for_each_legal<V>(b, [&](const DMove& m) -> bool {
+      if (++k < j) return true;
+      do_move(c, m);
+      mv = pmove_code(b, m);
+      return false;
+    });
+  }
+  out[r] = PlainRules<V>::pack(c);
+  moves[r] = mv;
+  uint8_t f;
+  if (j) {
+    bool any = false;
+    const DBoard d = c;  // a copy for the generator's reference
+    for_each_legal<V>(d, [&](const DMove&) -> bool {
+      any = true;
+      return false;
+    });
+    f = PlainRules<V>::end_flags(c, any);
+    if constexpr (V == kVariantRacingKings) {  // vb::variant_won
+      const uint64_t goal = c.bt[KING] & 0xFF00000000000000ull;
+      if (plain_over<V>(c) && (goal & colour(c, c.stm)) && !(goal & colour(c, c.stm ^ 1))) f |= kFinalWon;
+    }
+  } else {
+    f = PlainRules<V>::end_flags(b, off[lo + 1] - o0 > 1);
+  }
+  end[r] = f;
+}
+
 }  // namespace
+
+hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off,
+                                  hipStream_t s, BuilderScratch& ws) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(d_cnt + n, 0, 4, s)) != hipSuccess) return e;
+  if (n) {
+    const uint32_t bs = 64;
+    const dim3 grid((n + bs - 1) / bs);
+    if (variant == kVariantKingOfTheHill)
+      hipLaunchKernelGGL(pcount_children_kernel<kVariantKingOfTheHill>, grid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(d_states), n, d_cnt);
+    else if (variant == kVariantRacingKings)
+      hipLaunchKernelGGL(pcount_children_kernel<kVariantRacingKings>, grid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(d_states), n, d_cnt);
+    else
+      hipLaunchKernelGGL(vcount_children_kernel, grid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(d_states), n,
+                         d_cnt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return builder_exclusive_scan(d_cnt, d_off, n, s, ws);
+}
+
+hipError_t vchildren_write_device(int variant, const void* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                  fnnue_vpos* d_out, uint16_t* d_moves, uint8_t* d_end, hipStream_t s) {
+  if (n == 0 || total == 0) return hipSuccess;
+  const uint32_t bs = 64;
+  const dim3 grid((total + bs - 1) / bs);
+  if (variant == kVariantKingOfTheHill)
+    hipLaunchKernelGGL(pwrite_children_record_kernel<kVariantKingOfTheHill>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, d_out, d_moves, d_end);
+  else if (variant == kVariantRacingKings)
+    hipLaunchKernelGGL(pwrite_children_record_kernel<kVariantRacingKings>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, d_out, d_moves, d_end);
+  else
+    hipLaunchKernelGGL(vwrite_children_record_kernel, grid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(d_states),
+                       n, d_off, total, d_out, d_moves, d_end);
+  return hipGetLastError();
+}
+
+size_t vstate_bytes(int variant) {
+  return variant == kVariantKingOfTheHill || variant == kVariantRacingKings ? sizeof(DBoard) : sizeof(vb::VBoard);
+}
 
 hipError_t replay_vgames_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                 const uint32_t* d_ply_off, uint32_t ngames, fnnue_vpos* d_out, void* d_states,
@@ -480,7 +631,8 @@ hipError_t replay_vgames_device(int variant, const char* d_text, const uint32_t*
 
 BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                 uint32_t ngames, bool children, fnnue_vpos* d_out, size_t cap, uint32_t* d_group_off,
-                                size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final) {
+                                size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final, uint16_t* d_moves,
+                                uint8_t* d_end, VChildrenBufs* own) {
   BuildResult R;
   auto fail = [&](hipError_t e) {
     R.hip = e;
@@ -519,6 +671,11 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
         hipSuccess)
       return fail(e);
   } else {
+    if (own && total_plies > own->max_groups) {  // the search's capacity: one record per ply
+      R.n_groups = total_plies;
+      R.capacity = true;
+      return R;
+    }
     if ((e = ws.get(W::kStates, (size_t)total_plies * state_bytes, &states)) != hipSuccess)
       return fail(e);
     if ((e = ws.get(W::kCnt, (size_t)(total_plies + 1) * 4, (void**)&cnt)) != hipSuccess) return fail(e);
@@ -535,41 +692,47 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
       R.err_ply = herr[2];
       return R;
     }
-    if ((e = hipMemsetAsync(cnt + total_plies, 0, 4, s)) != hipSuccess) return fail(e);
-    const dim3 cgrid((total_plies + bs - 1) / bs);
-    if (variant == kVariantKingOfTheHill)
-      hipLaunchKernelGGL(pcount_children_kernel<kVariantKingOfTheHill>, cgrid, dim3(bs), 0, s,
-                         static_cast<const DBoard*>(states), total_plies, cnt);
-    else if (variant == kVariantRacingKings)
-      hipLaunchKernelGGL(pcount_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
-                         static_cast<const DBoard*>(states), total_plies, cnt);
-    else
-      hipLaunchKernelGGL(vcount_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),
-                         total_plies, cnt);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    if ((e = builder_exclusive_scan(cnt, coff, total_plies, s, ws)) != hipSuccess) return fail(e);
+    if ((e = vchildren_count_device(variant, states, total_plies, cnt, coff, s, ws)) != hipSuccess) return fail(e);
     uint32_t total = 0;
     if ((e = hipMemcpyAsync(&total, coff + total_plies, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
     R.n_out = total;
     R.n_groups = total_plies;
-    if (cap < total || off_cap < (size_t)total_plies + 1 || !d_out || !d_group_off) {
-      R.capacity = true;
-      return R;
+    if (own) {
+      if ((e = ws.get(W::kKids, (size_t)total * sizeof(fnnue_vpos), (void**)&own->pos)) != hipSuccess) return fail(e);
+      if ((e = ws.get(W::kKidMoves, (size_t)total * 2, (void**)&own->moves)) != hipSuccess) return fail(e);
+      if ((e = ws.get(W::kKidEnd, (size_t)total, (void**)&own->end)) != hipSuccess) return fail(e);
+      own->off = coff;
+      own->ply_off = ply_off;
+      if ((e = vchildren_write_device(variant, states, total_plies, coff, total, own->pos, own->moves, own->end,
+                                      s)) != hipSuccess)
+        return fail(e);
+    } else {
+      if (cap < total || off_cap < (size_t)total_plies + 1 || !d_out || !d_group_off) {
+        R.capacity = true;
+        return R;
+      }
+      const dim3 cgrid((total_plies + bs - 1) / bs);
+      if (d_moves && d_end) {
+        if ((e = vchildren_write_device(variant, states, total_plies, coff, total, d_out, d_moves, d_end, s)) !=
+            hipSuccess)
+          return fail(e);
+      } else {
+        if (variant == kVariantKingOfTheHill)
+          hipLaunchKernelGGL(pwrite_children_kernel<kVariantKingOfTheHill>, cgrid, dim3(bs), 0, s,
+                             static_cast<const DBoard*>(states), total_plies, coff, d_out);
+        else if (variant == kVariantRacingKings)
+          hipLaunchKernelGGL(pwrite_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
+                             static_cast<const DBoard*>(states), total_plies, coff, d_out);
+        else
+          hipLaunchKernelGGL(vwrite_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),
+                             total_plies, coff, d_out);
+        if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+      }
+      if ((e = hipMemcpyAsync(d_group_off, coff, (size_t)(total_plies + 1) * 4, hipMemcpyDeviceToDevice, s)) !=
+          hipSuccess)
+        return fail(e);
     }
-    if (variant == kVariantKingOfTheHill)
-      hipLaunchKernelGGL(pwrite_children_kernel<kVariantKingOfTheHill>, cgrid, dim3(bs), 0, s,
-                         static_cast<const DBoard*>(states), total_plies, coff, d_out);
-    else if (variant == kVariantRacingKings)
-      hipLaunchKernelGGL(pwrite_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
-                         static_cast<const DBoard*>(states), total_plies, coff, d_out);
-    else
-      hipLaunchKernelGGL(vwrite_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),
-                         total_plies, coff, d_out);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(d_group_off, coff, (size_t)(total_plies + 1) * 4, hipMemcpyDeviceToDevice, s)) !=
-        hipSuccess)
-      return fail(e);
   }
   uint32_t herr[4];
   if ((e = hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);

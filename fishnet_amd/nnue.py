@@ -179,6 +179,7 @@ def game_vchildren(variant: int, fen: str, moves: str | list[str]) -> tuple[np.n
 
 END_NO_MOVES, END_CHECK, END_EXTINCT = 1, 2, 4
 END_VARIANT = 8  # the side to move has lost by the variant's own rule (kingofthehill, racingkings)
+END_WON = 0x40   # on a child of build_vchildren: its side to move has already won (the mover lost by playing it)
 
 
 def game_end(fen: str, moves: str | list[str] = "", variant: int = 0) -> int:
@@ -224,7 +225,7 @@ class Best(C.Structure):
 
 BEST_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("best", "<u4"),
                        ("move", "<u2"), ("kind", "u1"), ("end", "u1")])
-BEST_NONE, BEST_CP, BEST_MATE = N.BEST_NONE, N.BEST_CP, N.BEST_MATE
+BEST_NONE, BEST_CP, BEST_MATE, BEST_LOST = N.BEST_NONE, N.BEST_CP, N.BEST_MATE, N.BEST_LOST
 
 
 class Line(C.Structure):
@@ -242,6 +243,14 @@ def move_uci(code: int) -> str:
     """A fnnue_move code as UCI text ("" for 0); FnnueError FNNUE_E_ARG for a code that is no move."""
     buf = C.create_string_buffer(8)
     N.check(N.lib.fnnue_move_uci(int(code), buf))
+    return buf.value.decode()
+
+
+def vmove_uci(code: int) -> str:
+    """A variant move code as UCI text (fnnue_vmove_uci): as move_uci, and a drop (from == to, the piece
+    type in the promo field) as "N@f3"; FnnueError FNNUE_E_ARG for a code that is neither."""
+    buf = C.create_string_buffer(8)
+    N.check(N.lib.fnnue_vmove_uci(int(code), buf))
     return buf.value.decode()
 
 
@@ -522,6 +531,86 @@ class Evaluator:
                                                  C.c_void_p(d_moves_off), ngames, int(k), C.c_void_p(d_out), cap,
                                                  C.c_void_p(d_off), off_cap, C.c_void_p(d_lines), lines_cap,
                                                  C.byref(n), C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    # The one-ply search of the Fairy-Stockfish variants (ABI 3.6): a variant net's context.
+    def build_vchildren(self, variant: int, games):
+        """fnnue_build_vchildren: (records, STAR offsets, variant move codes, end flags) of every ply and its
+        children; a child's flags carry END_WON when its side to move has already won."""
+        text, fen_off, mv_off = pack_games(games)
+        n, g = C.c_size_t(), C.c_size_t()
+        rc = N.lib.fnnue_build_vchildren(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                         None, 0, None, 0, None, None, C.byref(n), C.byref(g))
+        if rc != -10:
+            N.check(rc)
+            return N.vpositions_array(0), np.zeros(1, dtype=np.uint32), np.zeros(0, np.uint16), np.zeros(0, np.uint8)
+        out = N.vpositions_array(n.value)
+        off = np.zeros(g.value + 1, dtype=np.uint32)
+        moves = np.zeros(n.value, dtype=np.uint16)
+        end = np.zeros(n.value, dtype=np.uint8)
+        N.check(N.lib.fnnue_build_vchildren(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off),
+                                            len(games), N.ptr(out), len(out), N.ptr(off), len(off), N.ptr(moves),
+                                            N.ptr(end), C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1], moves[: n.value], end[: n.value]
+
+    def build_vchildren_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int,
+                               d_out: int, cap: int, d_off: int, off_cap: int, d_moves: int, d_end: int,
+                               stream: int | None):
+        """fnnue_build_vchildren_device -> (rc, records, groups); rc is FNNUE_E_CAPACITY (-10) on a sizing call."""
+        n, g = C.c_size_t(), C.c_size_t()
+        rc = N.lib.fnnue_build_vchildren_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap,
+                                                C.c_void_p(d_off), off_cap, C.c_void_p(d_moves), C.c_void_p(d_end),
+                                                C.byref(n), C.byref(g), C.c_void_p(stream))
+        if rc != -10:
+            N.check(rc)
+        return rc, n.value, g.value
+
+    def vsearch1(self, variant: int, games, cap: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_vsearch1: a one-ply search per ply of variant games -> (BEST_DTYPE records, CHAIN offsets).
+        `cap` (default: the plies) sizes the record buffer."""
+        text, fen_off, mv_off = pack_games(games)
+        if cap is None:
+            cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch1(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                     N.ptr(out), cap, N.ptr(off), len(off), C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1]
+
+    def vsearch1_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int,
+                        cap: int, d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_vsearch1_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch1_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                            C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off),
+                                            off_cap, C.byref(n), C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    def vsearch1_lines(self, variant: int, games, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fnnue_vsearch1_lines: vsearch1 plus each ply's k best children ->
+        (BEST_DTYPE records, CHAIN offsets per game, LINE_DTYPE slots of shape (plies, k))."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        lines = np.zeros(max(cap * max(int(k), 0), 1), dtype=LINE_DTYPE)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch1_lines(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                           int(k), N.ptr(out), cap, N.ptr(off), len(off), N.ptr(lines), cap * int(k),
+                                           C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1], lines[: n.value * int(k)].reshape(n.value, int(k))
+
+    def vsearch1_lines_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, k: int,
+                              d_out: int, cap: int, d_off: int, off_cap: int, d_lines: int, lines_cap: int,
+                              stream: int | None) -> tuple[int, int]:
+        """fnnue_vsearch1_lines_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when a buffer is too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch1_lines_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                  C.c_void_p(d_moves_off), ngames, int(k), C.c_void_p(d_out), cap,
+                                                  C.c_void_p(d_off), off_cap, C.c_void_p(d_lines), lines_cap,
+                                                  C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
     def perft_device(self, fen: str, depth: int) -> int:

@@ -343,6 +343,10 @@ int fnnue_game_children(const char *fen, const char *moves, fnnue_pos *out, size
 #define FNNUE_END_CHECK 2
 #define FNNUE_END_EXTINCT 4
 #define FNNUE_END_VARIANT 8
+/* Only on a child record of fnnue_build_vchildren (never from fnnue_game_end):
+ * the child's side to move has already won by the variant's rule (racingkings:
+ * the mover failed to catch up), so the parent's mover lost by playing it. */
+#define FNNUE_END_WON 0x40
 int fnnue_game_end(int variant, const char *fen, const char *moves, int *flags);
 /* Seeded random playouts from the start position (splitmix64; L ~ U[min,max]
  * plies of uniformly random legal moves, stopping at mate, stalemate or the
@@ -395,11 +399,11 @@ int fnnue_random_game(uint64_t seed, const char *fen, uint32_t plies, char *move
 /* ---- one-ply search on the device (ABI 3.4) ----
  * What a search over a position's children needs beyond their records: the
  * move that leads to each child and whether the child is checkmated or
- * stalemated; then, per STAR group, the best child.  Chess nets only
- * (standard, chess960, fromPosition): the Fairy-Stockfish variants keep their
- * host-side one-ply search for move work, and the end-flag byte leaves bits
- * FNNUE_END_EXTINCT / FNNUE_END_VARIANT (and 0x40, "won by the side to move")
- * free for their rules.
+ * stalemated; then, per STAR group, the best child.  These entry points are
+ * for chess nets (standard, chess960, fromPosition); the Fairy-Stockfish
+ * variants have their own below (ABI 3.6: fnnue_build_vchildren,
+ * fnnue_vsearch1), whose end-flag bytes also carry FNNUE_END_EXTINCT /
+ * FNNUE_END_VARIANT and, on a child, FNNUE_END_WON.
  *
  * A move code: from | to << 6 | promo << 12 (squares A1 = 0 .. H8 = 63; promo 0
  * or the piece type 2..5 = n b r q).  Castling carries the squares the game's
@@ -422,17 +426,21 @@ int fnnue_build_children(fnnue_ctx *ctx, const char *text, size_t text_len, cons
                          const uint32_t *moves_off, size_t ngames, fnnue_pos *out, size_t cap, uint32_t *off,
                          size_t off_cap, fnnue_move *moves, uint8_t *end, size_t *n_out, size_t *n_groups);
 /* The best child of a STAR group [off[g], off[g + 1]) (its first record is the
- * parent), by the rule of the backend's move work: a child with NO_MOVES |
- * CHECK is a mate in one and beats everything; a child with NO_MOVES alone is
- * worth 0; any other child -(((int64)psqt + positional) / 16) (C truncation);
- * the first maximum (the lowest index) wins.  An empty group gives an
- * all-zero record. */
-#define FNNUE_BEST_NONE 0 /* no child: `end` says mate 0 (NO_MOVES | CHECK) or cp 0 */
+ * parent), by the rule of the backend's move work: a child with NO_MOVES and
+ * any of CHECK | EXTINCT | VARIANT is a mate in one and beats everything; a
+ * child with NO_MOVES alone is worth 0; any other child
+ * -(((int64)psqt + positional) / 16) (C truncation); a child with
+ * FNNUE_END_WON (whatever its other bits) ranks below all of these, worth 0:
+ * it is chosen only when every child has it.  The first maximum (the lowest
+ * index) wins.  An empty group gives an all-zero record.  (End bytes that use
+ * bits 0 and 1 only — every chess record — rank as they did before ABI 3.6.) */
+#define FNNUE_BEST_NONE 0 /* no child: `end` says mate 0 (NO_MOVES and a deciding flag) or cp 0 */
 #define FNNUE_BEST_CP 1
 #define FNNUE_BEST_MATE 2 /* mate in 1 */
+#define FNNUE_BEST_LOST 3 /* every move loses at once (FNNUE_END_WON children only): mate -1 */
 typedef struct {
   int32_t psqt, positional; /* of the best child, negated (as move work reports them); 0 when none */
-  int32_t value;            /* Stockfish internal units, side to move of the parent; 0 for mate / none */
+  int32_t value;            /* Stockfish internal units, side to move of the parent; 0 for mate / lost / none */
   uint32_t nodes;           /* children */
   uint32_t best;            /* index of the best child within the group (1-based record index), 0 when none */
   fnnue_move move;          /* 0 when none (or without a moves array) */
@@ -466,7 +474,8 @@ int fnnue_search1(fnnue_ctx *ctx, const char *text, size_t text_len, const uint3
 /* ---- MultiPV at depth 1: the k best children of a group (ABI 3.5) ----
  * fnnue_best_children's rule extended to a total order: the mates in one
  * first, in index order; then the children by value (a stalemating child worth
- * 0), descending; equal values by lower index.  A chess ply has at most
+ * 0), descending; equal values by lower index; then the FNNUE_END_WON children
+ * (kind FNNUE_BEST_LOST), in index order.  A chess ply has at most
  * FNNUE_MAX_CHILDREN children. */
 #define FNNUE_MAX_CHILDREN 218
 typedef struct {
@@ -474,7 +483,7 @@ typedef struct {
   int32_t value;            /* internal units, parent's side to move; 0 for a mate */
   uint32_t child;           /* 1-based record index within the group */
   fnnue_move move;          /* 0 without a moves array */
-  uint8_t kind;             /* FNNUE_BEST_CP / FNNUE_BEST_MATE; FNNUE_BEST_NONE = unused slot (all zero) */
+  uint8_t kind;             /* FNNUE_BEST_CP / _MATE / _LOST; FNNUE_BEST_NONE = unused slot (all zero) */
   uint8_t reserved;         /* 0 */
 } fnnue_line;
 /* Group g owns the slots [line_off[g], line_off[g + 1]) of `lines` (line_off:
@@ -509,6 +518,52 @@ int fnnue_search1_lines(fnnue_ctx *ctx, const char *text, size_t text_len, const
                         const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best *out, size_t cap,
                         uint32_t *off, size_t off_cap, fnnue_line *lines, size_t lines_cap, size_t *n_out,
                         size_t *n_groups);
+
+/* ---- one-ply search for the Fairy-Stockfish variants (ABI 3.6) ----
+ * crazyhouse, atomic, kingofthehill and racingkings, on a variant net's
+ * context.
+ *
+ * A variant move code is a fnnue_move that can also spell a drop: from == to
+ * (the drop square) with the promo field holding the dropped piece type 1..5
+ * (P N B R Q), printed "N@f3".  A promotion is never from == to, so the two
+ * forms cannot collide; every other move is encoded as for chess (castling:
+ * the king's two-square step, or king-takes-rook when the game needs Chess960
+ * notation).  FNNUE_E_ARG for from == to with promo 0, for promo 6 or 7, for
+ * promo 1 with from != to, and for a set bit 15.  Host only. */
+int fnnue_vmove_uci(fnnue_move m, char out[8]);
+/* fnnue_build_vbatch[_device] in FNNUE_PLAYOUT_CHILDREN mode (records and
+ * offsets byte for byte, same capacity protocol, same errors) plus moves[r],
+ * the variant move code that leads to record r (0 for a ply's own record), and
+ * end[r], record r's own FNNUE_END_NO_MOVES | CHECK | EXTINCT | VARIANT flags
+ * under the variant's rules (as fnnue_game_end computes them); a child also
+ * carries FNNUE_END_WON when its side to move has already won. */
+int fnnue_build_vchildren_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                                 const uint32_t *d_moves_off, size_t ngames, fnnue_vpos *d_out, size_t cap,
+                                 uint32_t *d_off, size_t off_cap, fnnue_move *d_moves, uint8_t *d_end, size_t *n_out,
+                                 size_t *n_groups, void *stream);
+int fnnue_build_vchildren(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                          const uint32_t *moves_off, size_t ngames, fnnue_vpos *out, size_t cap, uint32_t *off,
+                          size_t off_cap, fnnue_move *moves, uint8_t *end, size_t *n_out, size_t *n_groups);
+/* fnnue_search1[_lines][_device] for a variant net's context: the same three
+ * steps (fnnue_build_vchildren, fnnue_eval_vgroups STAR, the reduction) in the
+ * context's scratch, the same capacity protocol.  `variant` must be one the
+ * context's net evaluates (its own; an atomic net also kingofthehill and
+ * racingkings): FNNUE_E_ARCH otherwise, and on a chess context.  A crazyhouse
+ * ply may have more than FNNUE_MAX_CHILDREN children; k stays 1..218. */
+int fnnue_vsearch1_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                          const uint32_t *d_moves_off, size_t ngames, fnnue_best *d_out, size_t cap, uint32_t *d_off,
+                          size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_vsearch1(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                   const uint32_t *moves_off, size_t ngames, fnnue_best *out, size_t cap, uint32_t *off,
+                   size_t off_cap, size_t *n_out, size_t *n_groups);
+int fnnue_vsearch1_lines_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                                const uint32_t *d_moves_off, size_t ngames, uint32_t k, fnnue_best *d_out, size_t cap,
+                                uint32_t *d_off, size_t off_cap, fnnue_line *d_lines, size_t lines_cap, size_t *n_out,
+                                size_t *n_groups, void *stream);
+int fnnue_vsearch1_lines(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                         const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best *out, size_t cap,
+                         uint32_t *off, size_t off_cap, fnnue_line *lines, size_t lines_cap, size_t *n_out,
+                         size_t *n_groups);
 
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware

@@ -40,7 +40,8 @@
  *                                             a parameter because it is unpinned)
  * Analysis work: one response per ply, depth 0, nodes 1, no pv / best move
  * (the default; fnnue_backend_set_analysis_depth(b, 1) answers chess batches
- * with a one-ply search per ply instead, see there).
+ * with a one-ply search per ply instead, and
+ * fnnue_backend_set_variant_analysis_depth(b, 1) the variant batches, see there).
  * A position with no legal move (it can only be a game's last ply) is
  * answered as the engine answers it — `info depth 0 score mate 0` when the
  * side to move is checkmated (atomic: its king exploded), `score cp 0` when
@@ -153,9 +154,9 @@ void fnnue_backend_free(fnnue_backend *b);
  * child's, negated.  A ply without a legal move is answered exactly as at
  * depth 0 (mate 0 / cp 0, depth 0, nodes 0, no move); skipped ids stay
  * skipped; move work is unchanged.  Variant batches (crazyhouse, atomic,
- * kingOfTheHill, racingKings) are answered at depth 0 exactly as on a depth-0
- * channel: their rules' end flags (FNNUE_END_EXTINCT, FNNUE_END_VARIANT) are
- * not part of the device search yet.
+ * kingOfTheHill, racingKings) are not affected by this setter: they are
+ * answered at depth 0 exactly as on a depth-0 channel unless
+ * fnnue_backend_set_variant_analysis_depth (below) says otherwise.
  * Pieces are cut at a 32nd of FNNUE_BACKEND_PIECE_PLIES, so that a piece's
  * children (about 35 per ply) take the room a depth-0 piece's plies do; each
  * piece reads its children count back once (a bounded wait inside the call's
@@ -170,6 +171,23 @@ void fnnue_backend_free(fnnue_backend *b);
  * more kernel per piece (fnnue_topk_children_device's) and returns the lines
  * beside the responses. */
 int fnnue_backend_set_analysis_depth(fnnue_backend *b, int depth);
+/* The same for the variant nets (ABI 3.6), independent of the chess setting:
+ * 0 (the default) or 1, anything else FNNUE_E_ARG.  At 1 every non-skipped ply
+ * of a crazyhouse, atomic, kingOfTheHill or racingKings analysis batch is
+ * answered with a one-ply search on the device under the variant's rules
+ * (fnnue_vsearch1's steps), by the rule of move work: a child that ends the
+ * game for the opponent (checkmate, an exploded king, the variant's rule) is
+ * Mate(1); a child the mover has lost by playing (racingKings: black fails to
+ * catch up) is chosen only when there is nothing else, Mate(-1); otherwise
+ * Cp(value * 100 / normalize_to_pawn).  depth 1, nodes = the children,
+ * best_move spelled by fnnue_vmove_uci (drops as "N@f3").  A ply without a
+ * legal move is answered as at depth 0; move work is unchanged; go_compact
+ * gives the score without a move; fnnue_backend_go_lines gives such plies their
+ * min(multipv, nodes, 218) lines.  Pieces are cut at an 8th of
+ * FNNUE_BACKEND_PIECE_PLIES, and a piece's children buffers are sized from the
+ * count that is read back (a crazyhouse ply with full pockets has several
+ * hundred children). */
+int fnnue_backend_set_variant_analysis_depth(fnnue_backend *b, int depth);
 
 /* Number of responses batch `a` expands to (IncomingBatch::from_acquired):
  * analysis = moves + 1, move = 1.  Host only; FNNUE_E_ARG on a bad work type. */

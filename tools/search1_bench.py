@@ -3,7 +3,7 @@ shape: N random games (L ~ U[0, 160] plies) with every legal child, HD 1024.
 GPU box only.  One JSON line per measurement.
 
     python tools/search1_bench.py [--games 5000] [--hd 1024] [--runs 3] [--lib PATH] [--actor] [--base-only]
-                                  [--lines K[,K...]]
+                                  [--lines K[,K...]] [--variant NAME[,NAME...]]
 
 The phases are timed with HIP events on the launch stream, after the workload
 ran untimed for 0.3 s:
@@ -22,6 +22,13 @@ phase).  FNNUE_CHILDREN_IMPL=ply|record in
 the environment picks the children kernel (A/B).  `--actor` adds the engine
 actor at depth 0 and 1 for 1, 64 and 1024 lichess-shaped batches; with
 `--lines` also go_lines() at depth 1 with multipv = K for every K <= 5.
+`--variant crazyhouse,atomic,kingOfTheHill,racingKings` (this tree's library
+only) times the variant one-ply search instead, per variant on N random legal
+games of the variant (L ~ U[0, 160] plies): fnnue_build_vbatch_device(CHILDREN)
+(`build`), fnnue_build_vchildren_device (`children`), fnnue_eval_vgroups_device
+(STAR), the reduction and fnnue_vsearch1_device, with the records per ply and
+the share of plies beyond 256 children; with `--actor` the engine actor's go()
+at variant analysis depth 0 and 1 on 1, 64 and 1024 batches of the variant.
 """
 import argparse
 import ctypes as C
@@ -83,7 +90,10 @@ def main():
     ap.add_argument("--base-only", action="store_true", help="only build + eval, whatever the library has")
     ap.add_argument("--lines", default="", help="slots per group, e.g. 1,3,5,218: also time the top-k kernel and "
                                                 "search1_lines (and go_lines with --actor)")
+    ap.add_argument("--variant", default="", help="comma-separated variants: the variant one-ply search instead")
     a = ap.parse_args()
+    if a.variant:
+        return variant_main(a)
     import torch
     lib, has_new, has_lines = bind(a.lib)
     ks = [int(k) for k in a.lines.split(",") if k]
@@ -260,6 +270,138 @@ def actor_lines(a, multipvs=()):
                               "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
                   flush=True)
             actor.close()
+
+
+VSTART = {"crazyhouse": START.replace(" w", "[] w"), "atomic": START, "kingOfTheHill": START,
+          "racingKings": "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1"}
+
+
+def variant_games(F, variant, name, seed, count, lo, hi):
+    """`count` seeded random legal games of the variant, lo..hi plies asked of each (generated on 16 threads)."""
+    from concurrent.futures import ThreadPoolExecutor
+    rng = np.random.default_rng(seed)
+    want = [int(x) for x in rng.integers(lo, hi + 1, count)]
+    with ThreadPoolExecutor(16) as ex:
+        mvs = list(ex.map(lambda i: F.random_vgame(seed * 1_000_003 + i, variant, VSTART[name], want[i]),
+                          range(count)))
+    return [(VSTART[name], m) for m in mvs]
+
+
+def variant_main(a):
+    sys.path.insert(0, ROOT)
+    import torch
+    import fishnet_amd as F
+    from fishnet_amd import backend as B
+    ids = {"crazyhouse": F.VARIANT_CRAZYHOUSE, "atomic": F.VARIANT_ATOMIC, "kingOfTheHill": F.VARIANT_KINGOFTHEHILL,
+           "racingKings": F.VARIANT_RACINGKINGS}
+    dev = torch.device("cuda", 0)
+    for name in a.variant.split(","):
+        v = ids[name]
+        net = F.Net.from_bytes_variant(F.synthesize_variant_net(5 + v, a.hd, v), v)
+        ev = F.Evaluator(net, 0)
+        games = variant_games(F, v, name, a.seed, a.games, 0, 160)
+        text, fen_off, mv_off = F.pack_games(games)
+        d_text = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev)
+        d_fo = torch.from_numpy(fen_off.view(np.int32)).to(dev)
+        d_mo = torch.from_numpy(mv_off.view(np.int32)).to(dev)
+        T, FO, MO, ng = d_text.data_ptr(), d_fo.data_ptr(), d_mo.data_ptr(), len(games)
+        stream = torch.cuda.Stream(dev)
+        S = stream.cuda_stream
+        rc, R, G = ev.build_vchildren_device(v, T, FO, MO, ng, 0, 0, 0, 0, 0, 0, S)
+        assert rc == -10
+        d_pos = torch.empty((R, 48), dtype=torch.uint8, device=dev)
+        d_off = torch.empty(G + 1, dtype=torch.int32, device=dev)
+        d_mv = torch.empty(R, dtype=torch.int16, device=dev)
+        d_end = torch.empty(R, dtype=torch.uint8, device=dev)
+        d_ps = torch.empty(R, dtype=torch.int32, device=dev)
+        d_po = torch.empty(R, dtype=torch.int32, device=dev)
+        d_best = torch.zeros((G, 24), dtype=torch.uint8, device=dev)
+        d_best2 = torch.zeros((G, 24), dtype=torch.uint8, device=dev)
+        d_goff = torch.empty(ng + 1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        n, g = sz(), sz()
+        L = F.nnue.N.lib
+
+        def build():
+            F.nnue.N.check(L.fnnue_build_vbatch_device(ev._h, v, vp(T), vp(FO), vp(MO), ng, 2, vp(d_pos.data_ptr()), R,
+                                                       vp(d_off.data_ptr()), G + 1, C.byref(n), C.byref(g), vp(S)))
+
+        def children():
+            ev.build_vchildren_device(v, T, FO, MO, ng, d_pos.data_ptr(), R, d_off.data_ptr(), G + 1, d_mv.data_ptr(),
+                                      d_end.data_ptr(), S)
+
+        def evaluate():
+            F.nnue.N.check(L.fnnue_eval_vgroups_device(ev._h, vp(d_pos.data_ptr()), vp(d_off.data_ptr()), G, R, 1,
+                                                       vp(d_ps.data_ptr()), vp(d_po.data_ptr()), vp(S)))
+
+        def reduce():
+            ev.best_children_device(d_ps.data_ptr(), d_po.data_ptr(), d_end.data_ptr(), d_mv.data_ptr(),
+                                    d_off.data_ptr(), G, R, d_best.data_ptr(), S)
+
+        def search1():
+            ev.vsearch1_device(v, T, FO, MO, ng, d_best2.data_ptr(), G, d_goff.data_ptr(), ng + 1, S)
+
+        phases = [("build", build), ("eval", evaluate), ("children", children), ("reduce", reduce), ("vsearch1", search1)]
+
+        def once(timed):
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)] if timed else None
+            with torch.cuda.stream(stream):
+                for k, (_, fn) in enumerate(phases):
+                    if timed:
+                        evs[k].record(stream)
+                    fn()
+                if timed:
+                    evs[-1].record(stream)
+            stream.synchronize()
+            ev.check()
+            return [evs[k].elapsed_time(evs[k + 1]) for k in range(len(phases))] if timed else None
+
+        t0 = time.perf_counter()
+        once(False)
+        while time.perf_counter() - t0 < 0.3:
+            once(False)
+        runs = [once(True) for _ in range(a.runs)]
+        kids = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)) - 1
+        base = {"variant": name, "games": a.games, "hd": a.hd, "plies": G, "records": R,
+                "records_per_ply": round(R / G, 2), "max_children": int(kids.max()),
+                "plies_beyond_256_children": int((kids > 256).sum()),
+                "share_beyond_256": round(float((kids > 256).mean()), 6),
+                "plies_beyond_218_children": int((kids > 218).sum())}
+        for k, (pname, _) in enumerate(phases):
+            ms = sorted(r[k] for r in runs)
+            print(json.dumps(dict(base, phase=pname, ms=[round(x, 4) for x in ms], median_ms=round(ms[len(ms) // 2], 4),
+                                  records_per_s=round(R / (ms[len(ms) // 2] * 1e-3)))), flush=True)
+        same = bool(torch.equal(d_best, d_best2))
+        print(json.dumps(dict(base, check="vsearch1 == children + eval + reduce", ok=same,
+                              best_sha256=hashlib.sha256(d_best2.cpu().numpy().tobytes()).hexdigest()[:16])), flush=True)
+        if not same:
+            sys.exit(1)
+        ev.close()
+        if not a.actor:
+            continue
+        for nb in (1, 64, 1024):
+            bodies = [B.AcquireResponseBody(f"b{i}", fen, mv, variant=name)
+                      for i, (fen, mv) in enumerate(variant_games(F, v, name, 11, nb, 40, 160))]
+            plies = sum(len(b.moves.split()) + 1 for b in bodies)
+            for depth in (0, 1):
+                stub, actor = B.channel(net, 0, variant_analysis_depth=depth)
+                t0 = time.perf_counter()
+                stub.go(bodies)
+                while time.perf_counter() - t0 < 0.3:
+                    stub.go(bodies)
+                calls, stats = [], None
+                for _ in range(a.runs):
+                    stub.go(bodies)
+                    calls.append(stub.last_call_s * 1e3)
+                    stats = B.last_stats(actor)
+                calls.sort()
+                med = calls[len(calls) // 2]
+                print(json.dumps({"variant": name, "actor_variant_depth": depth, "batches": nb, "plies": plies,
+                                  "positions": stats["positions"], "ms_per_call": [round(x, 3) for x in calls],
+                                  "median_ms": round(med, 3), "plies_per_s": round(plies / (med * 1e-3)),
+                                  "last_stats": {k: (round(x, 3) if isinstance(x, float) else x)
+                                                 for k, x in stats.items()}}), flush=True)
+                actor.close()
 
 
 if __name__ == "__main__":
