@@ -10,6 +10,7 @@ import fishnet_amd as F
 from fishnet_amd import _native as N
 from oracle.oracle import OracleNet
 from tests.conftest import ROOT, net_bytes
+from tests.corpus import edge_net
 from tests.positions import FENS
 
 pytestmark = pytest.mark.gpu
@@ -627,25 +628,6 @@ def test_swar_rows_match_packed_rows(ev_cache, seed, hd, flags):
     with pytest.raises(F.FnnueError) as e:
         evw.set_swar(True)
     assert e.value.name == "FNNUE_E_ARCH"
-
-
-def edge_net(seed: int, hd: int, mag: tuple[int, int]) -> bytes:
-    """A synthetic net whose FT columns each keep one sign over every row with
-    |w| in [mag[0], mag[1]] and a zero bias: full-board accumulators reach
-    31-32 times mag, close to the doubled-column SWAR limit (2^14).  The first
-    half's odd columns stay small (|w| <= 12) so that half the transform pairs
-    do not saturate and the evaluation still depends on the position."""
-    data = bytearray(net_bytes(seed, hd, 0))
-    desc_len = int(np.frombuffer(data, np.uint32, 1, 8)[0])
-    o = 12 + desc_len + 4
-    rng = np.random.default_rng(seed)
-    sign = np.where(rng.random(hd) < 0.5, -1, 1)
-    w = rng.integers(mag[0], mag[1] + 1, size=(22528, hd)) * sign
-    small = np.arange(hd)[1:hd // 2:2]
-    w[:, small] = rng.integers(-12, 13, size=(22528, small.size))
-    data[o:o + 2 * hd] = bytes(2 * hd)
-    data[o + 2 * hd:o + 2 * hd + 2 * 22528 * hd] = w.astype(np.int16).tobytes()
-    return bytes(data)
 
 
 def test_swar_exact_at_the_doubled_column_limit():
