@@ -30,6 +30,8 @@ VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature
 POS_BYTES = 36
 BEST_BYTES = 24  # fnnue_best
 BEST_NONE, BEST_CP, BEST_MATE, BEST_LOST = 0, 1, 2, 3
+BEST2_BYTES = 32  # fnnue_best2
+BEST_MATED = 4
 LINE_BYTES = 20  # fnnue_line
 PV_LINE_BYTES = 24  # fnnue_pv_line
 MAX_CHILDREN = 218  # FNNUE_MAX_CHILDREN
@@ -169,6 +171,16 @@ SIGNATURES = {
     "fnnue_vsearch1_lines": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
                               _P(_sz)], _i32),
     # include/fnnue_backend.h
+    # the two-ply search (ABI 3.7)
+    "fnnue_best_replies_device": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp], _i32),
+    "fnnue_best_replies": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp], _i32),
+    "fnnue_search2_device": ([_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_search2": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_search2_children": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _P(_sz),
+                                _P(_sz), _P(_sz)], _i32),
+    "fnnue_backend_set_analysis_plies": ([_vp, _i32], _i32),
+    "fnnue_backend_go_pv": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32], _i32),
+    "fnnue_backend_analysis_json_pv": ([_vp, _sz, _vp, C.c_char_p, _sz, _P(_sz)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

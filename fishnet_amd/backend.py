@@ -21,6 +21,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _native as N
+from .nnue import move_uci
 
 WORK_ANALYSIS, WORK_MOVE = 0, 1
 SCORE_CP, SCORE_MATE = 0, 1
@@ -101,6 +102,7 @@ class PositionResponse:
     skipped: bool = False
     matrix: bool = False              # AnalysisPart::Matrix (the batch asked for multipv)
     lines: list[PvLine] | None = None  # go_lines: the MultiPV lines, best first (None: go() / no line)
+    reply: str | None = None          # go_pv on a 2-plies channel: the pv's second move (None: no reply)
 
 
 @dataclass
@@ -184,7 +186,14 @@ class GpuEvalStub:
         line buffer's size (default: lines_bound(bodies))."""
         return self._go(bodies, timeout_ms, lines_bound(bodies) if lines_cap is None else int(lines_cap))
 
-    def _go(self, bodies, timeout_ms, lines_cap):
+    def go_pv(self, bodies: Sequence[AcquireResponseBody],
+              timeout_ms: int = 0) -> list[list[PositionResponse] | PositionFailed]:
+        """go() with the pv's second move (fnnue_backend_go_pv): on a 2-plies
+        channel every ply whose pv has two moves carries `reply`; every other
+        response has reply = None."""
+        return self._go(bodies, timeout_ms, None, with_reply=True)
+
+    def _go(self, bodies, timeout_ms, lines_cap, with_reply=False):
         nb = len(bodies)
         if nb == 0:
             return []
@@ -198,7 +207,11 @@ class GpuEvalStub:
         rc = np.zeros(nb, dtype=np.int32)
         self.last_batch_rc = rc
         t0 = time.perf_counter()
-        if lines_cap is None:
+        if with_reply:
+            reply = np.zeros(max(1, cap), dtype=np.uint16)
+            ret = N.lib.fnnue_backend_go_pv(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc), N.ptr(reply),
+                                            int(timeout_ms))
+        elif lines_cap is None:
             ret = N.lib.fnnue_backend_go_timeout(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc),
                                                  int(timeout_ms))
         else:
@@ -224,6 +237,8 @@ class GpuEvalStub:
                     r.position_id, Score("mate" if r.score_kind == SCORE_MATE else "cp", int(r.score)), r.psqt,
                     r.positional, r.depth, r.nodes, r.time_ms, r.nps, r.best_move.decode() or None,
                     matrix=bool(r.matrix)))
+                if with_reply and reply[k]:
+                    rows[-1].reply = move_uci(int(reply[k]))
                 if lines_cap is not None and loff[k + 1] > loff[k]:
                     rows[-1].lines = [
                         PvLine(Score("mate" if l.score_kind == SCORE_MATE else "cp", int(l.score)), l.move.decode(),
@@ -279,6 +294,11 @@ class GpuEvalStub:
         default), 1 = a one-ply search per chess analysis ply (best move, pv)."""
         N.check(N.lib.fnnue_backend_set_analysis_depth(self._actor._h, int(depth)))
 
+    def set_analysis_plies(self, plies: int) -> None:
+        """fnnue_backend_set_analysis_plies: 0 and 1 as set_analysis_depth, 2 = a full-width two-ply
+        search per chess analysis ply (best move, the reply in go_pv's rows)."""
+        N.check(N.lib.fnnue_backend_set_analysis_plies(self._actor._h, int(plies)))
+
     def set_variant_analysis_depth(self, depth: int) -> None:
         """fnnue_backend_set_variant_analysis_depth: the same for crazyhouse, atomic, kingOfTheHill and
         racingKings analysis batches (drops as "N@f3"); independent of set_analysis_depth."""
@@ -311,14 +331,16 @@ class _Nets(C.Structure):
 
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
             atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0,
-            analysis_depth: int = 0, variant_analysis_depth: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
+            analysis_depth: int = 0, variant_analysis_depth: int = 0,
+            analysis_plies: int | None = None) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` theirs
     (fnnue_backend_channel_netv): each batch is evaluated by its variant's net.
     `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316).
     `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth); `variant_analysis_depth`: 0 or 1
-    for the variant nets' batches (GpuEvalStub.set_variant_analysis_depth)."""
+    for the variant nets' batches (GpuEvalStub.set_variant_analysis_depth); `analysis_plies`: 0, 1 or 2
+    (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None:
@@ -337,12 +359,23 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_analysis_depth(analysis_depth)
     if variant_analysis_depth:
         stub.set_variant_analysis_depth(variant_analysis_depth)
+    if analysis_plies is not None:
+        stub.set_analysis_plies(analysis_plies)
     return stub, actor
+
+
+def _move_code(uci: str | None) -> int:
+    """The fnnue_move code of a chess move's UCI text (0 for None / "")."""
+    if not uci:
+        return 0
+    sq = lambda s: (ord(s[0]) - 97) | (int(s[1]) - 1) << 3
+    return sq(uci[0:2]) | sq(uci[2:4]) << 6 | (" pnbrq".index(uci[4]) if len(uci) > 4 else 0) << 12
 
 
 def into_analysis(responses: Sequence[PositionResponse]) -> str:
     """The `analysis` JSON array of a completed analysis batch (fnnue_backend_analysis_json; with
-    MultiPV lines, fnnue_backend_analysis_json_lines)."""
+    MultiPV lines, fnnue_backend_analysis_json_lines; with a row's `reply`, the two-move pv of
+    fnnue_backend_analysis_json_pv)."""
     arr = (_Response * max(1, len(responses)))()
     for i, r in enumerate(responses):
         if r.skipped:
@@ -366,6 +399,12 @@ def into_analysis(responses: Sequence[PositionResponse]) -> str:
         buf = C.create_string_buffer(n.value + 1)
         N.check(N.lib.fnnue_backend_analysis_json_lines(arr, len(responses), pv, N.ptr(loff), buf, len(buf),
                                                         C.byref(n)))
+        return buf.value.decode()
+    if any(getattr(r, "reply", None) for r in responses):  # go_pv rows: the pv's second move
+        reply = np.array([_move_code(getattr(r, "reply", None)) for r in responses], dtype=np.uint16)
+        N.lib.fnnue_backend_analysis_json_pv(arr, len(responses), N.ptr(reply), None, 0, C.byref(n))
+        buf = C.create_string_buffer(n.value + 1)
+        N.check(N.lib.fnnue_backend_analysis_json_pv(arr, len(responses), N.ptr(reply), buf, len(buf), C.byref(n)))
         return buf.value.decode()
     N.lib.fnnue_backend_analysis_json(arr, len(responses), None, 0, C.byref(n))
     buf = C.create_string_buffer(n.value + 1)

@@ -37,6 +37,14 @@
 // and the variant's end flags, fnnue_eval_vgroups_device's STAR evaluation and
 // the same reduction, whose ranks know the variant flags.
 //
+// Analysis at two plies (fnnue_backend_set_analysis_plies(b, 2); chess nets):
+// stage_search goes on behind the children's evaluation: the children's boards
+// as a dense array (child_states_device), their own children counted (a second
+// sizing read-back), expanded, evaluated as STAR groups and reduced to one
+// fnnue_best per child, then the second reduction (fnnue_best_replies_device's)
+// into one fnnue_best2 per ply; fill() writes score, depth = the pv's length,
+// best move, and the reply beside the responses (fnnue_backend_go_pv).
+//
 // MultiPV (fnnue_backend_go_lines, a depth-1 channel): a piece with a batch
 // that asked for k lines carries every ply's slot offsets up (after ply_off)
 // and one more kernel, fnnue_topk_children_device's, ranks the children that
@@ -100,6 +108,7 @@ struct Job {
   // fnnue_backend_go_lines: the MultiPV lines beside `out`, line_off per response
   fnnue_pv_line* lines = nullptr;
   uint32_t* line_off = nullptr;
+  fnnue_move* reply = nullptr;  // fnnue_backend_go_pv: the pv's second move beside `out`
   int ret = 0;
   std::string err;  // fnnue_last_error of a failed call
 };
@@ -332,6 +341,9 @@ struct Piece {
   // boards sit at st0 of the net's board buffer, and `searched` counts the
   // children the piece's search evaluated.
   bool depth1 = false;
+  // Two plies: depth1's image with one fnnue_best2 per ply at o_best instead;
+  // `searched` counts the children and the grandchildren.
+  bool depth2 = false;
   size_t st0 = 0;
   size_t searched = 0;
   // MultiPV (fnnue_backend_go_lines at depth 1): the plies' slot offsets go up
@@ -366,6 +378,9 @@ struct NetWork {
   // time (records, counts and offsets, moves, end flags, psqt, positional; the
   // pieces follow one another on the stream), with the builder's scan scratch.
   DevBuf states, kid_pos, kid_cnt, kid_off, kid_moves, kid_end, kid_ps, kid_po;
+  // Two plies: one piece's children as boards, their counts, STAR offsets and
+  // depth-1 records, and the grandchildren (records, moves, end flags, terms).
+  DevBuf kid_states, kid2_cnt, kid2_off, kid_best, g_pos, g_moves, g_end, g_ps, g_po;
   PinnedBuf sizing;                 // the builder's error word and a piece's record count, read back
   BuilderScratch bscratch;
   void clear() {
@@ -394,7 +409,9 @@ struct NetWork {
     up.release();
     down.release();
     scratch.release();
-    for (DevBuf* b : {&states, &kid_pos, &kid_cnt, &kid_off, &kid_moves, &kid_end, &kid_ps, &kid_po}) b->release();
+    for (DevBuf* b : {&states, &kid_pos, &kid_cnt, &kid_off, &kid_moves, &kid_end, &kid_ps, &kid_po, &kid_states,
+                      &kid2_cnt, &kid2_off, &kid_best, &g_pos, &g_moves, &g_end, &g_ps, &g_po})
+      b->release();
     sizing.release();
     bscratch.release();
     for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
@@ -435,9 +452,13 @@ struct fnnue_backend {
   fnnue_ctx* ctx[kKinds] = {};  // one evaluator per net, all on one device
   int device = 0;
   int32_t norm = kNormalizeToPawnSf151;
-  int analysis_depth = 0;        // fnnue_backend_set_analysis_depth: 1 = a one-ply search per chess analysis ply
+  // fnnue_backend_set_analysis_depth / _plies: 1 = a one-ply search per chess analysis ply, 2 = two plies
+  int analysis_depth = 0;
   int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
-  bool depth1(int k) const { return (k == kVariantChess ? analysis_depth : variant_analysis_depth) == 1; }
+  int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
+  // a search per ply (one ply or two), and the two-ply search
+  bool depth1(int k) const { return (k == kVariantChess ? job_plies : variant_analysis_depth) >= 1; }
+  bool depth2(int k) const { return k == kVariantChess && job_plies == 2; }
   size_t piece_plies = 524288;  // FNNUE_BACKEND_PIECE_PLIES
   bool any_order = true;         // FNNUE_BACKEND_ANY_ORDER=0: wait for the nets' pieces in net order
   size_t tail_plies = 0;         // FNNUE_BACKEND_TAIL_PLIES: a net's last piece cut to about this many
@@ -641,6 +662,7 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.nk = P.kids ? W.nk : 0;
   const size_t ng = P.ng, n = P.n, nk = P.nk;
   P.depth1 = depth1(k) && ng;
+  P.depth2 = depth2(k) && ng;
   P.nslots = 0;
   if (j.lines && P.depth1)
     for (size_t i : P.games) P.nslots += (size_t)(j.off[i + 1] - j.off[i]) * line_slots(j.batches[i]);
@@ -654,7 +676,7 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.o_ps = align16(P.o_fin + ng);
   P.o_po = P.o_ps + 4 * (n + nk);
   P.o_best = align16(P.o_po + 4 * (n + nk));
-  P.o_lines = P.o_best + n * sizeof(fnnue_best);
+  P.o_lines = P.o_best + n * (P.depth2 ? sizeof(fnnue_best2) : sizeof(fnnue_best));
   P.end = P.depth1 ? P.o_lines + P.nslots * sizeof(fnnue_line) : P.o_po + 4 * (n + nk);
 }
 
@@ -672,7 +694,9 @@ int fnnue_backend::plan(Job& j, int k) {
   // that read-back, so fewer and larger pieces measured faster (DESIGN.md
   // §4.16: 1024 crazyhouse batches in 33.1 / 17.4 / 13.4 ms at a 128th / 32nd
   // / 8th).
+  // At two plies a ply brings about a thousand grandchildren: a 1024th.
   const size_t cut_plies = !depth1(k)           ? piece_plies
+                           : depth2(k)          ? std::max<size_t>(16, piece_plies / 1024)
                            : k == kVariantChess ? std::max<size_t>(1024, piece_plies / 32)
                                                 : std::max<size_t>(256, piece_plies / 8);
   for (size_t i : W.games) {
@@ -904,9 +928,56 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                      : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(kp), coff, n, total,
                                                  FNNUE_GROUP_STAR, kps, kpo, s))
     return rc;
-  HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
-                               s),
-          "best_children launch");
+  P.searched = total - n;
+  if (P.depth2) {
+    // Two plies: the children's boards, their own children counted and the
+    // count read back (the second sizing wait), expanded and evaluated, one
+    // fnnue_best per child, then the second reduction into the results image.
+    const size_t nkid = total - n;
+    if (int rc = W.kid_best.reserve((nkid + 1) * sizeof(fnnue_best))) return rc;
+    fnnue_best* kb = W.kid_best.at<fnnue_best>(0);
+    if (nkid) {
+      if (int rc = W.kid_states.reserve(nkid * sizeof(DBoard))) return rc;
+      if (int rc = W.kid2_cnt.reserve((nkid + 1) * 4)) return rc;
+      if (int rc = W.kid2_off.reserve((nkid + 1) * 4)) return rc;
+      DBoard* ks = W.kid_states.at<DBoard>(0);
+      uint32_t* goff = W.kid2_off.at<uint32_t>(0);
+      HIP_TRY(child_states_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total, ks, nullptr, s),
+              "child_states launch");
+      HIP_TRY(children_count_device(ks, (uint32_t)nkid, W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch),
+              "grandchildren count launch");
+      HIP_TRY(hipMemcpyAsync(hs + 1, goff + nkid, 4, hipMemcpyDeviceToHost, s), "D2H(grandchildren count)");
+      HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(grandchildren count)");
+      const auto tg = Clock::now();
+      const int rcg = wait_event(W.ev_done[pi], "sizing a piece's grandchildren");
+      wait_ms += ms_since(tg);
+      ++syncs;
+      if (rcg) return rcg;
+      const size_t gtotal = hs[1];
+      if (int rc = W.g_pos.reserve(gtotal * W.rec)) return rc;
+      if (int rc = W.g_moves.reserve(gtotal * 2)) return rc;
+      if (int rc = W.g_end.reserve(gtotal)) return rc;
+      if (int rc = W.g_ps.reserve(gtotal * 4)) return rc;
+      if (int rc = W.g_po.reserve(gtotal * 4)) return rc;
+      fnnue_pos* gp = W.g_pos.at<fnnue_pos>(0);
+      uint16_t* gm = W.g_moves.at<uint16_t>(0);
+      uint8_t* ge = W.g_end.at<uint8_t>(0);
+      int32_t* gps = W.g_ps.at<int32_t>(0);
+      int32_t* gpo = W.g_po.at<int32_t>(0);
+      HIP_TRY(children_write_device(ks, (uint32_t)nkid, goff, (uint32_t)gtotal, gp, gm, ge, s), "grandchildren launch");
+      if (int rc = fnnue_eval_groups_device(c, gp, goff, nkid, gtotal, FNNUE_GROUP_STAR, gps, gpo, s)) return rc;
+      HIP_TRY(launch_best_children_own(gps, gpo, ge, gm, goff, (uint32_t)nkid, (uint32_t)gtotal, kb, s),
+              "best_children launch");
+      P.searched += gtotal - nkid;
+    }
+    HIP_TRY(launch_best_replies(ke, km, coff, n, (uint32_t)total, kb, nullptr,
+                                reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
+            "best_replies launch");
+  } else {
+    HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
+                                 reinterpret_cast<fnnue_best*>(dimg + P.o_best), s),
+            "best_children launch");
+  }
   if (P.nslots)  // a go_lines() call whose piece has a batch that asked for MultiPV
     HIP_TRY(launch_topk_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
                                  reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
@@ -915,7 +986,6 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   HIP_TRY(launch_gather_parents(kps, kpo, coff, n, (uint32_t)total, reinterpret_cast<int32_t*>(dimg + P.o_ps),
                                 reinterpret_cast<int32_t*>(dimg + P.o_po), s),
           "gather_parents launch");
-  P.searched = total - n;
   return FNNUE_OK;
 }
 
@@ -1047,7 +1117,8 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const int32_t* po = reinterpret_cast<const int32_t*>(res + (P.o_po - P.o_res));
   const uint32_t* ply = W.up.at<uint32_t>(P.up0 + P.o_ply);
   filled += P.n + P.nk + P.searched;
-  const fnnue_best* best = P.depth1 ? reinterpret_cast<const fnnue_best*>(res + (P.o_best - P.o_res)) : nullptr;
+  const fnnue_best* best = P.depth1 && !P.depth2 ? reinterpret_cast<const fnnue_best*>(res + (P.o_best - P.o_res)) : nullptr;
+  const fnnue_best2* best2 = P.depth2 ? reinterpret_cast<const fnnue_best2*>(res + (P.o_best - P.o_res)) : nullptr;
   const bool with_lines = P.depth1 && P.nslots && j.lines;
   const fnnue_line* dlines = with_lines ? reinterpret_cast<const fnnue_line*>(res + (P.o_lines - P.o_res)) : nullptr;
   const uint32_t* loff = with_lines ? W.up.at<uint32_t>(P.up0 + P.o_loff) : nullptr;
@@ -1068,6 +1139,44 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
       // be played from it): mate 0 / cp 0 instead of an evaluation.
       const bool ends = fin[g] & kFinalNoMoves;
       const uint8_t end_kind = (fin[g] & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+      if (best2) {
+        // Two plies: every ply from its fnnue_best2; a ply without a child as at depth 0.
+        const fnnue_best2* gb = best2 + ply[g];
+        const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
+        for (uint32_t q = 0; q < len; ++q) {
+          const fnnue_best2& B = gb[q];
+          const bool skipped = sk && skip[b + q];
+          const bool none = B.kind == FNNUE_BEST_NONE;
+          const bool mate = B.kind == FNNUE_BEST_MATE, mated = B.kind == FNNUE_BEST_MATED;
+          const uint8_t kind = none ? end_kind : mate || mated ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+          const int64_t score = none ? 0 : mate ? 1 : mated ? -1 : (int64_t)B.value * 100 / nrm;
+          const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
+          const uint8_t depth = none ? 0 : B.pv_len;
+          if (j.cout) {
+            if (skipped)
+              put_compact(j.cout + b + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
+            else
+              put_compact(j.cout + b + q, rps, rpo, (int32_t)score, kind, depth, none ? fl | FNNUE_COMPACT_NO_MOVES : fl);
+            continue;
+          }
+          fnnue_position_response* r = j.out + b + q;
+          if (skipped) {
+            put_response(r, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
+            continue;
+          }
+          put_response(r, response_head(q, 0, kind, depth, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
+          if (!none) (void)fnnue_move_uci(B.move, r->best_move);
+          if (j.reply && !none) j.reply[b + q] = B.reply;
+        }
+        if (j.cout) {
+          fnnue_batch_compact& B = j.bout[i];
+          B.time_ms = ms;
+          B.nps = nps;
+          B.nodes = 0;
+          std::memset(B.best_move, 0, sizeof(B.best_move));
+        }
+        continue;
+      }
       if (best) {
         // Depth 1: every ply from its fnnue_best.  A ply without a child is the
         // game's last one without a legal move, answered as at depth 0.
@@ -1300,6 +1409,7 @@ void fnnue_backend::run(Job& j) {
   filled = 0;
   fill_ms = wait_ms = 0;
   syncs = rebuilds = 0;
+  job_plies = analysis_depth == 2 && j.lines ? 1 : analysis_depth;  // MultiPV is a one-ply search
   const size_t nb = j.nb;
   flen.resize(nb);
   mlen.resize(nb);
@@ -1362,6 +1472,7 @@ void fnnue_backend::run(Job& j) {
     return;
   }
   for (NetWork& W : net) W.clear();
+  if (j.reply) std::memset(j.reply, 0, (size_t)j.off[nb] * sizeof(fnnue_move));  // none until fill() says otherwise
   if (j.lines) {  // every response without lines until fill() says otherwise
     std::memset(j.line_off, 0, ((size_t)j.off[nb] + 1) * sizeof(uint32_t));
     lbase.resize(nb);
@@ -1746,6 +1857,17 @@ int fnnue_backend_go_lines(fnnue_backend* b, const fnnue_acquired* batches, size
   return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
 }
 
+int fnnue_backend_go_pv(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches, fnnue_position_response* out,
+                        size_t cap, uint32_t* off, int32_t* batch_rc, fnnue_move* reply, uint32_t timeout_ms) {
+  if (!b || !off || !batch_rc || (nbatches && !batches) || (cap && (!out || !reply)))
+    return fail(FNNUE_E_ARG, "null argument");
+  if (nbatches > (1u << 24)) return fail(FNNUE_E_ARG, "too many batches");
+  Job j;
+  j.out = out;
+  j.reply = reply;
+  return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
+}
+
 int fnnue_backend_go(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches, fnnue_position_response* out,
                      size_t cap, uint32_t* off, int32_t* batch_rc) {
   return fnnue_backend_go_timeout(b, batches, nbatches, out, cap, off, batch_rc, 0);
@@ -1756,6 +1878,14 @@ int fnnue_backend_set_analysis_depth(fnnue_backend* b, int depth) {
   if (depth != 0 && depth != 1) return fail(FNNUE_E_ARG, "analysis depth 0 or 1, not " + std::to_string(depth));
   std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
   b->analysis_depth = depth;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_analysis_plies(fnnue_backend* b, int plies) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (plies < 0 || plies > 2) return fail(FNNUE_E_ARG, "analysis plies 0, 1 or 2, not " + std::to_string(plies));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->analysis_depth = plies;
   return FNNUE_OK;
 }
 
@@ -1779,7 +1909,7 @@ int fnnue_backend_last_stats(fnnue_backend* b, fnnue_backend_stats* out) {
 namespace {
 // Both JSON forms: without `lines` every response has its own one line.
 int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_line* lines, const uint32_t* line_off,
-                  char* buf, size_t cap, size_t* len) {
+                  char* buf, size_t cap, size_t* len, const fnnue_move* reply = nullptr) {
   std::string s = "[";
   char tmp[192];
   for (size_t i = 0; i < n; ++i) {
@@ -1800,6 +1930,9 @@ int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_lin
     pv[7] = 0;
     for (char* c = pv; *c; ++c)
       if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';  // never from this library
+    // the pv's second move (fnnue_backend_go_pv): only behind a first one
+    char pv2[8] = {0};
+    if (reply && reply[i] && pv[0] && fnnue_move_uci(reply[i], pv2) != FNNUE_OK) pv2[0] = 0;
     const size_t nl = line_off && r[i].matrix ? line_off[i + 1] - line_off[i] : 0;  // lines are rows of the matrix form
     if (nl) {
       // Matrix::set per line: row l is `depth` nulls and then the entry
@@ -1826,14 +1959,15 @@ int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_lin
     } else if (r[i].matrix) {
       s += "{\"pv\":[[";
       for (unsigned d = 0; d < r[i].depth; ++d) s += "null,";
-      s += pv[0] ? std::string("[\"") + pv + "\"]" : std::string("[]");
+      s += pv[0] ? std::string("[\"") + pv + (pv2[0] ? std::string("\",\"") + pv2 : std::string()) + "\"]"
+                 : std::string("[]");
       s += "]],\"score\":[[";
       for (unsigned d = 0; d < r[i].depth; ++d) s += "null,";
       std::snprintf(tmp, sizeof(tmp), "{\"%s\":%lld}]],\"depth\":%u,\"nodes\":%llu,\"time\":%llu", kind,
                     (long long)r[i].score, (unsigned)r[i].depth, (unsigned long long)r[i].nodes,
                     (unsigned long long)r[i].time_ms);
     } else {
-      if (pv[0]) s += std::string("{\"pv\":\"") + pv + "\",";
+      if (pv[0]) s += std::string("{\"pv\":\"") + pv + (pv2[0] ? std::string(" ") + pv2 : std::string()) + "\",";
       else s += '{';
       std::snprintf(tmp, sizeof(tmp), "\"score\":{\"%s\":%lld},\"depth\":%u,\"nodes\":%llu,\"time\":%llu", kind,
                     (long long)r[i].score, (unsigned)r[i].depth, (unsigned long long)r[i].nodes,
@@ -1862,6 +1996,12 @@ extern "C" {
 int fnnue_backend_analysis_json(const fnnue_position_response* r, size_t n, char* buf, size_t cap, size_t* len) {
   if ((n && !r) || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
   return analysis_json(r, n, nullptr, nullptr, buf, cap, len);
+}
+
+int fnnue_backend_analysis_json_pv(const fnnue_position_response* r, size_t n, const fnnue_move* reply, char* buf,
+                                   size_t cap, size_t* len) {
+  if ((n && !r) || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
+  return analysis_json(r, n, nullptr, nullptr, buf, cap, len, reply);
 }
 
 int fnnue_backend_analysis_json_lines(const fnnue_position_response* r, size_t n, const fnnue_pv_line* lines,

@@ -69,6 +69,10 @@ struct BuilderScratch {
   enum {
     kPlies, kPlyOff, kErr, kScan, kStates, kCnt, kCoff,
     kKids, kKidMoves, kKidEnd, kKidPsqt, kKidPositional,  // the one-ply search's children and their evaluation
+    // the two-ply search: the children's boards, counts, STAR offsets and depth-1 records (whole call), the
+    // plies' spans in them, then one chunk's offsets, grandchild records, moves, end flags and terms
+    kKidStates, kKidCnt, kKidOff, kKidBest, kPlySpans, kChunkOff, kGrand, kGrandMoves, kGrandEnd, kGrandPsqt,
+    kGrandPositional,
     kSlots
   };
   void* p[kSlots] = {};
@@ -118,6 +122,22 @@ hipError_t children_write_device(const DBoard* d_states, uint32_t n, const uint3
 // one (measurements: DESIGN.md §4.14).
 int children_impl();
 
+// The two-ply search's child states: the boards of the children of n plies'
+// STAR groups (d_off: n + 1 offsets, total = d_off[n] records) as a dense array
+// in record order, the plies' own records skipped: child j (1-based) of ply i
+// is entry d_off[i] - i + j - 1, total - n entries in all.  d_map (optional):
+// entry -> (ply, child index).  children_count_device / children_write_device
+// expand the array like any other.  Stream-ordered, no sync.
+hipError_t child_states_device(const DBoard* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                               DBoard* d_out, uint2* d_map, hipStream_t s);
+// Per ply p in 0..n: d_first_child[p] = d_off[p] - p, d_first_rec[p] =
+// d_kid_off[d_first_child[p]] (the children's STAR offsets): what the host
+// needs to cut the plies into chunks of bounded grandchild records.
+hipError_t ply_spans_device(const uint32_t* d_off, const uint32_t* d_kid_off, uint32_t n, uint32_t* d_first_child,
+                            uint32_t* d_first_rec, hipStream_t s);
+// d_dst[i] = d_src[i] - d_src[0], i < n: a chunk's offsets from the whole array's.
+hipError_t rebase_offsets_device(const uint32_t* d_src, uint32_t n, uint32_t* d_dst, hipStream_t s);
+
 // The chess replay with both outputs: the packed plies and their boards.
 hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                       const uint32_t* d_ply_off, uint32_t ngames, fnnue_pos* d_out, DBoard* d_states,
@@ -128,6 +148,18 @@ hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_
 hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
                                 const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
                                 fnnue_best* d_out, hipStream_t s);
+// The same with a childless group's own terms in its record (the two-ply
+// search's children: fnnue_best_replies reads them for a one-move pv).
+hipError_t launch_best_children_own(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
+                                    const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
+                                    fnnue_best* d_out, hipStream_t s);
+// The second reduction (fnnue_best_replies_device).  d_base: group g's first
+// entry in d_child_best (launch_child_counts' d_cnt, ngroups + 1 words, scanned),
+// or null when no group is empty: d_off[g] - g.
+hipError_t launch_child_counts(const uint32_t* d_off, uint32_t ngroups, uint32_t npos, uint32_t* d_cnt, hipStream_t s);
+hipError_t launch_best_replies(const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups,
+                               uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                               fnnue_best2* d_out, hipStream_t s);
 // The k best children of every group as fnnue_line records: group g's slots are
 // [d_line_off[g], d_line_off[g + 1]), or [g * uniform_k, (g + 1) * uniform_k)
 // when d_line_off is null; nothing is written at or beyond lines_cap.

@@ -149,6 +149,56 @@ __global__ __launch_bounds__(64) void write_children_record_kernel(const DBoard*
   end[r] = j ? end_of(c) : ChessRules::end_flags(b, off[lo + 1] - o0 > 1);
 }
 
+// ---- the two-ply search's child states ----
+// One thread per record of the plies' STAR groups, as write_children_record_kernel
+// finds its ply and its move; a child's board is stored as it is (not packed),
+// the ply's own record is skipped.  Child j of ply i is entry off[i] - i + j - 1:
+// a dense array in record order, which children_count_device and
+// children_write_device expand like any array of boards.  map (optional):
+// entry d -> (ply, 1-based child index).
+__global__ __launch_bounds__(64) void child_states_kernel(const DBoard* __restrict__ states, uint32_t n,
+                                                          const uint32_t* __restrict__ off, uint32_t total,
+                                                          DBoard* __restrict__ out, uint2* __restrict__ map) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  uint32_t lo = 0, hi = n;  // off[lo] <= r < off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t j = r - off[lo];
+  if (j == 0) return;
+  const DBoard b = states[lo];
+  DBoard c = b;
+  uint32_t k = 0;
+  for_each_legal(b, [&](const DMove& m) -> bool {
+    if (++k < j) return true;
+    do_move(c, m);
+    return false;
+  });
+  const uint32_t d = r - lo - 1;
+  out[d] = c;
+  if (map) map[d] = make_uint2(lo, j);
+}
+
+// Per ply p (p = n: the totals): its first entry in the dense child array and
+// that entry's first grandchild record (kid_off: the children's STAR offsets).
+__global__ void ply_spans_kernel(const uint32_t* __restrict__ off, const uint32_t* __restrict__ kid_off, uint32_t n,
+                                 uint32_t* __restrict__ first_child, uint32_t* __restrict__ first_rec) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > n) return;
+  const uint32_t c = off[p] - p;
+  first_child[p] = c;
+  first_rec[p] = kid_off[c];
+}
+
+// dst[i] = src[i] - src[0]: a chunk's STAR offsets cut out of the whole array's.
+__global__ void rebase_offsets_kernel(const uint32_t* __restrict__ src, uint32_t n, uint32_t* __restrict__ dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[i] - src[0];
+}
+
 template <int D>
 __device__ uint64_t perft_dev(const DBoard& b) {
   uint64_t n = 0;
@@ -278,6 +328,30 @@ hipError_t children_write_device(const DBoard* d_states, uint32_t n, const uint3
   else
     hipLaunchKernelGGL(write_children_ply_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, d_states, n, d_off, d_out,
                        d_moves, d_end);
+  return hipGetLastError();
+}
+
+hipError_t child_states_device(const DBoard* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                               DBoard* d_out, uint2* d_map, hipStream_t s) {
+  if (n == 0 || total == 0) return hipSuccess;
+  const uint32_t bs = 64;
+  hipLaunchKernelGGL(child_states_kernel, dim3((total + bs - 1) / bs), dim3(bs), 0, s, d_states, n, d_off, total, d_out,
+                     d_map);
+  return hipGetLastError();
+}
+
+hipError_t ply_spans_device(const uint32_t* d_off, const uint32_t* d_kid_off, uint32_t n, uint32_t* d_first_child,
+                            uint32_t* d_first_rec, hipStream_t s) {
+  const uint32_t bs = 256;
+  hipLaunchKernelGGL(ply_spans_kernel, dim3((n + 1 + bs - 1) / bs), dim3(bs), 0, s, d_off, d_kid_off, n, d_first_child,
+                     d_first_rec);
+  return hipGetLastError();
+}
+
+hipError_t rebase_offsets_device(const uint32_t* d_src, uint32_t n, uint32_t* d_dst, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t bs = 256;
+  hipLaunchKernelGGL(rebase_offsets_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, d_src, n, d_dst);
   return hipGetLastError();
 }
 

@@ -395,7 +395,10 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      fnnue_best / fnnue_best_children[_device], fnnue_search1[_device], fnnue_backend_set_analysis_depth
 // 3.5: MultiPV at depth 1: fnnue_line / fnnue_topk_children[_device], fnnue_search1_lines[_device],
 //      fnnue_pv_line / fnnue_backend_go_lines, fnnue_backend_lines_bound, fnnue_backend_analysis_json_lines
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 6u; }
+// 3.7: the two-ply search: fnnue_best2 / fnnue_best_replies[_device], fnnue_search2[_device],
+//      fnnue_search2_children, fnnue_backend_set_analysis_plies, fnnue_backend_go_pv,
+//      fnnue_backend_analysis_json_pv
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 7u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1692,6 +1695,299 @@ int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint3
                   size_t* n_out, size_t* n_groups) {
   return search1_host(ctx, kVariantChess, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0, n_out,
                       n_groups);
+}
+
+int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
+                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
+                              void* stream) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!d_end || !d_off || !d_child_best || !d_out) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // the groups' first entries in d_child_best (a caller's groups may be empty) live in the context's scratch
+  int rc = order_workspace(ctx, s);
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  uint32_t *cnt = nullptr, *base = nullptr;
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidCnt, (ngroups + 1) * 4, (void**)&cnt), "device allocation (scratch)");
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidOff, (ngroups + 1) * 4, (void**)&base), "device allocation (scratch)");
+  HIP_TRY(launch_child_counts(d_off, (uint32_t)ngroups, (uint32_t)npos, cnt, s), "child_counts launch");
+  HIP_TRY(builder_exclusive_scan(cnt, base, (uint32_t)ngroups, s, ctx->bscratch), "scan");
+  HIP_TRY(launch_best_replies(d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_child_best, base, d_out, s),
+          "best_replies launch");
+  return FNNUE_OK;
+}
+
+int fnnue_best_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                       size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!off || !out || (npos && !end)) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  size_t nchild = 0;  // as the kernel clamps the offsets
+  for (size_t i = 0; i < ngroups; ++i) {
+    const size_t e = std::min<size_t>(off[i + 1], npos), o = std::min<size_t>(off[i], e);
+    if (e > o) nchild += e - o - 1;
+  }
+  if (nchild && !child_best) return fail(FNNUE_E_ARG, "null buffer");
+  DeviceGuard g(ctx->device);
+  // [child_best | off | out | moves | end]: 4-byte parts first
+  const size_t o_off = (nchild + 1) * sizeof(fnnue_best), o_out = o_off + (ngroups + 1) * 4;
+  const size_t o_mv = o_out + ngroups * sizeof(fnnue_best2), o_end = o_mv + npos * 2;
+  TempDev buf;
+  if (int rc = buf.get(o_end + npos)) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  if (nchild) HIP_TRY(hipMemcpyAsync(d, child_best, nchild * sizeof(fnnue_best), hipMemcpyHostToDevice, s), "H2D");
+  if (npos) {
+    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
+    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  const int rc = fnnue_best_replies_device(ctx, reinterpret_cast<uint8_t*>(d + o_end),
+                                           moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
+                                           reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
+                                           reinterpret_cast<fnnue_best*>(d), reinterpret_cast<fnnue_best2*>(d + o_out), s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d + o_out, ngroups * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One ply's most records two plies down: 218 children of 1 + 218 records each.
+constexpr size_t kSearch2MinRecords = (size_t)(FNNUE_MAX_CHILDREN + 1) * (FNNUE_MAX_CHILDREN + 1);
+
+size_t search2_budget() {
+  size_t n = (size_t)16 << 20;
+  if (const char* e = std::getenv("FNNUE_SEARCH2_RECORDS")) n = (size_t)std::max(0LL, std::atoll(e));
+  return std::min<size_t>(std::max(n, kSearch2MinRecords), 0xFFFFFFFFu);
+}
+
+// FNNUE_SEARCH2_TRACE=1 in the environment (read per call): HIP events between
+// the phases of a fnnue_search2 call; the call then waits for its work and
+// prints the phases' device times to stderr, one JSON line — diagnostics only
+// (tools/search2_bench.py).
+struct Search2Trace {
+  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kPhases };
+  bool on = false;
+  hipStream_t s = nullptr;
+  std::vector<std::pair<int, hipEvent_t>> marks;
+  Search2Trace(hipStream_t stream) : s(stream) {
+    const char* e = std::getenv("FNNUE_SEARCH2_TRACE");
+    on = e && *e && *e != '0';
+  }
+  void mark(int phase) {  // `phase` starts here (kPhases: the end)
+    if (!on) return;
+    hipEvent_t ev = nullptr;
+    if (hipEventCreate(&ev) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) on = false;
+    if (ev) marks.emplace_back(phase, ev);
+  }
+  void report(size_t plies, size_t kids, size_t records, size_t chunks) {
+    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1", "reduce2"};
+    if (on && !marks.empty() && hipEventSynchronize(marks.back().second) == hipSuccess) {
+      double ms[kPhases] = {};
+      for (size_t i = 0; i + 1 < marks.size(); ++i) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, marks[i].second, marks[i + 1].second) == hipSuccess) ms[marks[i].first] += t;
+      }
+      std::string line = "FNNUE_SEARCH2_TRACE {\"plies\":" + std::to_string(plies) + ",\"children\":" +
+                         std::to_string(kids) + ",\"grandchild_records\":" + std::to_string(records) +
+                         ",\"chunks\":" + std::to_string(chunks);
+      for (int k = 0; k < kPhases; ++k) line += std::string(",\"") + kName[k] + "_ms\":" + std::to_string(ms[k]);
+      std::fprintf(stderr, "%s}\n", line.c_str());
+    }
+  }
+  ~Search2Trace() {
+    for (auto& m : marks) (void)hipEventDestroy(m.second);
+  }
+};
+
+// fnnue_search2_device; with d_child_best / d_child_map (child_cap entries
+// each) also the children's depth-1 records (fnnue_search2_children).
+int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                   size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
+                   fnnue_best* d_child_best, uint32_t* d_child_map, size_t child_cap, size_t* n_out, size_t* n_groups,
+                   size_t* n_children, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (n_children) *n_children = 0;
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  int rc = order_workspace(ctx, s);
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  using W = BuilderScratch;
+  W& ws = ctx->bscratch;
+  Search2Trace trace(s);
+  trace.mark(Search2Trace::kLevel1);
+  // level 1: the plies' boards (scratch) and their STAR groups' offsets, moves and end flags
+  ChildrenBufs kids;
+  kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  size_t nrec = 0, nply = 0;
+  rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
+                    nullptr, nullptr, &nrec, &nply, s, &kids);
+  *n_out = nply;
+  *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
+  if (rc) return rc;
+  if (nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  const size_t nkid = nrec - nply;
+  if (n_children) *n_children = nkid;
+  if (n_children && (nkid > child_cap || (nkid && (!d_child_best || !d_child_map))))
+    return fail(FNNUE_E_CAPACITY, "child buffers too small");
+  const DBoard* plies = static_cast<const DBoard*>(ws.p[W::kStates]);
+  DBoard* kid_states = nullptr;
+  uint32_t *kid_cnt = nullptr, *kid_off = nullptr, *spans = nullptr;
+  fnnue_best* kid_best = nullptr;
+  HIP_TRY(ws.get(W::kKidStates, (nkid + 1) * sizeof(DBoard), (void**)&kid_states), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kKidCnt, (nkid + 1) * 4, (void**)&kid_cnt), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kKidOff, (nkid + 1) * 4, (void**)&kid_off), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kKidBest, (nkid + 1) * sizeof(fnnue_best), (void**)&kid_best), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kPlySpans, (nply + 1) * 8, (void**)&spans), "device allocation (search scratch)");
+  if (nkid == 0) {  // every ply is a finished game's last
+    HIP_TRY(launch_best_replies(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr,
+                                d_out, s),
+            "best_replies launch");
+    HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
+    return FNNUE_OK;
+  }
+  trace.mark(Search2Trace::kChildStates);
+  HIP_TRY(child_states_device(plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kid_states,
+                              reinterpret_cast<uint2*>(d_child_map), s),
+          "child_states launch");
+  // level 2 sizes: every child's records, and per ply where its children and their records start
+  trace.mark(Search2Trace::kCount);
+  HIP_TRY(children_count_device(kid_states, (uint32_t)nkid, kid_cnt, kid_off, s, ws), "children count");
+  HIP_TRY(ply_spans_device(kids.off, kid_off, (uint32_t)nply, spans, spans + nply + 1, s), "ply_spans launch");
+  std::vector<uint32_t> h((nply + 1) * 2);
+  HIP_TRY(hipMemcpyAsync(h.data(), spans, h.size() * 4, hipMemcpyDeviceToHost, s), "D2H(sizes)");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  const uint32_t *first_kid = h.data(), *first_rec = h.data() + nply + 1;
+  // chunks of whole plies within the budget (one ply alone always fits); the
+  // differences are taken in 32 bits, as the device takes them, so a call whose
+  // grandchild records pass 2^32 in all still cuts and runs chunk by chunk
+  const size_t budget = search2_budget();
+  std::vector<uint32_t> cuts{0};
+  size_t max_rec = 0, max_kid = 0, all_rec = 0;
+  for (size_t p = 0; p < nply;) {
+    size_t q = p + 1;
+    while (q < nply && (uint32_t)(first_rec[q + 1] - first_rec[p]) <= budget &&
+           (size_t)(q + 1 - p) * kSearch2MinRecords <= 0xFFFFFFFFu)
+      ++q;
+    max_rec = std::max<size_t>(max_rec, first_rec[q] - first_rec[p]);
+    all_rec += first_rec[q] - first_rec[p];
+    max_kid = std::max<size_t>(max_kid, first_kid[q] - first_kid[p]);
+    cuts.push_back((uint32_t)q);
+    p = q;
+  }
+  uint32_t* ch_off = nullptr;
+  fnnue_pos* gpos = nullptr;
+  uint16_t* gmoves = nullptr;
+  uint8_t* gend = nullptr;
+  int32_t *gps = nullptr, *gpo = nullptr;
+  HIP_TRY(ws.get(W::kChunkOff, (max_kid + 1) * 4, (void**)&ch_off), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrand, max_rec * sizeof(fnnue_pos), (void**)&gpos), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrandMoves, max_rec * 2, (void**)&gmoves), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrandEnd, max_rec, (void**)&gend), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrandPsqt, max_rec * 4, (void**)&gps), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrandPositional, max_rec * 4, (void**)&gpo), "device allocation (search scratch)");
+  for (size_t i = 0; i + 1 < cuts.size(); ++i) {
+    const uint32_t k0 = first_kid[cuts[i]], nk = first_kid[cuts[i + 1]] - k0;
+    const uint32_t nr = first_rec[cuts[i + 1]] - first_rec[cuts[i]];
+    if (nk == 0) continue;  // plies without a legal move
+    trace.mark(Search2Trace::kExpand);
+    HIP_TRY(rebase_offsets_device(kid_off + k0, nk + 1, ch_off, s), "rebase_offsets launch");
+    HIP_TRY(children_write_device(kid_states + k0, nk, ch_off, nr, gpos, gmoves, gend, s), "children write");
+    trace.mark(Search2Trace::kEval);
+    if ((rc = fnnue_eval_groups_device(ctx, gpos, ch_off, nk, nr, FNNUE_GROUP_STAR, gps, gpo, s))) return rc;
+    trace.mark(Search2Trace::kReduce1);
+    HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
+  }
+  trace.mark(Search2Trace::kReduce2);
+  HIP_TRY(launch_best_replies(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out,
+                              s),
+          "best_replies launch");
+  trace.mark(Search2Trace::kPhases);
+  trace.report(nply, nkid, all_rec, cuts.size() - 1);
+  if (n_children && nkid)
+    HIP_TRY(hipMemcpyAsync(d_child_best, kid_best, nkid * sizeof(fnnue_best), hipMemcpyDeviceToDevice, s),
+            "D2D(children)");
+  HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
+  return FNNUE_OK;
+}
+
+int search2_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
+                 size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap, fnnue_best* child_best,
+                 uint32_t* child_map, size_t child_cap, size_t* n_out, size_t* n_groups, size_t* n_children) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (n_children) *n_children = 0;
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  const bool room = out && off && off_cap >= ngames + 1;
+  const bool kroom = n_children && child_best && child_map;
+  if (!kroom) child_cap = 0;
+  // [best2 | child_best | child_map | off]
+  TempDev buf;
+  const size_t o_cb = cap * sizeof(fnnue_best2), o_cm = o_cb + child_cap * sizeof(fnnue_best);
+  const size_t o_off = o_cm + child_cap * 8;
+  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  rc = search2_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best2*>(d) : nullptr,
+                      room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
+                      room && kroom ? reinterpret_cast<fnnue_best*>(d + o_cb) : nullptr,
+                      room && kroom ? reinterpret_cast<uint32_t*>(d + o_cm) : nullptr, room ? child_cap : 0, n_out,
+                      n_groups, n_children, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
+  if (n_children && *n_children) {
+    HIP_TRY(hipMemcpyAsync(child_best, d + o_cb, *n_children * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
+    HIP_TRY(hipMemcpyAsync(child_map, d + o_cm, *n_children * 8, hipMemcpyDeviceToHost, s), "D2H");
+  }
+  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return latched(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnnue_search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                         size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
+                         size_t* n_groups, void* stream) {
+  return search2_device(ctx, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, nullptr, nullptr, 0,
+                        n_out, n_groups, nullptr, stream);
+}
+
+int fnnue_search2(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                  const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap,
+                  size_t* n_out, size_t* n_groups) {
+  return search2_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr, nullptr, 0,
+                      n_out, n_groups, nullptr);
+}
+
+int fnnue_search2_children(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                           const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
+                           size_t off_cap, fnnue_best* child_best, uint32_t* child_map, size_t child_cap,
+                           size_t* n_out, size_t* n_groups, size_t* n_children) {
+  if (!n_children) return fail(FNNUE_E_ARG, "null argument");
+  return search2_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, child_best, child_map,
+                      child_cap, n_out, n_groups, n_children);
 }
 
 int fnnue_vmove_uci(fnnue_move m, char out[8]) {

@@ -13,6 +13,8 @@
 // 24-byte record.  No atomics, no LDS, no host synchronisation.
 // The k best children of every group (fnnue_topk_children_device, MultiPV):
 // topk_children_kernel below, the same key ranked by counting in LDS.
+// The second reduction of the two-ply search (fnnue_best_replies_device):
+// best_replies_kernel below, the same shape over the children's own records.
 #include <hip/hip_runtime.h>
 
 #include "builder.h"
@@ -49,6 +51,9 @@ __device__ __forceinline__ uint32_t key_kind(unsigned long long key) {
   return rank == 2 ? FNNUE_BEST_MATE : rank == 0 ? FNNUE_BEST_LOST : FNNUE_BEST_CP;
 }
 
+// kOwnTerms (the two-ply search's children): a group without a child stores its
+// own first record's terms as they are instead of zeros (fnnue_best_replies).
+template <bool kOwnTerms>
 __global__ __launch_bounds__(kBlock) void best_children_kernel(
     const int32_t* __restrict__ psqt, const int32_t* __restrict__ positional, const uint8_t* __restrict__ end,
     const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off, uint32_t ngroups, uint32_t npos,
@@ -78,8 +83,8 @@ __global__ __launch_bounds__(kBlock) void best_children_kernel(
   if (nrec) {  // an empty group: all zero
     const uint32_t kind = !best ? FNNUE_BEST_NONE : key_kind(key);
     switch (lane) {
-      case 0: w = best ? 0u - (uint32_t)psqt[o + best] : 0u; break;        // negated, wrapping
-      case 1: w = best ? 0u - (uint32_t)positional[o + best] : 0u; break;
+      case 0: w = best ? 0u - (uint32_t)psqt[o + best] : kOwnTerms ? (uint32_t)psqt[o] : 0u; break;  // negated, wrapping
+      case 1: w = best ? 0u - (uint32_t)positional[o + best] : kOwnTerms ? (uint32_t)positional[o] : 0u; break;
       case 2: w = kind == FNNUE_BEST_CP ? (uint32_t)value : 0u; break;
       case 3: w = nrec - 1; break;
       case 4: w = best; break;
@@ -199,6 +204,95 @@ __global__ __launch_bounds__(kBlock) void gather_parents_kernel(const int32_t* _
   po_out[g] = ok ? positional[o] : 0;
 }
 
+// ---- the second reduction of the two-ply search (fnnue_best_replies_device) ----
+// The first reduction's shape: 32 lanes per ply, each folding the children
+// lane + 1, lane + 33, ... into one key
+//   rank (3 mate in one, 2 a value: a stalemating move is worth 0, 1 the reply
+//   mates) << 62 | (value + 2^29) << 32 | ~index,   value = -b_c.value
+// from the child's end flags and its own depth-1 record b_c, and summing the
+// children's nodes beside it; five xor-shuffles leave the largest key and the
+// sum in every lane; lanes 0-7 store one dword each of the 32-byte record.
+// Child c of group g is child_best[base + c - 1], base = off[g] - g when every
+// group has its own record (the search), else base[g] (hand-made input: the
+// count of the children of the groups before, child_counts_kernel and a scan).
+static_assert(sizeof(fnnue_best2) == 32, "fnnue_best2 is eight dwords");
+
+__global__ __launch_bounds__(kBlock) void child_counts_kernel(const uint32_t* __restrict__ off, uint32_t ngroups,
+                                                              uint32_t npos, uint32_t* __restrict__ cnt) {
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  if (g > ngroups) return;
+  uint32_t n = 0;
+  if (g < ngroups) {
+    const uint32_t e = min(off[g + 1], npos), o = min(off[g], e);
+    n = e - o ? e - o - 1 : 0;
+  }
+  cnt[g] = n;
+}
+
+__global__ __launch_bounds__(kBlock) void best_replies_kernel(
+    const uint8_t* __restrict__ end, const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off,
+    uint32_t ngroups, uint32_t npos, const uint32_t* __restrict__ child_best, const uint32_t* __restrict__ base_of,
+    uint32_t* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t g = (uint32_t)(t / kGroupLanes), lane = (uint32_t)(t % kGroupLanes);
+  const bool live = g < ngroups;  // no early return: the shuffles below run with the whole wave
+  uint32_t o = 0, e = 0, base = 0;
+  if (live) {
+    e = min(off[g + 1], npos);
+    o = min(off[g], e);
+    base = base_of ? base_of[g] : o - g;
+  }
+  const uint32_t nrec = e - o;
+  constexpr uint32_t kDeciding = kFinalCheck | kFinalExtinct | kFinalVariant;
+  unsigned long long key = 0;  // 0: no child (a child's key is never 0: ~index)
+  uint32_t nodes = 0;
+  for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
+    const uint32_t f = end[o + c];
+    const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
+    uint32_t rank = 2;
+    int32_t v = 0;
+    if (f & kFinalNoMoves) {
+      rank = (f & kDeciding) ? 3u : 2u;
+    } else {
+      const uint32_t kind = (b[5] >> 16) & 0xFFu;
+      if (kind == FNNUE_BEST_MATE) rank = 1;
+      else v = -(int32_t)b[2];
+    }
+    nodes += b[3];
+    const unsigned long long k =
+        (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+    key = k > key ? k : key;
+  }
+#pragma unroll
+  for (int m = kGroupLanes / 2; m >= 1; m >>= 1) {
+    const unsigned long long other = (unsigned long long)__shfl_xor((long long)key, m, kGroupLanes);
+    key = other > key ? other : key;
+    nodes += (uint32_t)__shfl_xor((int)nodes, m, kGroupLanes);
+  }
+  uint32_t w = 0;
+  if (nrec) {  // an empty group: all zero
+    const uint32_t best = key ? 0xFFFFFFFFu - (uint32_t)key : 0u;
+    const uint32_t rank = (uint32_t)(key >> 62);
+    const int32_t value = (int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29);
+    const bool one = best && (end[o + best] & kFinalNoMoves);  // the pv ends at the child
+    const uint32_t kind = !best ? FNNUE_BEST_NONE : rank == 3 ? FNNUE_BEST_MATE : rank == 1 ? FNNUE_BEST_MATED : FNNUE_BEST_CP;
+    const uint32_t pv_len = !best ? 0u : one ? 1u : 2u;
+    const uint32_t* b = child_best + (size_t)(base + (best ? best - 1 : 0)) * 6;  // read only with a best child
+    switch (lane) {
+      case 0: w = !best ? 0u : one ? 0u - b[0] : b[0]; break;  // a one-move pv: the child's own terms, negated (wrapping)
+      case 1: w = !best ? 0u : one ? 0u - b[1] : b[1]; break;
+      case 2: w = kind == FNNUE_BEST_CP ? (uint32_t)value : 0u; break;
+      case 3: w = nrec - 1 + nodes; break;
+      case 4: w = best; break;
+      case 5: w = best && !one ? b[4] : 0u; break;
+      case 6: w = (best && moves ? (uint32_t)moves[o + best] : 0u) | (best && !one ? (b[5] & 0xFFFFu) << 16 : 0u); break;
+      case 7: w = kind | (uint32_t)end[o] << 8 | pv_len << 16; break;
+      default: break;
+    }
+  }
+  if (live && lane < 8) out[(size_t)g * 8 + lane] = w;
+}
+
 }  // namespace
 
 hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
@@ -206,8 +300,35 @@ hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_position
                                 fnnue_best* d_out, hipStream_t s) {
   if (ngroups == 0) return hipSuccess;
   const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
-  hipLaunchKernelGGL(best_children_kernel, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+  hipLaunchKernelGGL(best_children_kernel<false>, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                      d_psqt, d_positional, d_end, d_moves, d_off, ngroups, npos, reinterpret_cast<uint32_t*>(d_out));
+  return hipGetLastError();
+}
+
+hipError_t launch_best_children_own(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
+                                    const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
+                                    fnnue_best* d_out, hipStream_t s) {
+  if (ngroups == 0) return hipSuccess;
+  const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
+  hipLaunchKernelGGL(best_children_kernel<true>, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     d_psqt, d_positional, d_end, d_moves, d_off, ngroups, npos, reinterpret_cast<uint32_t*>(d_out));
+  return hipGetLastError();
+}
+
+hipError_t launch_child_counts(const uint32_t* d_off, uint32_t ngroups, uint32_t npos, uint32_t* d_cnt, hipStream_t s) {
+  hipLaunchKernelGGL(child_counts_kernel, dim3((ngroups + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d_off, ngroups,
+                     npos, d_cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_best_replies(const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups,
+                               uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                               fnnue_best2* d_out, hipStream_t s) {
+  if (ngroups == 0) return hipSuccess;
+  const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
+  hipLaunchKernelGGL(best_replies_kernel, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_end,
+                     d_moves, d_off, ngroups, npos, reinterpret_cast<const uint32_t*>(d_child_best), d_base,
+                     reinterpret_cast<uint32_t*>(d_out));
   return hipGetLastError();
 }
 

@@ -226,6 +226,11 @@ class Best(C.Structure):
 BEST_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("best", "<u4"),
                        ("move", "<u2"), ("kind", "u1"), ("end", "u1")])
 BEST_NONE, BEST_CP, BEST_MATE, BEST_LOST = N.BEST_NONE, N.BEST_CP, N.BEST_MATE, N.BEST_LOST
+# fnnue_best2: the result of a two-ply search over one position (kind BEST_MATED: every move allows a mate in one)
+BEST2_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("best", "<u4"),
+                        ("reply_index", "<u4"), ("move", "<u2"), ("reply", "<u2"), ("kind", "u1"), ("end", "u1"),
+                        ("pv_len", "u1"), ("reserved", "u1")])
+BEST_MATED = N.BEST_MATED
 
 
 class Line(C.Structure):
@@ -472,6 +477,58 @@ class Evaluator:
         """fnnue_search1_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
         n, g = C.c_size_t(), C.c_size_t()
         N.check(N.lib.fnnue_search1_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
+                                           ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n),
+                                           C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    # the two-ply search (ABI 3.7)
+    def best_replies(self, end, moves, off, child_best) -> np.ndarray:
+        """fnnue_best_replies: the second reduction, one BEST2_DTYPE record per STAR group from the
+        level-1 end flags and moves (moves may be None) and the children's BEST_DTYPE records
+        (dense, in record order)."""
+        end = np.ascontiguousarray(end, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        child_best = np.ascontiguousarray(child_best, dtype=BEST_DTYPE)
+        if moves is not None:
+            moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        out = np.zeros(len(off) - 1, dtype=BEST2_DTYPE)
+        N.check(N.lib.fnnue_best_replies(self._h, N.ptr(end), N.ptr(moves), N.ptr(off), len(off) - 1, len(end),
+                                         N.ptr(child_best), N.ptr(out)))
+        return out
+
+    def best_replies_device(self, d_end: int, d_moves: int | None, d_off: int, ngroups: int, npos: int,
+                            d_child_best: int, d_out: int, stream: int | None):
+        N.check(N.lib.fnnue_best_replies_device(self._h, C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off),
+                                                ngroups, npos, C.c_void_p(d_child_best), C.c_void_p(d_out),
+                                                C.c_void_p(stream)))
+
+    def search2(self, games, children: bool = False):
+        """fnnue_search2: a two-ply search per ply -> (BEST2_DTYPE records, CHAIN offsets per game).
+        With `children` (fnnue_search2_children) also the children's depth-1 records and their
+        (ply, 1-based child index) pairs: -> (records, offsets, BEST_DTYPE records, (n, 2) uint32)."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST2_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        if not children:
+            N.check(N.lib.fnnue_search2(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                        N.ptr(out), cap, N.ptr(off), len(off), C.byref(n), C.byref(g)))
+            return out[: n.value], off[: g.value + 1]
+        kcap = cap * MAX_CHILDREN
+        kb = np.zeros(max(kcap, 1), dtype=BEST_DTYPE)
+        km = np.zeros((max(kcap, 1), 2), dtype=np.uint32)
+        nk = C.c_size_t()
+        N.check(N.lib.fnnue_search2_children(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                             N.ptr(out), cap, N.ptr(off), len(off), N.ptr(kb), N.ptr(km), kcap,
+                                             C.byref(n), C.byref(g), C.byref(nk)))
+        return out[: n.value], off[: g.value + 1], kb[: nk.value], km[: nk.value]
+
+    def search2_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int, cap: int,
+                       d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_search2_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search2_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
                                            ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n),
                                            C.byref(g), C.c_void_p(stream)))
         return n.value, g.value

@@ -565,6 +565,73 @@ int fnnue_vsearch1_lines(fnnue_ctx *ctx, int variant, const char *text, size_t t
                          uint32_t *off, size_t off_cap, fnnue_line *lines, size_t lines_cap, size_t *n_out,
                          size_t *n_groups);
 
+/* ---- two-ply search on the device (ABI 3.7) ----
+ * Full-width minimax over two plies, chess nets only.  For a ply P with the
+ * children c = 1..n in generation order, b_c is child c's own depth-1 record:
+ * fnnue_best_children's result for the STAR group (child c, its children).
+ * The key of child c, from P's side to move:
+ *   end[c] has NO_MOVES and a deciding flag (CHECK): mate in one   rank 3             pv c
+ *   end[c] has NO_MOVES alone: a stalemating move                  rank 2, value 0    pv c
+ *   b_c.kind == FNNUE_BEST_MATE: the reply mates                   rank 1             pv c, reply
+ *   otherwise                                                      rank 2, -b_c.value pv c, reply
+ * The higher rank wins, then the higher value, then the lower child index (the
+ * first maximum, as at depth 1).  A ply without a legal move is
+ * FNNUE_BEST_NONE with its own end flags. */
+#define FNNUE_BEST_MATED 4 /* every move allows a mate in one: Score::Mate(-1) */
+typedef struct {
+  int32_t psqt, positional; /* of the pv's last position, from P's side to move: a two-move pv -> the
+                               grandchild's terms as they are; a one-move pv -> the child's, negated with
+                               wrap-around (as fnnue_best); 0 when none */
+  int32_t value;            /* FNNUE_BEST_CP only, else 0 */
+  uint32_t nodes;           /* children + all grandchildren of P */
+  uint32_t best;            /* 1-based index of the child in P's group; 0 when none */
+  uint32_t reply_index;     /* 1-based index of the reply in the child's group; 0 when the pv has one move */
+  fnnue_move move, reply;   /* reply 0 when the pv has one move */
+  uint8_t kind;             /* FNNUE_BEST_NONE / _CP / _MATE / _MATED */
+  uint8_t end;              /* P's own end flags */
+  uint8_t pv_len;           /* 0, 1 or 2 */
+  uint8_t reserved;         /* 0 */
+} fnnue_best2;
+/* The second reduction alone (no atomics, no host synchronisation): end / moves
+ * (moves may be NULL) hold npos entries and off ngroups + 1, as for
+ * fnnue_best_children (offsets beyond npos are clamped; an empty group gives an
+ * all-zero record).  child_best holds one fnnue_best per child record, dense,
+ * in record order: the children of the first group with any, then the next
+ * group's (npos less the non-empty groups, after clamping).  The entry of a
+ * child without a legal move is read for its psqt / positional only, taken as
+ * the child's own terms from its own side to move (fnnue_search2 stores them
+ * there); the record negates them.  nodes = the group's children + the sum of
+ * their entries' nodes.  End bytes are read as chess end bytes (bits 0, 1).
+ * Any net. */
+int fnnue_best_replies_device(fnnue_ctx *ctx, const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                              size_t ngroups, size_t npos, const fnnue_best *d_child_best, fnnue_best2 *d_out,
+                              void *stream);
+int fnnue_best_replies(fnnue_ctx *ctx, const uint8_t *end, const fnnue_move *moves, const uint32_t *off,
+                       size_t ngroups, size_t npos, const fnnue_best *child_best, fnnue_best2 *out);
+/* Depth 2 for every ply of every game: fnnue_search1's signature, capacity
+ * protocol (*n_out = plies, *n_groups = games, set also with
+ * FNNUE_E_CAPACITY, before anything is expanded) and errors.  The plies are
+ * walked in chunks, cut at ply boundaries so that a chunk's grandchild records
+ * stay within FNNUE_SEARCH2_RECORDS (environment; default 16M, never below one
+ * ply's maximum of 219 * 219); the results do not depend on it.  The children's
+ * boards and depth-1 records (112 bytes per child) are held for the whole
+ * call.  Host waits: the builder's sizing read-backs and one for the chunk cuts.
+ * A chess net's context; FNNUE_E_ARCH otherwise. */
+int fnnue_search2_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off, const uint32_t *d_moves_off,
+                         size_t ngames, fnnue_best2 *d_out, size_t cap, uint32_t *d_off, size_t off_cap,
+                         size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_search2(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                  const uint32_t *moves_off, size_t ngames, fnnue_best2 *out, size_t cap, uint32_t *off,
+                  size_t off_cap, size_t *n_out, size_t *n_groups);
+/* fnnue_search2 plus the children's depth-1 records it reduced: child_best[d]
+ * and child_map[d] = (ply, 1-based child index) for every child of every ply,
+ * in record order (child_cap entries each; *n_children is set also with
+ * FNNUE_E_CAPACITY).  For tests and tools. */
+int fnnue_search2_children(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                           const uint32_t *moves_off, size_t ngames, fnnue_best2 *out, size_t cap, uint32_t *off,
+                           size_t off_cap, fnnue_best *child_best, uint32_t *child_map, size_t child_cap,
+                           size_t *n_out, size_t *n_groups, size_t *n_children);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

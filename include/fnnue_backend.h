@@ -271,7 +271,7 @@ typedef struct {
   double device_ms;       /* host waiting for the device (blocked, or polling the nets' pieces) */
   double fill_ms;         /* responses written (overlaps the device's later pieces) */
   double total_ms;
-  uint64_t positions;     /* positions evaluated (analysis plies + move-work children) */
+  uint64_t positions;     /* positions evaluated (analysis plies + move-work children; + searched children, grandchildren) */
   uint32_t stream_syncs;  /* host blocking waits on an event, a stream or a copy */
   uint32_t rebuilds;      /* extra passes after a batch failed (per failed batch, its piece only) */
   uint32_t host_threads;  /* threads for the staging / fill loops (FNNUE_BACKEND_THREADS; default: the usable CPUs, at most 8) */
@@ -344,6 +344,43 @@ int fnnue_backend_go_lines(fnnue_backend *b, const fnnue_acquired *batches, size
  * one line the two functions give the same bytes. */
 int fnnue_backend_analysis_json_lines(const fnnue_position_response *r, size_t n, const fnnue_pv_line *lines,
                                       const uint32_t *line_off, char *buf, size_t cap, size_t *len);
+
+/* ---- analysis at two plies (ABI 3.7) ----
+ * fnnue_backend_set_analysis_plies(b, plies): 0, 1 or 2, anything else
+ * FNNUE_E_ARG.  0 and 1 are fnnue_backend_set_analysis_depth(b, 0 / 1), on the
+ * same field (that setter keeps refusing 2).  At 2 every non-skipped ply of a
+ * chess analysis batch is answered with fnnue_search2's full-width two-ply
+ * search on the device (fnnue.h, fnnue_best2): Score::Cp(value * 100 /
+ * normalize_to_pawn), Mate(1) (a mate in one) or Mate(-1) (every move allows a
+ * mate in one); depth = the pv's length, 2, or 1 when the best move ends the
+ * game; nodes = children + grandchildren; best_move = the pv's first move;
+ * psqt / positional = the record's (the pv's last position, from the ply's
+ * side to move).  A ply without a legal move is answered as at depth 0;
+ * skipped ids, move work and variant batches are unchanged; go_compact gives
+ * score and depth only.  fnnue_backend_go_lines on a 2-plies channel behaves
+ * as on a 1-ply channel: depth-1 responses and lines (MultiPV at two plies is
+ * not built).  Pieces are cut at a 1024th of FNNUE_BACKEND_PIECE_PLIES (at
+ * least 16 plies), so that a piece's grandchildren (about 1000 per ply) take
+ * the room a depth-0 piece's plies do; each piece has two bounded sizing waits
+ * (children, grandchildren) inside the call's budget; a piece with a rejected
+ * game skips the search.  fnnue_backend_stats.positions counts plies +
+ * children + grandchildren. */
+int fnnue_backend_set_analysis_plies(fnnue_backend *b, int plies);
+/* fnnue_backend_go_timeout plus the pv's second move: reply[i] is parallel to
+ * out[i] (cap entries), the reply's fnnue_move code (fnnue_move_uci prints it)
+ * or 0 for none: a channel below 2 plies, a one-move pv, a ply without a legal
+ * move, skipped ids, move work, variant batches, failed batches.  The
+ * responses are those of go() / go_timeout() on the same channel. */
+int fnnue_backend_go_pv(fnnue_backend *b, const fnnue_acquired *batches, size_t nbatches,
+                        fnnue_position_response *out, size_t cap, uint32_t *off, int32_t *batch_rc, fnnue_move *reply,
+                        uint32_t timeout_ms);
+/* fnnue_backend_analysis_json with the replies of a go_pv() (reply: n entries
+ * parallel to r, or NULL): a response with a best move and a reply carries
+ * both as its pv, "pv":"e2e4 e7e5" (space-separated, as Vec<Uci> is
+ * serialised; the matrix form: ["e2e4","e7e5"]).  Without a reply the bytes
+ * are fnnue_backend_analysis_json's. */
+int fnnue_backend_analysis_json_pv(const fnnue_position_response *r, size_t n, const fnnue_move *reply, char *buf,
+                                   size_t cap, size_t *len);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,153 @@
+"""Times of the two-ply search (fnnue_search2_device) and of the engine actor
+at two plies.  GPU box only.  One JSON line per measurement.
+
+    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor]
+
+The shape: N random legal games of L plies each from the start position
+(default 200 x 60: ~12k plies, ~400k children, ~13M grandchild records, a few
+chunks of the default FNNUE_SEARCH2_RECORDS budget).  Timed with HIP events on
+the launch stream, after the workload ran untimed for 0.3 s:
+  search1   fnnue_search1_device on the same games (the one-ply search)
+  search2   fnnue_search2_device, everything in one call
+then one more search2 call with FNNUE_SEARCH2_TRACE=1, whose phases the
+library times itself with HIP events between them and prints to stderr
+(`FNNUE_SEARCH2_TRACE {...}`): level1 (replay, the plies' children), child
+states, the children's counts and the sizing read-back, then over the chunks
+the grandchild expansion, their STAR evaluation and the first reduction, and
+the second reduction.  records_per_s counts the records each search evaluates
+(search1: plies + children; search2: the grandchild records, which hold every
+child once more).
+`--actor` adds the engine actor's go_pv() at 1 and 2 plies on 1 and 64
+lichess-shaped chess batches.
+"""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+START = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=200)
+    ap.add_argument("--plies", type=int, default=60)
+    ap.add_argument("--hd", type=int, default=1024)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=4)
+    ap.add_argument("--actor", action="store_true")
+    a = ap.parse_args()
+    import torch
+    import fishnet_amd as F
+    from fishnet_amd import _native as N
+
+    games = [(START, F.random_game(a.seed * 1_000_003 + i, START, a.plies)) for i in range(a.games)]
+    text, fen_off, mv_off = F.pack_games(games)
+    dev = torch.device("cuda", 0)
+    d_text = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev)
+    d_fo = torch.from_numpy(fen_off.view(np.int32)).to(dev)
+    d_mo = torch.from_numpy(mv_off.view(np.int32)).to(dev)
+    T, FO, MO, ng = d_text.data_ptr(), d_fo.data_ptr(), d_mo.data_ptr(), len(games)
+    ev = F.Evaluator(F.Net.from_bytes(F.synthesize_net(1, a.hd, 0)), 0)
+    stream = torch.cuda.Stream(dev)
+    S = stream.cuda_stream
+    plies = sum(len(m.split()) + 1 for _, m in games)
+    d_b1 = torch.zeros((plies, N.BEST_BYTES), dtype=torch.uint8, device=dev)
+    d_b2 = torch.zeros((plies, N.BEST2_BYTES), dtype=torch.uint8, device=dev)
+    d_goff = torch.empty(ng + 1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+
+    def search1():
+        ev.search1_device(T, FO, MO, ng, d_b1.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+
+    def search2():
+        ev.search2_device(T, FO, MO, ng, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+
+    phases = [("search1", search1), ("search2", search2)]
+
+    def once(timed):
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)] if timed else None
+        with torch.cuda.stream(stream):
+            for k, (_, fn) in enumerate(phases):
+                if timed:
+                    evs[k].record(stream)
+                fn()
+            if timed:
+                evs[-1].record(stream)
+        stream.synchronize()
+        ev.check()
+        return [evs[k].elapsed_time(evs[k + 1]) for k in range(len(phases))] if timed else None
+
+    t0 = time.perf_counter()
+    once(False)
+    while time.perf_counter() - t0 < 0.3:
+        once(False)
+    runs = [once(True) for _ in range(a.runs)]
+    b1 = d_b1.cpu().numpy().view(F.BEST_DTYPE).reshape(-1)
+    b2 = d_b2.cpu().numpy().view(F.BEST2_DTYPE).reshape(-1)
+    children = int(b1["nodes"].sum())
+    grand_records = int(b2["nodes"].sum())  # every child's own record + its children
+    assert int(b2["nodes"].max()) <= 219 * 219
+    base = {"games": ng, "hd": a.hd, "plies": plies, "children": children, "grandchild_records": grand_records,
+            "budget": int(os.environ.get("FNNUE_SEARCH2_RECORDS", 16 << 20))}
+    for k, (name, _) in enumerate(phases):
+        ms = sorted(r[k] for r in runs)
+        rec = plies + children if name == "search1" else grand_records
+        print(json.dumps(dict(base, phase=name, ms=[round(x, 4) for x in ms], median_ms=round(ms[len(ms) // 2], 4),
+                              records=rec, records_per_s=round(rec / (ms[len(ms) // 2] * 1e-3)))), flush=True)
+    kinds = {int(k): int((b2["kind"] == k).sum()) for k in np.unique(b2["kind"])}
+    print(json.dumps(dict(base, check="kinds and pv lengths", kinds=kinds,
+                          pv_len={int(k): int((b2["pv_len"] == k).sum()) for k in np.unique(b2["pv_len"])},
+                          best2_sha256=hashlib.sha256(b2.tobytes()).hexdigest()[:16])), flush=True)
+    # the phases, timed by the library itself (its line goes to stderr)
+    os.environ["FNNUE_SEARCH2_TRACE"] = "1"
+    for _ in range(a.runs):
+        with torch.cuda.stream(stream):
+            search2()
+        stream.synchronize()
+    os.environ["FNNUE_SEARCH2_TRACE"] = "0"
+    ev.close()
+    if a.actor:
+        actor_lines(a)
+
+
+def actor_lines(a):
+    """The engine actor at 1 and 2 plies on the same lichess-shaped chess batches."""
+    import fishnet_amd as F
+    from fishnet_amd import backend as B
+    import bench
+    net = F.Net.from_bytes(F.synthesize_net(1, a.hd, 0))
+    for nb in (1, 64):
+        bodies = bench.lichess_batches(F, 11, nb, variants=0.0)
+        plies = sum(len(b.moves.split()) + 1 for b in bodies)
+        for n in (1, 2):
+            stub, actor = B.channel(net, 0, analysis_plies=n)
+            t0 = time.perf_counter()
+            stub.go_pv(bodies)
+            while time.perf_counter() - t0 < 0.3:
+                stub.go_pv(bodies)
+            calls, stats = [], None
+            for _ in range(a.runs):
+                stub.go_pv(bodies)
+                calls.append(stub.last_call_s * 1e3)
+                stats = B.last_stats(actor)
+            calls.sort()
+            med = calls[len(calls) // 2]
+            print(json.dumps({"actor_plies": n, "batches": nb, "plies": plies, "positions": stats["positions"],
+                              "ms_per_call": [round(x, 3) for x in calls], "median_ms": round(med, 3),
+                              "plies_per_s": round(plies / (med * 1e-3)),
+                              "positions_per_s": round(stats["positions"] / (med * 1e-3)),
+                              "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
+                  flush=True)
+            actor.close()
+
+
+if __name__ == "__main__":
+    main()
