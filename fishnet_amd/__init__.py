@@ -10,5 +10,5 @@ from .nnue import (  # noqa: F401
 )
 from ._native import (  # noqa: F401
     GROUP_CHAIN, GROUP_STAR, PLAYOUT_CHILDREN, PLAYOUT_FINAL, PLAYOUT_PLIES, VARIANT_ATOMIC, VARIANT_CRAZYHOUSE,
-    VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS,
+    VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS, VARIANT_THREECHECK,
 )

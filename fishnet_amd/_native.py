@@ -27,6 +27,7 @@ FT_GATHER_MAX = 16384  # FNNUE_FT_AUTO gathers chess positions calls up to this 
 PLAYOUT_FINAL, PLAYOUT_PLIES, PLAYOUT_CHILDREN = 0, 1, 2
 VARIANT_CHESS, VARIANT_CRAZYHOUSE, VARIANT_ATOMIC = 0, 1, 2
 VARIANT_KINGOFTHEHILL, VARIANT_RACINGKINGS = 3, 4  # atomic's board-only feature set, their own rules
+VARIANT_THREECHECK = 5  # the same feature set; chess with check counters carried along the game (ABI 3.8)
 POS_BYTES = 36
 BEST_BYTES = 24  # fnnue_best
 BEST_NONE, BEST_CP, BEST_MATE, BEST_LOST = 0, 1, 2, 3

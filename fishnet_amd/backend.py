@@ -300,8 +300,8 @@ class GpuEvalStub:
         N.check(N.lib.fnnue_backend_set_analysis_plies(self._actor._h, int(plies)))
 
     def set_variant_analysis_depth(self, depth: int) -> None:
-        """fnnue_backend_set_variant_analysis_depth: the same for crazyhouse, atomic, kingOfTheHill and
-        racingKings analysis batches (drops as "N@f3"); independent of set_analysis_depth."""
+        """fnnue_backend_set_variant_analysis_depth: the same for crazyhouse, atomic, kingOfTheHill,
+        racingKings and threeCheck analysis batches (drops as "N@f3"); independent of set_analysis_depth."""
         N.check(N.lib.fnnue_backend_set_variant_analysis_depth(self._actor._h, int(depth)))
 
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
@@ -330,12 +330,12 @@ class _Nets(C.Structure):
 
 
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
-            atomic=None, kingofthehill=None, racingkings=None, timeout_ms: int = 0,
+            atomic=None, kingofthehill=None, racingkings=None, threecheck=None, timeout_ms: int = 0,
             analysis_depth: int = 0, variant_analysis_depth: int = 0,
             analysis_plies: int | None = None) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
-    (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` theirs
+    (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
     (fnnue_backend_channel_netv): each batch is evaluated by its variant's net.
     `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316).
     `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth); `variant_analysis_depth`: 0 or 1
@@ -343,8 +343,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
-    if kingofthehill is not None or racingkings is not None:
-        given = [n for n in (net, crazyhouse, atomic, kingofthehill, racingkings) if n is not None]
+    if kingofthehill is not None or racingkings is not None or threecheck is not None:
+        given = [n for n in (net, crazyhouse, atomic, kingofthehill, racingkings, threecheck) if n is not None]
         arr = (C.c_void_p * len(given))(*[n._h.value for n in given])
         N.check(N.lib.fnnue_backend_channel_netv(arr, len(given), device, C.byref(init), C.byref(h)))
     elif crazyhouse is None and atomic is None:

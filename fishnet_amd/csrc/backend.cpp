@@ -238,9 +238,10 @@ inline void put_compact(fnnue_position_compact* r, int32_t psqt, int32_t positio
 
 // The net slot of a batch's variant (shakmaty Variant names, [ref]
 // src/api.rs:304; logger.rs:194-201): standard chess (EngineFlavor::Official
-// for analysis, queue.rs:530-539) and the four variants with a Fairy-Stockfish
+// for analysis, queue.rs:530-539) and the five variants with a Fairy-Stockfish
 // NNUE feature set here.  -1: a variant this backend does not evaluate
-// (antichess, horde, threeCheck).
+// (antichess, horde: kingless sides, which the king-block feature sets cannot
+// express).
 int kind_of(const char* v) {
   if (!v || !*v || !std::strcmp(v, "standard") || !std::strcmp(v, "chess960") || !std::strcmp(v, "fromPosition") ||
       !std::strcmp(v, "chess"))
@@ -249,6 +250,7 @@ int kind_of(const char* v) {
   if (!std::strcmp(v, "atomic")) return kVariantAtomic;
   if (!std::strcmp(v, "kingOfTheHill")) return kVariantKingOfTheHill;
   if (!std::strcmp(v, "racingKings")) return kVariantRacingKings;
+  if (!std::strcmp(v, "threeCheck")) return kVariantThreeCheck;
   return -1;
 }
 

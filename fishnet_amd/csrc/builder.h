@@ -21,7 +21,7 @@ __host__ __device__ inline int make_piece_d(int c, int pt) { return (c << 3) | p
 // side) in byte 2c + s of `cr`, 0xFF none (accessors in builder.hip).
 struct DBoard {
   uint64_t bc[2];   // by colour
-  uint64_t bt[7];   // by piece type (1..6), [0] unused
+  uint64_t bt[7];   // by piece type (1..6); [0]: threecheck's remaining checks (vboard.h checks_word), else 0
   uint32_t cr;
   int32_t ep;
   uint32_t stm;
@@ -41,7 +41,8 @@ constexpr uint32_t kBuildErrFen = 1, kBuildErrMove = 2, kBuildErrCount = 3;
 // ([ref] src/stockfish.rs:359-376 parses them to Score::Mate(0) / Cp(0)).
 constexpr uint8_t kFinalNoMoves = 1, kFinalCheck = 2, kFinalExtinct = 4;
 // The game was decided by the variant's own rule (kingofthehill: a king on the
-// hill; racingkings: one king on rank 8): `score mate 0`.  (The racingkings
+// hill; racingkings: one king on rank 8; threecheck: a check counter at 0):
+// `score mate 0`.  (The racingkings
 // draw with both kings on rank 8 is kFinalNoMoves alone.)
 constexpr uint8_t kFinalVariant = 8;
 // On a child only (move work, the variant one-ply search): the decided game is
@@ -193,8 +194,8 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
                                 size_t off_cap, hipStream_t s, BuilderScratch& ws, uint8_t* d_final = nullptr,
                                 uint16_t* d_moves = nullptr, uint8_t* d_end = nullptr, VChildrenBufs* own = nullptr);
 // children_count_device / children_write_device over a variant's boards
-// (vstate_bytes(variant) each: DBoard for kingofthehill / racingkings,
-// vb::VBoard otherwise), one thread per record.  Stream-ordered, no sync.
+// (vstate_bytes(variant) each: DBoard for kingofthehill / racingkings /
+// threecheck, vb::VBoard otherwise), one thread per record.  Stream-ordered, no sync.
 size_t vstate_bytes(int variant);
 hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off,
                                   hipStream_t s, BuilderScratch& ws);

@@ -398,7 +398,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.7: the two-ply search: fnnue_best2 / fnnue_best_replies[_device], fnnue_search2[_device],
 //      fnnue_search2_children, fnnue_backend_set_analysis_plies, fnnue_backend_go_pv,
 //      fnnue_backend_analysis_json_pv
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 7u; }
+// 3.8: FNNUE_VARIANT_THREECHECK accepted wherever a variant id is (check counters in the FEN, carried by
+//      every replay, host and device)
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 8u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -531,7 +533,11 @@ int fnnue_net_synthesize(uint64_t seed, uint32_t hd, uint32_t flags, void** buf,
 
 int fnnue_net_synthesize_variant(uint64_t seed, uint32_t hd, int variant, uint32_t flags, void** buf, size_t* len) {
   if (!buf || !len) return fail(FNNUE_E_ARG, "null argument");
-  if (!variant_net_id(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  // The ids of ABI 3.2, unchanged: threecheck has none of its own here, its
+  // nets are atomic-format bytes (synthesise with FNNUE_VARIANT_ATOMIC, load
+  // with FNNUE_VARIANT_THREECHECK).
+  if (!variant_net_id(variant) || variant == kVariantThreeCheck)
+    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
   if (!hd_supported(hd)) return fail(FNNUE_E_ARCH, "unsupported hd");
   try {
     Net n;
@@ -1562,7 +1568,7 @@ namespace {
 
 // The net a one-ply search of `variant` needs: fnnue_search1* a chess net,
 // fnnue_vsearch1* one whose feature set and game-over records are the
-// variant's (its own net; the atomic net also for kingofthehill, racingkings).
+// variant's (its own net; the atomic net also for kingofthehill, racingkings, threecheck).
 int search1_arch(const fnnue_ctx* ctx, int variant) {
   if (variant == kVariantChess)
     return ctx->variant == kVariantChess ? (int)FNNUE_OK : fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");

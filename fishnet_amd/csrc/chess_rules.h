@@ -1,7 +1,7 @@
 // chess_rules.h — chess on bitboards for the device (DBoard, builder.h) and
 // the chess rule set of the wave replay (replay_wave.h): what builder.hip's
-// kernels run, and what vbuilder.hip derives the kingofthehill / racingkings
-// rule set from (chess moves, so the lane-parallel chain fits them).
+// kernels run, and what vbuilder.hip derives the kingofthehill / racingkings /
+// threecheck rule sets from (chess moves, so the lane-parallel chain fits them).
 //
 // Everything lives in an unnamed namespace: each including file gets its own
 // force-inlined copy.
@@ -174,11 +174,15 @@ __device__ __forceinline__ void do_move(DBoard& b, const DMove& m) {
 // net.h kVariant* whose moves are chess moves).  kingofthehill: a king on d4,
 // e4, d5 or e5.  racingkings: a king on rank 8, unless it is white's alone
 // with black to move and black's king has a rank-8 neighbour square that
-// holds no black piece and that white does not attack.
+// holds no black piece and that white does not attack.  threecheck: a check
+// counter at 0 (DBoard::bt[0]: white's remaining checks | black's << 8).
 template <int V>
 __device__ __forceinline__ bool plain_over(const DBoard& b) {
   if constexpr (V == kVariantKingOfTheHill) {
     return (b.bt[KING] & 0x0000001818000000ull) != 0;
+  } else if constexpr (V == kVariantThreeCheck) {
+    const uint32_t w = (uint32_t)b.bt[0];
+    return !(w & 0xFFu) || !(w & 0xFF00u);
   } else if constexpr (V == kVariantRacingKings) {
     constexpr uint64_t kRank8 = 0xFF00000000000000ull;
     const uint64_t goal = b.bt[KING] & kRank8;
@@ -193,6 +197,24 @@ __device__ __forceinline__ bool plain_over(const DBoard& b) {
     return !catch_up;
   } else {
     return false;
+  }
+}
+
+// Does the side to move's king stand attacked (the move that led to b gave
+// check)?
+__device__ __forceinline__ bool in_check(const DBoard& b) {
+  const int k = king_sq(b, b.stm);
+  return k >= 0 && attacked(b, k, b.stm ^ 1, b.bc[0] | b.bc[1]);
+}
+
+// do_move under variant V's rules: threecheck takes one off the mover's
+// counter (never below 0) when the move gives check.
+template <int V>
+__device__ __forceinline__ void do_move_v(DBoard& b, const DMove& m) {
+  do_move(b, m);
+  if constexpr (V == kVariantThreeCheck) {
+    const int sh = 8 * (int)(b.stm ^ 1);  // the mover's byte
+    if (((b.bt[0] >> sh) & 0xFFu) && in_check(b)) b.bt[0] -= 1ull << sh;
   }
 }
 

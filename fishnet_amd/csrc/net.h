@@ -25,11 +25,13 @@ constexpr uint32_t kFtHashBaseVariants = 0x5F234CB8u;  // HalfKAv2::HashValue
 constexpr int kVariantChess = 0, kVariantCrazyhouse = 1, kVariantAtomic = 2;
 // The board-only feature set of atomic under other rules (no explosions).
 constexpr int kVariantKingOfTheHill = 3, kVariantRacingKings = 4;
-constexpr int kVariants = 5;
+// Chess with check counters carried along the game (not net inputs).
+constexpr int kVariantThreeCheck = 5;
+constexpr int kVariants = 6;
 constexpr bool variant_known(int v) { return v >= kVariantChess && v < kVariants; }
-// Board-only feature set (704 rows per king square): atomic and the two above.
+// Board-only feature set (704 rows per king square): atomic and the three above.
 constexpr bool variant_board_only(int v) {
-  return v == kVariantAtomic || v == kVariantKingOfTheHill || v == kVariantRacingKings;
+  return v == kVariantAtomic || v == kVariantKingOfTheHill || v == kVariantRacingKings || v == kVariantThreeCheck;
 }
 // A position with one king is a finished game's record, answered (0, 0):
 // atomic alone (an exploded king); everywhere else it is an invalid position.
@@ -40,6 +42,7 @@ constexpr const char* variant_name(int v) {
          : v == kVariantAtomic             ? "atomic"
          : v == kVariantKingOfTheHill      ? "kingofthehill"
          : v == kVariantRacingKings        ? "racingkings"
+         : v == kVariantThreeCheck         ? "threecheck"
                                            : "unknown";
 }
 constexpr int kVBoardRows = 704, kVHandSlots = 16, kVHandRows = 2 * 5 * kVHandSlots;

@@ -1,5 +1,5 @@
-// vboard.h — crazyhouse, atomic, king-of-the-hill and racing-kings rules on
-// bitboards, one source for the host
+// vboard.h — crazyhouse, atomic, king-of-the-hill, racing-kings and three-check
+// rules on bitboards, one source for the host
 // (fnnue_game_vpositions, fnnue_vperft) and the device batch builder
 // (vbuilder.hip): FEN with holdings and promoted marks, legal moves including
 // drops, do_move with pockets (crazyhouse) or explosions (atomic), packing to
@@ -32,6 +32,14 @@
 //    rank-8 neighbour square not occupied by a black piece and not attacked
 //    by white (shakmaty's RacingKings::is_variant_end: it does not ask
 //    whether that step is otherwise legal).  Both kings there: a draw.
+//  * threecheck: chess; each colour has a counter of remaining checks (3 at
+//    the start; the FEN carries them, parse_checks).  A move that leaves the
+//    other king attacked takes one off the mover's counter; a position with a
+//    counter at 0 is over (that colour has won) and has no legal move.  Only
+//    the mover's counter can reach 0 by a move, so after it the side to move
+//    has lost; a root FEN may also give the side to move's own counter as 0
+//    (it has already won: the racingkings precedent, variant_won).  The
+//    counters are not part of fnnue_vpos.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +56,7 @@ namespace vb {
 
 constexpr int kCrazyhouse = FNNUE_VARIANT_CRAZYHOUSE, kAtomic = FNNUE_VARIANT_ATOMIC;
 constexpr int kKingOfTheHill = FNNUE_VARIANT_KINGOFTHEHILL, kRacingKings = FNNUE_VARIANT_RACINGKINGS;
+constexpr int kThreeCheck = FNNUE_VARIANT_THREECHECK;
 constexpr uint64_t kHill = 0x0000001818000000ull;  // d4 e4 d5 e5
 constexpr int PAWN = 1, KNIGHT = 2, BISHOP = 3, ROOK = 4, QUEEN = 5, KING = 6;
 constexpr uint64_t kNotA = 0xFEFEFEFEFEFEFEFEull, kNotH = 0x7F7F7F7F7F7F7F7Full;
@@ -56,13 +65,13 @@ constexpr uint64_t kRank1 = 0xFFull, kRank8 = 0xFF00000000000000ull;
 
 struct VBoard {
   uint64_t bc[2];     // by colour
-  uint64_t bt[7];     // by piece type 1..6
+  uint64_t bt[7];     // by piece type 1..6; bt[0]: threecheck's remaining checks, white | black << 8 (else 0)
   uint64_t promoted;  // crazyhouse: promoted pieces (go to the pocket as pawns)
   uint64_t pocket[2]; // pockets: byte t - 1 of pocket[c] = colour c's pieces of type t (P N B R Q)
   int8_t cr[2][2];    // castling rook squares [colour][0 king side, 1 queen side], -1 none
   int8_t ep;          // en-passant target square or -1
   uint8_t stm;
-  uint8_t variant;    // kCrazyhouse / kAtomic / kKingOfTheHill / kRacingKings
+  uint8_t variant;    // kCrazyhouse / kAtomic / kKingOfTheHill / kRacingKings / kThreeCheck
   uint8_t c960;       // castling needs Chess960 (king-takes-rook) notation
 };
 
@@ -150,6 +159,28 @@ FNNUE_HD void cr_clear(VBoard& b, int c) {
 
 FNNUE_HD uint64_t occupied(const VBoard& b) { return b.bc[0] | b.bc[1]; }
 
+// Is this variant id threecheck?  On the host only: the device replays
+// threecheck games on DBoard boards (chess_rules.h, vbuilder.hip PlainRules),
+// so no VBoard there is one, and the crazyhouse / atomic kernels keep the code
+// they had before the variant existed.
+FNNUE_HD bool is_three_check(int variant) {
+#ifdef __HIP_DEVICE_COMPILE__
+  (void)variant;
+  return false;
+#else
+  return variant == kThreeCheck;
+#endif
+}
+
+// threecheck: the checks colour c may still give (the word VBoard / DBoard
+// keep in bt[0]: white | black << 8).
+FNNUE_HD int checks_left(uint64_t word, int c) { return (int)((word >> (8 * c)) & 255u); }
+FNNUE_HD uint64_t checks_word(int white, int black) { return (uint64_t)white | (uint64_t)black << 8; }
+// The word after colour c gave a check: one fewer, never below 0.
+FNNUE_HD uint64_t checks_spend(uint64_t word, int c) {
+  return checks_left(word, c) ? word - (1ull << (8 * c)) : word;
+}
+
 FNNUE_HD int type_at(const VBoard& b, uint64_t m) {  // 0: empty
   int t = 0;
   for (int k = 1; k <= KING; ++k) t = (b.bt[k] & m) ? k : t;
@@ -203,10 +234,11 @@ FNNUE_HD bool king_danger(const VBoard& b, int s, int us, uint64_t occ) {
 }
 
 // Has the game ended by the variant's own rule (kingofthehill: a king on the
-// hill; racingkings: a king on rank 8, unless black may still catch up)?  No
-// move is legal in such a position.
+// hill; racingkings: a king on rank 8, unless black may still catch up;
+// threecheck: a counter at 0)?  No move is legal in such a position.
 FNNUE_HD bool variant_over(const VBoard& b) {
   if (b.variant == kKingOfTheHill) return (b.bt[KING] & kHill) != 0;
+  if (is_three_check(b.variant)) return !checks_left(b.bt[0], 0) || !checks_left(b.bt[0], 1);
   if (b.variant != kRacingKings) return false;
   const uint64_t goal = b.bt[KING] & kRank8;
   if (!goal) return false;
@@ -220,13 +252,16 @@ FNNUE_HD bool variant_over(const VBoard& b) {
 }
 // In a position variant_over() ended: has the side to move lost (false: a
 // racingkings draw with both kings on rank 8, or the side to move's own king
-// alone on rank 8 — white's after black missed its catch-up move)?
+// alone on rank 8 — white's after black missed its catch-up move; or a
+// threecheck root whose side to move's own counter is 0)?
 FNNUE_HD bool variant_lost(const VBoard& b) {
   if (b.variant == kKingOfTheHill) return true;
+  if (is_three_check(b.variant)) return !checks_left(b.bt[0], b.stm ^ 1);
   const uint64_t goal = b.bt[KING] & kRank8;
   return !(goal & colour(b, b.stm));
 }
 FNNUE_HD bool variant_won(const VBoard& b) {
+  if (is_three_check(b.variant)) return !checks_left(b.bt[0], b.stm) && checks_left(b.bt[0], b.stm ^ 1);
   if (b.variant != kRacingKings) return false;
   const uint64_t goal = b.bt[KING] & kRank8;
   return (goal & colour(b, b.stm)) && !(goal & colour(b, b.stm ^ 1));
@@ -282,9 +317,12 @@ FNNUE_HD void do_move(VBoard& b, const VMove& m) {
       if (r >= 0 && piece_at(b, r) != mkpc(c, ROOK)) b.cr[c][side] = -1;
     }
   }
-  (void)them;
   b.ep = (int8_t)new_ep;
   b.stm = (uint8_t)(us ^ 1);
+  if (is_three_check(b.variant)) {  // a check given: one off the mover's counter
+    const int kt = king_sq(b, them);
+    if (kt >= 0 && attacked(b, kt, us, occupied(b))) b.bt[0] = checks_spend(b.bt[0], us);
+  }
 }
 
 FNNUE_HD bool legal_after(const VBoard& before, const VBoard& after) {
@@ -455,7 +493,8 @@ __host__ __device__ void for_each_legal(const VBoard& b, F&& f, uint64_t from_ma
 // Game-end flags of a position (builder.h kFinal*): no legal move (bit 0),
 // the side to move's king attacked (bit 1), its king exploded (bit 2, atomic),
 // the game decided by the variant's own rule (bit 3: kingofthehill,
-// racingkings; not for the racingkings draw with both kings on rank 8).
+// racingkings, threecheck; not for the racingkings draw with both kings on
+// rank 8).
 FNNUE_HD uint8_t end_flags(const VBoard& b, bool any) {
   const int us = b.stm, k = king_sq(b, us);
   const bool check = k >= 0 && king_danger(b, k, us, occupied(b));
@@ -511,10 +550,45 @@ FNNUE_HD int piece_type_of(char ch) {
   }
 }
 
+// threecheck's counters from a FEN's fields after the en-passant square (the
+// fifth field on), in either form shakmaty reads: "3+3" as the fifth field,
+// the checks remaining, white then black; or a last field "+w+b", the checks
+// given (remaining = 3 - given).  Neither: 3+3.  false: both forms, a digit
+// outside 0..3, any other field with a '+' in it, or both counters 0.
+FNNUE_HD bool parse_checks(const char* text, uint32_t p, uint32_t end, uint64_t& word) {
+  int white = 3, black = 3, forms = 0;
+  uint32_t st;
+  for (int field = 4;; ++field) {
+    const int len = next_token(text, p, end, st);
+    if (len == 0) break;
+    bool plus = false;
+    for (int i = 0; i < len; ++i) plus = plus || text[st + i] == '+';
+    if (!plus) continue;
+    uint32_t q = p, st2;
+    const bool last = next_token(text, q, end, st2) == 0;
+    int a, b;
+    if (len == 3 && text[st + 1] == '+' && field == 4) {
+      a = text[st] - '0';
+      b = text[st + 2] - '0';
+    } else if (len == 4 && text[st] == '+' && text[st + 2] == '+' && last) {
+      a = 3 - (text[st + 1] - '0');
+      b = 3 - (text[st + 3] - '0');
+    } else {
+      return false;
+    }
+    if (a < 0 || a > 3 || b < 0 || b > 3 || ++forms > 1) return false;
+    white = a;
+    black = b;
+  }
+  word = checks_word(white, black);
+  return white || black;
+}
+
 // FEN of a variant position: placement (a '~' after a piece marks it
 // promoted), crazyhouse holdings as "[...]" after the placement or as a ninth
 // placement field ("/..."), then side to move, castling (KQkq, Shredder or
-// X-FEN), en passant.  Returns false on malformed input.
+// X-FEN), en passant; threecheck: the check counters (parse_checks).  Returns
+// false on malformed input.
 FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant, VBoard& b) {
   for (int i = 0; i < 2; ++i) b.bc[i] = 0;
   for (int i = 0; i < 7; ++i) b.bt[i] = 0;
@@ -530,9 +604,10 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
   if (len == 0) return false;
   int r = 7, f = 0, last = -1;
   bool holdings = false;
-  // kingofthehill / racingkings FENs are plain chess FENs (no holdings, no
-  // promoted marks): what the chess parser of the device builder accepts
-  const bool plain = variant == kKingOfTheHill || variant == kRacingKings;
+  // kingofthehill / racingkings / threecheck FENs are plain chess FENs (no
+  // holdings, no promoted marks): what the chess parser of the device builder
+  // accepts
+  const bool plain = variant == kKingOfTheHill || variant == kRacingKings || is_three_check(variant);
   for (uint32_t i = st; i < st + (uint32_t)len; ++i) {
     const char ch = text[i];
     if (holdings) {
@@ -628,6 +703,7 @@ FNNUE_HD bool parse_fen(const char* text, uint32_t p, uint32_t end, int variant,
   const int elen = next_token(text, p, end, est);
   if (elen == 2 && text[est] >= 'a' && text[est] <= 'h' && text[est + 1] >= '1' && text[est + 1] <= '8')
     b.ep = (int8_t)((text[est + 1] - '1') * 8 + (text[est] - 'a'));
+  if (is_three_check(variant) && !parse_checks(text, p, end, b.bt[0])) return false;
   return true;
 }
 

@@ -1,5 +1,5 @@
 // vbuilder.hip — device batch builder for Fairy-Stockfish variants
-// (crazyhouse, atomic, kingofthehill, racingkings): the variant half of
+// (crazyhouse, atomic, kingofthehill, racingkings, threecheck): the variant half of
 // IncomingBatch::from_acquired
 // ([ref] src/queue.rs:524-552 with body.variant != Standard, routed to the
 // MultiVariant engine at :530-539; variants from src/assets.rs:384-391).
@@ -13,11 +13,14 @@
 // (fnnue_build_vchildren) one thread per record for the children with their
 // move codes and game-end flags.
 //
-// kingofthehill and racingkings play chess moves (no drops, no explosions), so
-// they replay on the chess rule set's lane-parallel chain (chess_rules.h
-// ChessRules::lane_chain) with their own legality and end of the game
-// (PlainRules below), on DBoard boards; the host runs the same rules from
-// vboard.h, and the tests hold the two to each other record for record.
+// kingofthehill, racingkings and threecheck play chess moves (no drops, no
+// explosions), so they replay on the chess rule set's lane-parallel chain
+// (chess_rules.h ChessRules::lane_chain) with their own legality and end of
+// the game (PlainRules below), on DBoard boards; the host runs the same rules
+// from vboard.h, and the tests hold the two to each other record for record.
+// threecheck's counters ride on that chain too: lane j sees on its own
+// snapshot whether move j gave check, and every ply's counters follow from one
+// ballot (PlainRules::lane_chain).
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -321,17 +324,89 @@ struct VariantRules {
   __device__ static uint8_t end_flags(const vb::VBoard& b, bool any) { return vb::end_flags(b, any); }
 };
 
-// kingofthehill / racingkings (V): the chess rule set with
+// kingofthehill / racingkings / threecheck (V): the chess rule set with
 //  * fnnue_vpos records (the chess record, empty pockets),
 //  * vboard.h's FEN acceptance for them (racingkings: no pawns, no castling
-//    rights) and match_uci's token rules (promotion letters in either case),
+//    rights; threecheck: the check counters) and match_uci's token rules
+//    (promotion letters in either case),
 //  * the variant's legality: nothing is legal in a finished position, and no
 //    racingkings move gives check,
 //  * the variant's game-end flags.
-// Scalars, Win, window, lane_chain, fix, advance and board_from are ChessRules'.
+// Scalars, Win, window, advance and (but for threecheck) lane_chain, fix and
+// board_from are ChessRules'.
+//
+// threecheck's counters (DBoard::bt[0], vboard.h checks_word) travel along the
+// replay in the scalars' c960 word, above its bit 0: c960 | counters << 8.
+// That word becomes the third the chain collects per lane (kVary = 3), so
+// check() hands every lane the counters before and after its move like the
+// en-passant square; board_from splits it into DBoard::c960 and bt[0].
+//
+// The counters of a window's 64 plies need no serial pass.  After the chess
+// chain has written the window's snapshots, lane j turns its own (the board
+// after move j) into bitboards and asks whether the mover attacks the other
+// king: one ballot.  Colours alternate, so colour c's moves are the lanes of
+// one parity, and its counter after move j is the value carried into the
+// window minus the popcount of the ballot over that parity's lanes up to j,
+// never below 0 (vb::checks_spend).  The chain is exact up to the window's
+// first illegal move (ChessRules::lane_chain), and lane j's count reads
+// lanes <= j only: every ply up to the first failing one has the host's
+// counters, so the first ply that finds a counter at 0 before it (verify:
+// plain_over) is the host's, and nothing after a failing ply is used.
 template <int V>
 struct PlainRules : ChessRules {
   using Pos = fnnue_vpos;
+  static constexpr bool kCounts = V == kVariantThreeCheck;
+  static constexpr int kVary = kCounts ? 3 : ChessRules::kVary;
+  __device__ static Scalars scalars(const DBoard& b) {
+    Scalars s = ChessRules::scalars(b);
+    if constexpr (kCounts) s.c960 |= (uint32_t)b.bt[0] << 8;
+    return s;
+  }
+  __device__ static DBoard board_from(const uint32_t (&w)[16], const Scalars& sc) {
+    DBoard b = ChessRules::board_from(w, sc);
+    if constexpr (kCounts) {
+      b.c960 = sc.c960 & 1u;
+      b.bt[0] = sc.c960 >> 8;
+    }
+    return b;
+  }
+  __device__ static void fix(Scalars& s, const Scalars& s0, const Win& w, uint32_t j, bool after) {
+    const uint32_t word = s.c960;  // threecheck: this ply's own, collected along the chain
+    ChessRules::fix(s, s0, w, j, after);
+    if constexpr (kCounts) s.c960 = word;
+  }
+  __device__ static uint32_t lane_chain(Scalars& sc, uint32_t& sqv, uint32_t myc, uint32_t k, const Win& w,
+                                        uint32_t (*SNAP)[16], int lane, uint32_t& mvw, uint32_t (&scw)[kVary]) {
+    if constexpr (!kCounts) {
+      return ChessRules::lane_chain(sc, sqv, myc, k, w, SNAP, lane, mvw, scw);
+    } else {
+      const uint32_t word = sc.c960, stm0 = sc.stm;
+      sc.c960 = word & 1u;
+      uint32_t epw[ChessRules::kVary];
+      const uint32_t kplay = ChessRules::lane_chain(sc, sqv, myc, k, w, SNAP, lane, mvw, epw);
+      // did move j give check?  the board after it, from lane j's own snapshot
+      bool gives = false;
+      if ((uint32_t)lane < kplay) {
+        uint32_t wa[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) wa[i] = SNAP[lane + 1][i];
+        const DBoard a = ChessRules::board_from(wa, sc);  // the squares; the scalars are not read
+        const int mover = (int)(stm0 ^ ((uint32_t)lane & 1u)), kt = king_sq(a, mover ^ 1);
+        gives = kt >= 0 && attacked(a, kt, mover, a.bc[0] | a.bc[1]);
+      }
+      const uint64_t g = __ballot(gives);
+      const uint64_t upto = lane == 63 ? ~0ull : (2ull << lane) - 1;  // moves 0..j
+      const uint64_t white = stm0 == WHITE ? 0x5555555555555555ull : 0xAAAAAAAAAAAAAAAAull;  // white's moves
+      const int w0 = (int)((word >> 8) & 0xFFu), b0 = (int)((word >> 16) & 0xFFu);
+      const int wl = max(w0 - __popcll(g & white & upto), 0), bl = max(b0 - __popcll(g & ~white & upto), 0);
+      const uint32_t mine = (word & 1u) | (uint32_t)wl << 8 | (uint32_t)bl << 16;
+      scw[0] = epw[0];
+      scw[1] = 0;  // the side to move: fix() derives it
+      scw[2] = mine;
+      sc.c960 = kplay ? replay::lane_value(mine, (int)kplay - 1) : word;
+      return kplay;
+    }
+  }
   __device__ static fnnue_vpos widen(const fnnue_pos& p) {
     uint32_t q[12];
     memcpy(q, &p, sizeof(p));
@@ -349,6 +424,11 @@ struct PlainRules : ChessRules {
   }
   __device__ static uint32_t start_fen_len(int) { return V == kVariantRacingKings ? 39 : 56; }
   __device__ static DBoard start_board(int) {
+    if constexpr (V == kVariantThreeCheck) {
+      DBoard b = ChessRules::start_board(0);
+      b.bt[0] = vb::checks_word(3, 3);
+      return b;
+    }
     if constexpr (V != kVariantRacingKings) return ChessRules::start_board(0);
     DBoard b;
     b.bc[WHITE] = 0xF0F0ull;
@@ -370,6 +450,11 @@ struct PlainRules : ChessRules {
     if (V == kVariantRacingKings && (b.bt[PAWN] || b.cr != 0xFFFFFFFFu)) return false;
     // vboard.h takes an en-passant square only while it is empty
     if (b.ep >= 0 && (((b.bc[0] | b.bc[1]) >> b.ep) & 1)) b.ep = -1;
+    if constexpr (kCounts) {  // the fields after the en-passant square
+      uint32_t st;
+      for (int i = 0; i < 4; ++i) vb::next_token(t, p, e, st);
+      if (!vb::parse_checks(t, p, e, b.bt[0])) return false;
+    }
     return true;
   }
   __device__ static uint32_t encode(const char* c, int len) {
@@ -543,7 +628,7 @@ __global__ __launch_bounds__(64) void pwrite_children_record_kernel(
     uint32_t k = 0;
     for_each_legal<V>(b, [&](const DMove& m) -> bool {
       if (++k < j) return true;
-      do_move(c, m);
+      do_move_v<V>(c, m);  // threecheck: with the counters, which the child's flags read
       mv = pmove_code(b, m);
       return false;
     });
@@ -584,6 +669,9 @@ hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n,
     else if (variant == kVariantRacingKings)
       hipLaunchKernelGGL(pcount_children_kernel<kVariantRacingKings>, grid, dim3(bs), 0, s,
                          static_cast<const DBoard*>(d_states), n, d_cnt);
+    else if (variant == kVariantThreeCheck)
+      hipLaunchKernelGGL(pcount_children_kernel<kVariantThreeCheck>, grid, dim3(bs), 0, s,
+                         static_cast<const DBoard*>(d_states), n, d_cnt);
     else
       hipLaunchKernelGGL(vcount_children_kernel, grid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(d_states), n,
                          d_cnt);
@@ -603,20 +691,26 @@ hipError_t vchildren_write_device(int variant, const void* d_states, uint32_t n,
   else if (variant == kVariantRacingKings)
     hipLaunchKernelGGL(pwrite_children_record_kernel<kVariantRacingKings>, grid, dim3(bs), 0, s,
                        static_cast<const DBoard*>(d_states), n, d_off, total, d_out, d_moves, d_end);
+  else if (variant == kVariantThreeCheck)
+    hipLaunchKernelGGL(pwrite_children_record_kernel<kVariantThreeCheck>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, d_out, d_moves, d_end);
   else
     hipLaunchKernelGGL(vwrite_children_record_kernel, grid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(d_states),
                        n, d_off, total, d_out, d_moves, d_end);
   return hipGetLastError();
 }
 
-size_t vstate_bytes(int variant) {
-  return variant == kVariantKingOfTheHill || variant == kVariantRacingKings ? sizeof(DBoard) : sizeof(vb::VBoard);
+// The variants that replay on DBoard boards (PlainRules).
+static bool plain_variant(int variant) {
+  return variant == kVariantKingOfTheHill || variant == kVariantRacingKings || variant == kVariantThreeCheck;
 }
+
+size_t vstate_bytes(int variant) { return plain_variant(variant) ? sizeof(DBoard) : sizeof(vb::VBoard); }
 
 hipError_t replay_vgames_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                 const uint32_t* d_ply_off, uint32_t ngames, fnnue_vpos* d_out, void* d_states,
                                 uint8_t* d_final, uint32_t* d_err, hipStream_t s) {
-  // d_states: DBoard for kingofthehill / racingkings, vb::VBoard otherwise
+  // d_states: DBoard for kingofthehill / racingkings / threecheck, vb::VBoard otherwise
   if (variant == kVariantKingOfTheHill)
     return replay::launch_replay<PlainRules<kVariantKingOfTheHill>>(variant, d_text, d_fen_off, d_mv_off, ngames,
                                                                     d_ply_off, d_out, static_cast<DBoard*>(d_states),
@@ -625,6 +719,10 @@ hipError_t replay_vgames_device(int variant, const char* d_text, const uint32_t*
     return replay::launch_replay<PlainRules<kVariantRacingKings>>(variant, d_text, d_fen_off, d_mv_off, ngames,
                                                                   d_ply_off, d_out, static_cast<DBoard*>(d_states),
                                                                   d_err, d_final, s);
+  if (variant == kVariantThreeCheck)
+    return replay::launch_replay<PlainRules<kVariantThreeCheck>>(variant, d_text, d_fen_off, d_mv_off, ngames,
+                                                                 d_ply_off, d_out, static_cast<DBoard*>(d_states),
+                                                                 d_err, d_final, s);
   return replay::launch_replay<VariantRules>(variant, d_text, d_fen_off, d_mv_off, ngames, d_ply_off, d_out,
                                              static_cast<vb::VBoard*>(d_states), d_err, d_final, s);
 }
@@ -641,8 +739,7 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
   hipError_t e;
   uint32_t *plies = nullptr, *ply_off = nullptr, *err = nullptr, *cnt = nullptr, *coff = nullptr;
   void* states = nullptr;
-  const bool plain = variant == kVariantKingOfTheHill || variant == kVariantRacingKings;
-  const size_t state_bytes = plain ? sizeof(DBoard) : sizeof(vb::VBoard);
+  const size_t state_bytes = vstate_bytes(variant);
   using W = BuilderScratch;
   if ((e = ws.get(W::kPlies, (size_t)(ngames + 1) * 4, (void**)&plies)) != hipSuccess) return fail(e);
   if ((e = ws.get(W::kPlyOff, (size_t)(ngames + 1) * 4, (void**)&ply_off)) != hipSuccess) return fail(e);
@@ -723,6 +820,9 @@ BuildResult build_vbatch_device(int variant, const char* d_text, const uint32_t*
                              static_cast<const DBoard*>(states), total_plies, coff, d_out);
         else if (variant == kVariantRacingKings)
           hipLaunchKernelGGL(pwrite_children_kernel<kVariantRacingKings>, cgrid, dim3(bs), 0, s,
+                             static_cast<const DBoard*>(states), total_plies, coff, d_out);
+        else if (variant == kVariantThreeCheck)
+          hipLaunchKernelGGL(pwrite_children_kernel<kVariantThreeCheck>, cgrid, dim3(bs), 0, s,
                              static_cast<const DBoard*>(states), total_plies, coff, d_out);
         else
           hipLaunchKernelGGL(vwrite_children_kernel, cgrid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(states),

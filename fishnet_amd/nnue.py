@@ -40,7 +40,8 @@ class Net:
     @classmethod
     def load_variant(cls, path: str, variant: int) -> "Net":
         """A Fairy-Stockfish variant net (VARIANT_CRAZYHOUSE / VARIANT_ATOMIC /
-        VARIANT_KINGOFTHEHILL / VARIANT_RACINGKINGS; the last three share one file format)."""
+        VARIANT_KINGOFTHEHILL / VARIANT_RACINGKINGS / VARIANT_THREECHECK; the last four share one
+        file format)."""
         h = C.c_void_p()
         N.check(N.lib.fnnue_net_load_variant(path.encode(), variant, C.byref(h)))
         return cls(h.value)
@@ -178,7 +179,7 @@ def game_vchildren(variant: int, fen: str, moves: str | list[str]) -> tuple[np.n
 
 
 END_NO_MOVES, END_CHECK, END_EXTINCT = 1, 2, 4
-END_VARIANT = 8  # the side to move has lost by the variant's own rule (kingofthehill, racingkings)
+END_VARIANT = 8  # the game is decided by the variant's own rule (kingofthehill, racingkings, threecheck)
 END_WON = 0x40   # on a child of build_vchildren: its side to move has already won (the mover lost by playing it)
 
 

@@ -122,22 +122,33 @@ void fnnue_buffer_free(void *buf);
  * transformer hash is 0x5F234CB8 ^ 2*HD; widths 256, 512, 1024. */
 #define FNNUE_VARIANT_CHESS 0
 #define FNNUE_VARIANT_CRAZYHOUSE 1 /* 64 x (704 board + 160 hand) features */
-#define FNNUE_VARIANT_ATOMIC 2     /* 64 x 704 board features (also kingofthehill, racingkings) */
+#define FNNUE_VARIANT_ATOMIC 2     /* 64 x 704 board features (also kingofthehill, racingkings, threecheck) */
 /* The board-only feature set of atomic with the variant's own rules (no
  * explosions, one king per side always: a position without is
  * FNNUE_E_POSITION).  kingofthehill: chess, over with a king on d4 e4 d5 e5.
  * racingkings: start 8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1, no pawns and no
  * castling rights (such a FEN is FNNUE_E_FEN), no move gives check, over with
- * a king on rank 8 unless black may still catch up. */
+ * a king on rank 8 unless black may still catch up.
+ * threecheck (ABI 3.8): chess with a counter of remaining checks per colour, 3
+ * at the start; a move that leaves the other king attacked takes one off the
+ * mover's, and a position with a counter at 0 is over, won by that colour.  The
+ * counters travel in the FEN as "3+3" (remaining, white then black) between
+ * the en-passant square and the halfmove clock, or as a trailing "+w+b"
+ * (checks given); neither: 3+3; both, a digit outside 0..3, a malformed field
+ * or both counters 0: FNNUE_E_FEN.  The counters are no part of fnnue_vpos. */
 #define FNNUE_VARIANT_KINGOFTHEHILL 3
 #define FNNUE_VARIANT_RACINGKINGS 4
+#define FNNUE_VARIANT_THREECHECK 5
 int fnnue_net_load_variant(const char *path, int variant, fnnue_net **out);
 int fnnue_net_load_variant_mem(const void *buf, size_t len, int variant, fnnue_net **out);
 int fnnue_net_variant(const fnnue_net *net, int *variant);
+/* variant: FNNUE_VARIANT_CRAZYHOUSE .. _RACINGKINGS.  A threecheck net is
+ * atomic-format bytes loaded with FNNUE_VARIANT_THREECHECK; that id is
+ * FNNUE_E_ARG here, as every id above racingkings has been since ABI 3.2. */
 int fnnue_net_synthesize_variant(uint64_t seed, uint32_t hd, int variant, uint32_t flags, void **buf, size_t *len);
 /* FEN (crazyhouse holdings as "[PNbq]" after the placement or as a 9th
- * placement field; "~" promotion marks ignored; kingofthehill / racingkings:
- * plain chess FENs, holdings and marks refused) -> packed variant position. */
+ * placement field; "~" promotion marks ignored; kingofthehill / racingkings /
+ * threecheck: plain chess FENs, holdings and marks refused) -> packed variant position. */
 int fnnue_vpos_from_fen(int variant, const char *fen, fnnue_vpos *out);
 /* Test inputs: `count` seeded pseudo-legal random walks from the variant's
  * start position (captures go to the capturer's hand and drops come back out
@@ -149,8 +160,9 @@ int fnnue_random_vpositions(uint64_t seed, int variant, size_t count, uint32_t m
 /* Variant games (the expansion of IncomingBatch::from_acquired for the
  * variants the reference sends to Fairy-Stockfish, [ref] src/queue.rs:524-552,
  * :530-539): crazyhouse FENs with holdings / promoted marks and UCI moves with
- * drops ("P@e4"), atomic captures with explosions, kingofthehill and
- * racingkings games (no move after the game's end, no racingkings check);
+ * drops ("P@e4"), atomic captures with explosions, kingofthehill,
+ * racingkings and threecheck games (no move after the game's end, no
+ * racingkings check, the check counters carried along);
  * every move checked for legality in its variant (shakmaty's Uci::to_move).
  * Host replay: the root and the position after every move (n_moves + 1
  * records). */
@@ -335,7 +347,9 @@ int fnnue_game_children(const char *fen, const char *moves, fnnue_pos *out, size
  * legal move, the side to move's king attacked, its king exploded (atomic),
  * the side to move has lost by the variant's own rule (kingofthehill: the
  * other king on the hill; racingkings: one king on rank 8 — the racingkings
- * draw with both kings there is FNNUE_END_NO_MOVES alone).
+ * draw with both kings there is FNNUE_END_NO_MOVES alone; threecheck: a check
+ * counter at 0 — the mover's after its last check, so with FNNUE_END_CHECK; a
+ * root FEN whose side to move's own counter is 0 is over the same way, won).
  * A position without a legal move is where the engine answers `score mate 0`
  * (checkmate / explosion / variant loss) or `score cp 0` (stalemate, draw) with `bestmove (none)`
  * ([ref] src/stockfish.rs:359-376).  variant: FNNUE_VARIANT_* (host replay). */
@@ -520,8 +534,8 @@ int fnnue_search1_lines(fnnue_ctx *ctx, const char *text, size_t text_len, const
                         size_t *n_groups);
 
 /* ---- one-ply search for the Fairy-Stockfish variants (ABI 3.6) ----
- * crazyhouse, atomic, kingofthehill and racingkings, on a variant net's
- * context.
+ * crazyhouse, atomic, kingofthehill, racingkings and threecheck, on a variant
+ * net's context.
  *
  * A variant move code is a fnnue_move that can also spell a drop: from == to
  * (the drop square) with the promo field holding the dropped piece type 1..5
@@ -547,8 +561,8 @@ int fnnue_build_vchildren(fnnue_ctx *ctx, int variant, const char *text, size_t 
 /* fnnue_search1[_lines][_device] for a variant net's context: the same three
  * steps (fnnue_build_vchildren, fnnue_eval_vgroups STAR, the reduction) in the
  * context's scratch, the same capacity protocol.  `variant` must be one the
- * context's net evaluates (its own; an atomic net also kingofthehill and
- * racingkings): FNNUE_E_ARCH otherwise, and on a chess context.  A crazyhouse
+ * context's net evaluates (its own; an atomic net also kingofthehill,
+ * racingkings and threecheck): FNNUE_E_ARCH otherwise, and on a chess context.  A crazyhouse
  * ply may have more than FNNUE_MAX_CHILDREN children; k stays 1..218. */
 int fnnue_vsearch1_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
                           const uint32_t *d_moves_off, size_t ngames, fnnue_best *d_out, size_t cap, uint32_t *d_off,

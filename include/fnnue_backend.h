@@ -127,8 +127,8 @@ typedef struct {
 int fnnue_backend_channel_nets(const fnnue_backend_nets *nets, int device, const fnnue_backend_init *init,
                                fnnue_backend **out);
 /* Any set of nets, each going to the slot of its own variant
- * (fnnue_net_variant: chess, crazyhouse, atomic, kingofthehill, racingkings;
- * fnnue_backend_nets keeps its three members, its size being ABI).  n >= 1;
+ * (fnnue_net_variant: chess, crazyhouse, atomic, kingofthehill, racingkings,
+ * threecheck; fnnue_backend_nets keeps its three members, its size being ABI).  n >= 1;
  * two nets of one variant: FNNUE_E_ARG. */
 int fnnue_backend_channel_netv(const fnnue_net *const *nets, size_t n, int device, const fnnue_backend_init *init,
                                fnnue_backend **out);
@@ -154,7 +154,7 @@ void fnnue_backend_free(fnnue_backend *b);
  * child's, negated.  A ply without a legal move is answered exactly as at
  * depth 0 (mate 0 / cp 0, depth 0, nodes 0, no move); skipped ids stay
  * skipped; move work is unchanged.  Variant batches (crazyhouse, atomic,
- * kingOfTheHill, racingKings) are not affected by this setter: they are
+ * kingOfTheHill, racingKings, threeCheck) are not affected by this setter: they are
  * answered at depth 0 exactly as on a depth-0 channel unless
  * fnnue_backend_set_variant_analysis_depth (below) says otherwise.
  * Pieces are cut at a 32nd of FNNUE_BACKEND_PIECE_PLIES, so that a piece's
@@ -173,10 +173,10 @@ void fnnue_backend_free(fnnue_backend *b);
 int fnnue_backend_set_analysis_depth(fnnue_backend *b, int depth);
 /* The same for the variant nets (ABI 3.6), independent of the chess setting:
  * 0 (the default) or 1, anything else FNNUE_E_ARG.  At 1 every non-skipped ply
- * of a crazyhouse, atomic, kingOfTheHill or racingKings analysis batch is
+ * of a crazyhouse, atomic, kingOfTheHill, racingKings or threeCheck analysis batch is
  * answered with a one-ply search on the device under the variant's rules
  * (fnnue_vsearch1's steps), by the rule of move work: a child that ends the
- * game for the opponent (checkmate, an exploded king, the variant's rule) is
+ * game for the opponent (checkmate, an exploded king, the variant's rule: threeCheck's last check) is
  * Mate(1); a child the mover has lost by playing (racingKings: black fails to
  * catch up) is chosen only when there is nothing else, Mate(-1); otherwise
  * Cp(value * 100 / normalize_to_pawn).  depth 1, nodes = the children,

@@ -22,7 +22,7 @@ phase).  FNNUE_CHILDREN_IMPL=ply|record in
 the environment picks the children kernel (A/B).  `--actor` adds the engine
 actor at depth 0 and 1 for 1, 64 and 1024 lichess-shaped batches; with
 `--lines` also go_lines() at depth 1 with multipv = K for every K <= 5.
-`--variant crazyhouse,atomic,kingOfTheHill,racingKings` (this tree's library
+`--variant crazyhouse,atomic,kingOfTheHill,racingKings,threeCheck` (this tree's library
 only) times the variant one-ply search instead, per variant on N random legal
 games of the variant (L ~ U[0, 160] plies): fnnue_build_vbatch_device(CHILDREN)
 (`build`), fnnue_build_vchildren_device (`children`), fnnue_eval_vgroups_device
@@ -273,7 +273,7 @@ def actor_lines(a, multipvs=()):
 
 
 VSTART = {"crazyhouse": START.replace(" w", "[] w"), "atomic": START, "kingOfTheHill": START,
-          "racingKings": "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1"}
+          "racingKings": "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1", "threeCheck": START}
 
 
 def variant_games(F, variant, name, seed, count, lo, hi):
@@ -293,11 +293,13 @@ def variant_main(a):
     import fishnet_amd as F
     from fishnet_amd import backend as B
     ids = {"crazyhouse": F.VARIANT_CRAZYHOUSE, "atomic": F.VARIANT_ATOMIC, "kingOfTheHill": F.VARIANT_KINGOFTHEHILL,
-           "racingKings": F.VARIANT_RACINGKINGS}
+           "racingKings": F.VARIANT_RACINGKINGS, "threeCheck": F.VARIANT_THREECHECK}
     dev = torch.device("cuda", 0)
     for name in a.variant.split(","):
         v = ids[name]
-        net = F.Net.from_bytes_variant(F.synthesize_variant_net(5 + v, a.hd, v), v)
+        # a threeCheck net is atomic-format bytes under its own id
+        fmt = F.VARIANT_ATOMIC if v == F.VARIANT_THREECHECK else v
+        net = F.Net.from_bytes_variant(F.synthesize_variant_net(5 + v, a.hd, fmt), v)
         ev = F.Evaluator(net, 0)
         games = variant_games(F, v, name, a.seed, a.games, 0, 160)
         text, fen_off, mv_off = F.pack_games(games)
