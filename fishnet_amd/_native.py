@@ -111,6 +111,7 @@ SIGNATURES = {
     "fnnue_perft_device": ([_vp, C.c_char_p, _i32, _P(_u64)], _i32),
     "fnnue_random_game": ([_u64, C.c_char_p, _u32, C.c_char_p, _sz, _P(_sz)], _i32),
     "fnnue_multi_create": ([_vp, _P(_i32), _i32, _P(_vp)], _i32),
+    "fnnue_multi_create_replicas": ([_vp, _P(_i32), _i32, _P(_vp)], _i32),
     "fnnue_multi_free": ([_vp], None),
     "fnnue_multi_size": ([_vp, _P(_i32)], _i32),
     "fnnue_multi_ctx": ([_vp, _i32, _P(_vp)], _i32),

@@ -229,10 +229,10 @@ int name_invalid_v(int rc, const fnnue_vpos* pos, size_t n, int variant, size_t 
 
 // After the device latched FNNUE_E_POSITION: the message names the first
 // invalid position (the host rule is the device's, valid_host_pos).
-int name_invalid(int rc, const fnnue_pos* pos, size_t n) {
+int name_invalid(int rc, const fnnue_pos* pos, size_t n, size_t base) {
   if (rc != FNNUE_E_POSITION) return rc;
   for (size_t i = 0; i < n; ++i)
-    if (!valid_host_pos(pos[i])) return fail(FNNUE_E_POSITION, "invalid position at index " + std::to_string(i));
+    if (!valid_host_pos(pos[i])) return fail(FNNUE_E_POSITION, "invalid position at index " + std::to_string(base + i));
   return rc;
 }
 
@@ -400,7 +400,8 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      fnnue_backend_analysis_json_pv
 // 3.8: FNNUE_VARIANT_THREECHECK accepted wherever a variant id is (check counters in the FEN, carried by
 //      every replay, host and device)
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 8u; }
+// 3.9: fnnue_multi_create_replicas; the fnnue_multi_* messages name the shard and the caller's index
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 9u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -786,6 +787,13 @@ int eval_groups_device(fnnue_ctx* ctx, const void* d_pos, size_t pos_bytes, cons
   int rc = order_workspace(ctx, s);
   if (rc) return rc;
   WorkspaceUse use{ctx, s};
+  if (npos == 0) {
+    // Groups without a position (every group empty; fnnue_multi_eval_groups
+    // hands such a shard out when empty groups sit on a cut): nothing to
+    // evaluate, and no plan to launch.  The offsets are still checked.
+    HIP_TRY(launch_group_span(d_off, (uint32_t)ngroups, 0, nullptr, true, ctx->err, s), "group_span launch");
+    return FNNUE_OK;
+  }
   const bool sliced = ctx->ft_impl != FNNUE_FT_GATHER || ctx->variant != kVariantChess;
   if (sliced && ((rc = ensure_seg(ctx)) || (rc = ensure_span(ctx, npos)))) return rc;
   if (sliced && npos <= seg_small_plan_max()) {
@@ -977,7 +985,12 @@ int fnnue_eval_vpositions_device(fnnue_ctx* ctx, const fnnue_vpos* d_pos, size_t
   return FNNUE_OK;
 }
 
-int fnnue_eval_vpositions(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32_t* psqt, int32_t* positional) {
+}  // extern "C"
+
+namespace fnnue::detail {
+
+int eval_vpositions_at(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32_t* psqt, int32_t* positional,
+                       size_t base) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
   if (ctx->variant == kVariantChess) return fail(FNNUE_E_ARCH, "chess net: use fnnue_eval_positions*");
   if (n == 0) return FNNUE_OK;
@@ -995,9 +1008,17 @@ int fnnue_eval_vpositions(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32
     HIP_TRY(hipMemcpyAsync(psqt + b, ctx->d_psqt, m * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
     HIP_TRY(hipMemcpyAsync(positional + b, ctx->d_positional, m * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
     HIP_TRY(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if ((rc = latched(ctx))) return name_invalid_v(rc, pos + b, m, ctx->variant, b);
+    if ((rc = latched(ctx))) return name_invalid_v(rc, pos + b, m, ctx->variant, base + b);
   }
   return FNNUE_OK;
+}
+
+}  // namespace fnnue::detail
+
+extern "C" {
+
+int fnnue_eval_vpositions(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32_t* psqt, int32_t* positional) {
+  return eval_vpositions_at(ctx, pos, n, psqt, positional, 0);
 }
 
 int fnnue_ctx_check(fnnue_ctx* ctx) {
@@ -1012,7 +1033,12 @@ int fnnue_ctx_check(fnnue_ctx* ctx) {
   return latched(ctx);
 }
 
-int fnnue_eval_positions(fnnue_ctx* ctx, const fnnue_pos* pos, size_t n, int32_t* psqt, int32_t* positional) {
+}  // extern "C"
+
+namespace fnnue::detail {
+
+int eval_positions_at(fnnue_ctx* ctx, const fnnue_pos* pos, size_t n, int32_t* psqt, int32_t* positional,
+                      size_t base) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
   if (n == 0) return FNNUE_OK;
   if (!pos || !psqt || !positional) return fail(FNNUE_E_ARG, "null buffer");
@@ -1031,13 +1057,13 @@ int fnnue_eval_positions(fnnue_ctx* ctx, const fnnue_pos* pos, size_t n, int32_t
     HIP_TRY(hipMemcpyAsync(positional + b, ctx->d_positional, m * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
     HIP_TRY(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     rc = latched(ctx);
-    if (rc) return name_invalid(rc, pos, n);
+    if (rc) return name_invalid(rc, pos, n, base);
   }
   return FNNUE_OK;
 }
 
-int fnnue_eval_groups(fnnue_ctx* ctx, const fnnue_pos* pos, size_t npos, const uint32_t* off, size_t ngroups,
-                      int mode, int32_t* psqt, int32_t* positional) {
+int eval_groups_at(fnnue_ctx* ctx, const fnnue_pos* pos, size_t npos, const uint32_t* off, size_t ngroups, int mode,
+                   int32_t* psqt, int32_t* positional, size_t base) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
   if (mode != FNNUE_GROUP_CHAIN && mode != FNNUE_GROUP_STAR) return fail(FNNUE_E_ARG, "bad group mode");
   if (ngroups == 0) return npos == 0 ? FNNUE_OK : fail(FNNUE_E_ARG, "positions without groups");
@@ -1058,7 +1084,20 @@ int fnnue_eval_groups(fnnue_ctx* ctx, const fnnue_pos* pos, size_t npos, const u
   HIP_TRY(hipMemcpyAsync(psqt, ctx->d_psqt, npos * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
   HIP_TRY(hipMemcpyAsync(positional, ctx->d_positional, npos * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
   HIP_TRY(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-  return name_invalid(latched(ctx), pos, npos);
+  return name_invalid(latched(ctx), pos, npos, base);
+}
+
+}  // namespace fnnue::detail
+
+extern "C" {
+
+int fnnue_eval_positions(fnnue_ctx* ctx, const fnnue_pos* pos, size_t n, int32_t* psqt, int32_t* positional) {
+  return eval_positions_at(ctx, pos, n, psqt, positional, 0);
+}
+
+int fnnue_eval_groups(fnnue_ctx* ctx, const fnnue_pos* pos, size_t npos, const uint32_t* off, size_t ngroups,
+                      int mode, int32_t* psqt, int32_t* positional) {
+  return eval_groups_at(ctx, pos, npos, off, ngroups, mode, psqt, positional, 0);
 }
 
 int fnnue_eval_vgroups(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t npos, const uint32_t* off, size_t ngroups,

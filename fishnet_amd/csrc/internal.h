@@ -102,12 +102,21 @@ int ensure_builder_input(fnnue_ctx* c, size_t bytes);
 int latched(fnnue_ctx* c);
 // The device's position rule on the host (one king per side, <= 32 pieces, valid codes, stm 0/1).
 bool valid_host_pos(const fnnue_pos& p);
-// After FNNUE_E_POSITION latched: names the first invalid position.
-int name_invalid(int rc, const fnnue_pos* pos, size_t n);
+// After FNNUE_E_POSITION latched: names the first invalid position, as index
+// base + i (base: where pos[0] sits in the caller's buffer).
+int name_invalid(int rc, const fnnue_pos* pos, size_t n, size_t base);
 // A variant position as the device sees it: 0 invalid, 1 evaluated, 2 atomic
 // game over (one king exploded: result (0, 0), not an error).
 int host_vpos_state(const fnnue_vpos& p, int variant);
 int name_invalid_v(int rc, const fnnue_vpos* pos, size_t n, int variant, size_t base);
+// fnnue_eval_positions / fnnue_eval_groups / fnnue_eval_vpositions on a shard
+// that starts at index `base` of the caller's buffer: the same calls (they
+// pass base 0), an invalid position is named by base + its index in `pos`.
+int eval_positions_at(fnnue_ctx* ctx, const fnnue_pos* pos, size_t n, int32_t* psqt, int32_t* positional, size_t base);
+int eval_groups_at(fnnue_ctx* ctx, const fnnue_pos* pos, size_t npos, const uint32_t* off, size_t ngroups, int mode,
+                   int32_t* psqt, int32_t* positional, size_t base);
+int eval_vpositions_at(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32_t* psqt, int32_t* positional,
+                       size_t base);
 // fnnue_game_end for standard chess (board.cpp rules).
 int game_end_chess(const char* fen, const char* moves, int* flags);
 

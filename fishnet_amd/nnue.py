@@ -755,12 +755,16 @@ def _streams(vals):
 class MultiEvaluator:
     """Several GPUs from one process (fnnue_multi_*): the net is RCCL-broadcast
     from devices[0]; batches are sharded without a data-path collective.  The
-    reference's one-engine-per-core parallelism ([ref] src/main.rs:156-170)."""
+    reference's one-engine-per-core parallelism ([ref] src/main.rs:156-170).
+    replicas=True (fnnue_multi_create_replicas): an ordinal may repeat and the
+    image is copied to every context without RCCL, several contexts possibly
+    on one GPU; every call after creation is the same."""
 
-    def __init__(self, net: Net, devices):
+    def __init__(self, net: Net, devices, replicas: bool = False):
         devs = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
-        N.check(N.lib.fnnue_multi_create(net.handle, devs, len(devices), C.byref(h)))
+        create = N.lib.fnnue_multi_create_replicas if replicas else N.lib.fnnue_multi_create
+        N.check(create(net.handle, devs, len(devices), C.byref(h)))
         self._h = h
         self.devices = list(devices)
 

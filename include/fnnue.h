@@ -246,11 +246,25 @@ void fnnue_ctx_free(fnnue_ctx *ctx);
  * its disjoint slice of the caller's buffers.  Same results as one context. */
 typedef struct fnnue_multi fnnue_multi;
 int fnnue_multi_create(const fnnue_net *net, const int *devices, int ndev, fnnue_multi **out);
+/* Several contexts, each with its own stream, workspace and staging, possibly
+ * on one GPU (ABI 3.9): as fnnue_multi_create, except that an ordinal may
+ * repeat and no RCCL communicator is made — the image is packed once on the
+ * host and copied to every context.  Everything after creation is the same
+ * fnnue_multi: the same sharding, host threads, streams and error reports, so
+ * this is also how the sharding path is tested on a one-GPU box
+ * (devices = {0, 0, 0}).  Contexts that share a GPU share its time: no
+ * speed-up is implied. */
+int fnnue_multi_create_replicas(const fnnue_net *net, const int *devices, int ndev, fnnue_multi **out);
 void fnnue_multi_free(fnnue_multi *m);
 int fnnue_multi_size(const fnnue_multi *m, int *ndev);
 /* The context of device i (borrowed; owned by m). */
 int fnnue_multi_ctx(fnnue_multi *m, int i, fnnue_ctx **ctx);
-/* Host buffers, synchronous: one host thread per device (H2D, eval, D2H). */
+/* Host buffers, synchronous: one host thread per device (H2D, eval, D2H).
+ * An error is the first failing shard's, its message prefixed with
+ * "shard i (device d): " (i: the context's place in the multi); an invalid
+ * position is named by its index in the caller's buffer, e.g.
+ * "shard 2 (device 0): invalid position at index 2041".  The device-buffer
+ * calls and fnnue_multi_sync use the same prefix. */
 int fnnue_multi_eval_positions(fnnue_multi *m, const fnnue_pos *pos, size_t n, int32_t *psqt, int32_t *positional);
 int fnnue_multi_eval_groups(fnnue_multi *m, const fnnue_pos *pos, size_t npos, const uint32_t *off, size_t ngroups,
                             int mode, int32_t *psqt, int32_t *positional);

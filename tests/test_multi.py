@@ -1,8 +1,9 @@
 """Multi-GPU sharding: the partitioner (host), the fnnue_multi ABI's argument
 checks (no GPU needed), a world_size-2 gloo run of the per-rank sharding of
 grouped batches, and (-m gpu) the one-process multi-device path at ndev = 1
-against the oracle (one MI355X per box; ndev > 1 runs in the driver's
-8-GPU bench)."""
+against the oracle (one MI355X per box; two and three shards on one GPU run
+in tests/test_gpu_multi_shards.py, distinct devices in the driver's 8-GPU
+bench)."""
 import os
 import socket
 
@@ -55,6 +56,90 @@ def test_multi_create_argument_checks():
     # no GPU here -> FNNUE_E_DEVICE; with one, the duplicate device -> FNNUE_E_ARG
     assert rc in (-1, -5) and not h.value
     assert N.lib.fnnue_multi_sync(None) == -1
+
+
+def test_multi_create_replicas_argument_checks():
+    """fnnue_multi_create_replicas: the argument checks of fnnue_multi_create,
+    except that an ordinal may repeat; without a GPU FNNUE_E_DEVICE, *out null."""
+    import ctypes as C
+    net = F.Net.from_bytes(net_bytes(7, 128, 0))
+    create = N.lib.fnnue_multi_create_replicas
+    devs = (C.c_int * 3)(0, 0, 0)
+    for ndev in (0, -1):
+        h = C.c_void_p(1)
+        assert create(net.handle, devs, ndev, C.byref(h)) == -1 and not h.value
+    h = C.c_void_p(1)
+    assert create(None, devs, 3, C.byref(h)) == -1 and not h.value  # null net
+    h = C.c_void_p(1)
+    assert create(net.handle, None, 3, C.byref(h)) == -1 and not h.value  # null devices
+    assert create(net.handle, devs, 3, None) == -1  # null out
+    if F.device_count() == 0:
+        h = C.c_void_p(1)
+        assert create(net.handle, devs, 3, C.byref(h)) == -5 and not h.value
+        assert "no HIP device" in N.lib.fnnue_last_error().decode()
+        with pytest.raises(F.FnnueError) as e:
+            F.MultiEvaluator(net, [0, 0], replicas=True)
+        assert e.value.name == "FNNUE_E_DEVICE"
+    assert N.lib.fnnue_abi_version() >= (3 << 16) | 9
+    assert N.lib.fnnue_abi_version() >> 16 == 3
+
+
+def built_offset_tables(nd: int, unit: int = 6) -> dict:
+    """Group-offset tables whose cuts over nd parts are awkward (also used on
+    real shards by tests/test_gpu_multi_shards.py).  `unit` scales the sizes;
+    the totals are multiples of nd * 2, so the ideal split points k / nd of the
+    positions are whole numbers and can be hit exactly."""
+    u = unit
+    tables = {
+        # fewer groups than parts: some parts must stay empty
+        "one_group": [5 * u],
+        "fewer_groups": [3 * u + 1] * (nd - 1),
+        # empty groups at the start, at the end and exactly at every ideal split
+        "empty_at_cuts": [0, 0] + sum(([u, u - 1, 1, 0, 0] for _ in range(nd)), []) + [0],
+        # one group with more than half of all positions (no even split exists)
+        "one_big_first": [9 * u, u, 1, u - 1, 2],
+        "one_big_middle": [2, u, 1, 9 * u, u - 1, 3],
+        "one_big_last": [u, 2, 1, u, 9 * u],
+        # every group one position: every index is a boundary
+        "singles": [1] * (4 * u * nd + 1),
+        "only_empty": [0, 0, 0],
+    }
+    return {k: np.concatenate([[0], np.cumsum(v)]).astype(np.uint32) for k, v in tables.items()}
+
+
+@pytest.mark.parametrize("parts", [1, 2, 3, 4, 8])
+def test_partition_groups_built_tables(parts):
+    """On the built tables: cuts are monotone, sit on group boundaries (by
+    construction: they index off), each is the boundary nearest to its share
+    of the positions among those not before the previous cut (so a cut that
+    is one group off fails), and parts > ngroups leaves only empty extras."""
+    for nd in (2, 3):
+        for name, off in built_offset_tables(nd).items():
+            ngroups, total = len(off) - 1, int(off[-1])
+            cut = F.partition_groups(off, parts).astype(np.int64)
+            assert len(cut) == parts + 1 and cut[0] == 0 and cut[-1] == ngroups, name
+            assert np.all(np.diff(cut) >= 0), name
+            o = off.astype(np.int64)
+            for k in range(1, parts):
+                target = total * k // parts
+                best = np.abs(o[cut[k - 1]:] - target).min()
+                assert abs(o[cut[k]] - target) == best, (name, k, cut.tolist())
+            sizes = np.diff(o[cut])
+            assert sizes.sum() == total and np.all(sizes >= 0), name
+            nonempty_groups = int(np.count_nonzero(np.diff(o)))
+            assert np.count_nonzero(sizes) <= nonempty_groups, name
+            if parts > ngroups:  # the extra parts hold no group at all
+                assert np.count_nonzero(np.diff(cut)) <= ngroups, name
+                assert np.count_nonzero(np.diff(cut) == 0) >= parts - ngroups, name
+    # the ideal split is hit exactly where a boundary sits on it, empty groups or not
+    off = built_offset_tables(3)["empty_at_cuts"]
+    cut = F.partition_groups(off, 3)
+    assert [int(off[c]) for c in cut] == [0, 12, 24, 36]
+    off = built_offset_tables(2)["singles"]
+    assert list(F.partition_groups(off, 2)) == [0, 24, 49]
+    # one group larger than an even share: it lands whole in one part
+    off = built_offset_tables(2)["one_big_middle"]
+    assert list(F.partition_groups(off, 2)) == [0, 3, 6]  # 9 | 54 + 5 + 3: boundary 9 is nearer to 35 than 63
 
 
 def _free_port():
