@@ -88,12 +88,19 @@ def _wrap16(a: np.ndarray) -> np.ndarray:
     return ((a + 32768) % 65536) - 32768
 
 
+def _wrap32(a: int) -> int:
+    """int32 wraparound, as the oracle's explicit uint32 arithmetic gives it."""
+    return ((a + (1 << 31)) & M32) - (1 << 31)
+
+
 def _trunc_div(a: int, b: int) -> int:
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b > 0) else -q
 
 
-def evaluate(net: RefNet, board: list[int] | np.ndarray, stm: int) -> tuple[int, int]:
+def evaluate(net: RefNet, board: list[int] | np.ndarray, stm: int, trace: bool = False):
+    """(psqt, positional); with trace also the fc_0 sums y[16] and the fc_1 sums z[32] (int64),
+    taken from the same pass."""
     board = [int(x) for x in board]
     wk, bk = board.index(6), board.index(14)
     pieces = [(s, pc) for s, pc in enumerate(board) if pc]
@@ -103,7 +110,8 @@ def evaluate(net: RefNet, board: list[int] | np.ndarray, stm: int) -> tuple[int,
         acc.append(_wrap16(net.bias + net.w[idx].sum(axis=0)))
         psq.append(net.psqt[idx].sum(axis=0))
     bucket = (len(pieces) - 1) // 4
-    psqt = _trunc_div(int(psq[stm][bucket] - psq[1 - stm][bucket]), 2)
+    # PSQT accumulators and their difference wrap mod 2^32 (a no-op while the sums stay inside int32)
+    psqt = _trunc_div(_wrap32(_wrap32(int(psq[stm][bucket])) - _wrap32(int(psq[1 - stm][bucket]))), 2)
     half = net.hd // 2
     xs = []
     for persp in (stm, 1 - stm):
@@ -120,4 +128,6 @@ def evaluate(net: RefNet, board: list[int] | np.ndarray, stm: int) -> tuple[int,
     x2 = np.clip(z >> 6, 0, 127)
     out = b2 + int(w2 @ x2)
     fwd = _trunc_div(int(y[15]) * 9600, 8128)
+    if trace:
+        return psqt, out + fwd, y, z
     return psqt, out + fwd
