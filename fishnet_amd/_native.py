@@ -183,6 +183,14 @@ SIGNATURES = {
     "fnnue_backend_set_analysis_plies": ([_vp, _i32], _i32),
     "fnnue_backend_go_pv": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32], _i32),
     "fnnue_backend_analysis_json_pv": ([_vp, _sz, _vp, C.c_char_p, _sz, _P(_sz)], _i32),
+    # the two-ply search for the variants (ABI 3.10)
+    "fnnue_vbest_replies_device": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp], _i32),
+    "fnnue_vbest_replies": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp], _i32),
+    "fnnue_vsearch2_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_vsearch2": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_vsearch2_children": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz,
+                                 _P(_sz), _P(_sz), _P(_sz)], _i32),
+    "fnnue_backend_set_variant_analysis_plies": ([_vp, _i32], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

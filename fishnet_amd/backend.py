@@ -21,7 +21,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _native as N
-from .nnue import move_uci
+from .nnue import vmove_uci
 
 WORK_ANALYSIS, WORK_MOVE = 0, 1
 SCORE_CP, SCORE_MATE = 0, 1
@@ -238,7 +238,7 @@ class GpuEvalStub:
                     r.positional, r.depth, r.nodes, r.time_ms, r.nps, r.best_move.decode() or None,
                     matrix=bool(r.matrix)))
                 if with_reply and reply[k]:
-                    rows[-1].reply = move_uci(int(reply[k]))
+                    rows[-1].reply = vmove_uci(int(reply[k]))  # a chess code prints as move_uci prints it
                 if lines_cap is not None and loff[k + 1] > loff[k]:
                     rows[-1].lines = [
                         PvLine(Score("mate" if l.score_kind == SCORE_MATE else "cp", int(l.score)), l.move.decode(),
@@ -304,6 +304,11 @@ class GpuEvalStub:
         racingKings and threeCheck analysis batches (drops as "N@f3"); independent of set_analysis_depth."""
         N.check(N.lib.fnnue_backend_set_variant_analysis_depth(self._actor._h, int(depth)))
 
+    def set_variant_analysis_plies(self, plies: int) -> None:
+        """fnnue_backend_set_variant_analysis_plies: 0 and 1 as set_variant_analysis_depth, 2 = a two-ply
+        search per variant analysis ply under the variant's rules (the reply in go_pv's rows, drops included)."""
+        N.check(N.lib.fnnue_backend_set_variant_analysis_plies(self._actor._h, int(plies)))
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -332,7 +337,8 @@ class _Nets(C.Structure):
 def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse=None,
             atomic=None, kingofthehill=None, racingkings=None, threecheck=None, timeout_ms: int = 0,
             analysis_depth: int = 0, variant_analysis_depth: int = 0,
-            analysis_plies: int | None = None) -> tuple[GpuEvalStub, GpuEvalActor]:
+            analysis_plies: int | None = None,
+            variant_analysis_plies: int | None = None) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -340,7 +346,9 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     `timeout_ms`: the budget of each go() (0: 60 s, [ref] src/main.rs:316).
     `analysis_depth`: 0 or 1 (GpuEvalStub.set_analysis_depth); `variant_analysis_depth`: 0 or 1
     for the variant nets' batches (GpuEvalStub.set_variant_analysis_depth); `analysis_plies`: 0, 1 or 2
-    (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`)."""
+    (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`); `variant_analysis_plies`: 0, 1
+    or 2 for the variant nets' batches (GpuEvalStub.set_variant_analysis_plies; it takes the place of
+    `variant_analysis_depth`)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -361,14 +369,19 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_variant_analysis_depth(variant_analysis_depth)
     if analysis_plies is not None:
         stub.set_analysis_plies(analysis_plies)
+    if variant_analysis_plies is not None:
+        stub.set_variant_analysis_plies(variant_analysis_plies)
     return stub, actor
 
 
 def _move_code(uci: str | None) -> int:
-    """The fnnue_move code of a chess move's UCI text (0 for None / "")."""
+    """The fnnue_move code of a move's UCI text (0 for None / ""); a variant's drop "N@f3" is
+    from == to with the piece type in the promotion field (fnnue_vmove_uci)."""
     if not uci:
         return 0
     sq = lambda s: (ord(s[0]) - 97) | (int(s[1]) - 1) << 3
+    if uci[1] == "@":
+        return sq(uci[2:4]) | sq(uci[2:4]) << 6 | " PNBRQ".index(uci[0].upper()) << 12
     return sq(uci[0:2]) | sq(uci[2:4]) << 6 | (" pnbrq".index(uci[4]) if len(uci) > 4 else 0) << 12
 
 

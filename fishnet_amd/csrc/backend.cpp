@@ -37,7 +37,9 @@
 // and the variant's end flags, fnnue_eval_vgroups_device's STAR evaluation and
 // the same reduction, whose ranks know the variant flags.
 //
-// Analysis at two plies (fnnue_backend_set_analysis_plies(b, 2); chess nets):
+// Analysis at two plies (fnnue_backend_set_analysis_plies(b, 2) for the chess
+// nets, fnnue_backend_set_variant_analysis_plies(b, 2) for the variant nets,
+// over their boards, rules and ranks: vchild_states_device, launch_vbest_replies):
 // stage_search goes on behind the children's evaluation: the children's boards
 // as a dense array (child_states_device), their own children counted (a second
 // sizing read-back), expanded, evaluated as STAR groups and reduced to one
@@ -458,9 +460,10 @@ struct fnnue_backend {
   int analysis_depth = 0;
   int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
+  int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
-  bool depth1(int k) const { return (k == kVariantChess ? job_plies : variant_analysis_depth) >= 1; }
-  bool depth2(int k) const { return k == kVariantChess && job_plies == 2; }
+  bool depth1(int k) const { return (k == kVariantChess ? job_plies : vjob_plies) >= 1; }
+  bool depth2(int k) const { return (k == kVariantChess ? job_plies : vjob_plies) == 2; }
   size_t piece_plies = 524288;  // FNNUE_BACKEND_PIECE_PLIES
   bool any_order = true;         // FNNUE_BACKEND_ANY_ORDER=0: wait for the nets' pieces in net order
   size_t tail_plies = 0;         // FNNUE_BACKEND_TAIL_PLIES: a net's last piece cut to about this many
@@ -696,9 +699,12 @@ int fnnue_backend::plan(Job& j, int k) {
   // that read-back, so fewer and larger pieces measured faster (DESIGN.md
   // §4.16: 1024 crazyhouse batches in 33.1 / 17.4 / 13.4 ms at a 128th / 32nd
   // / 8th).
-  // At two plies a ply brings about a thousand grandchildren: a 1024th.
+  // At two plies a ply brings about a thousand grandchildren: a 1024th.  The
+  // variant nets' two-plies pieces are cut at a 256th: 64 crazyhouse batches in
+  // 59.7 / 46.3 / 38.1 / 33.8 ms at a 2048th / 1024th / 512th / 256th (DESIGN.md
+  // §4.18; a piece of 2048 crazyhouse plies holds about 4M grandchild records).
   const size_t cut_plies = !depth1(k)           ? piece_plies
-                           : depth2(k)          ? std::max<size_t>(16, piece_plies / 1024)
+                           : depth2(k)          ? std::max<size_t>(16, piece_plies / (k == kVariantChess ? 1024 : 256))
                            : k == kVariantChess ? std::max<size_t>(1024, piece_plies / 32)
                                                 : std::max<size_t>(256, piece_plies / 8);
   for (size_t i : W.games) {
@@ -939,14 +945,18 @@ int fnnue_backend::stage_search(int k, size_t pi) {
     if (int rc = W.kid_best.reserve((nkid + 1) * sizeof(fnnue_best))) return rc;
     fnnue_best* kb = W.kid_best.at<fnnue_best>(0);
     if (nkid) {
-      if (int rc = W.kid_states.reserve(nkid * sizeof(DBoard))) return rc;
+      if (int rc = W.kid_states.reserve(nkid * (chess ? sizeof(DBoard) : vstate_bytes(k)))) return rc;
       if (int rc = W.kid2_cnt.reserve((nkid + 1) * 4)) return rc;
       if (int rc = W.kid2_off.reserve((nkid + 1) * 4)) return rc;
-      DBoard* ks = W.kid_states.at<DBoard>(0);
+      void* ks = W.kid_states.at<char>(0);
       uint32_t* goff = W.kid2_off.at<uint32_t>(0);
-      HIP_TRY(child_states_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total, ks, nullptr, s),
+      HIP_TRY(chess ? child_states_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total,
+                                          static_cast<DBoard*>(ks), nullptr, s)
+                    : vchild_states_device(k, states, n, coff, (uint32_t)total, ks, nullptr, s),
               "child_states launch");
-      HIP_TRY(children_count_device(ks, (uint32_t)nkid, W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch),
+      HIP_TRY(chess ? children_count_device(static_cast<const DBoard*>(ks), (uint32_t)nkid,
+                                            W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch)
+                    : vchildren_count_device(k, ks, (uint32_t)nkid, W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch),
               "grandchildren count launch");
       HIP_TRY(hipMemcpyAsync(hs + 1, goff + nkid, 4, hipMemcpyDeviceToHost, s), "D2H(grandchildren count)");
       HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(grandchildren count)");
@@ -961,19 +971,28 @@ int fnnue_backend::stage_search(int k, size_t pi) {
       if (int rc = W.g_end.reserve(gtotal)) return rc;
       if (int rc = W.g_ps.reserve(gtotal * 4)) return rc;
       if (int rc = W.g_po.reserve(gtotal * 4)) return rc;
-      fnnue_pos* gp = W.g_pos.at<fnnue_pos>(0);
+      void* gp = W.g_pos.at<char>(0);
       uint16_t* gm = W.g_moves.at<uint16_t>(0);
       uint8_t* ge = W.g_end.at<uint8_t>(0);
       int32_t* gps = W.g_ps.at<int32_t>(0);
       int32_t* gpo = W.g_po.at<int32_t>(0);
-      HIP_TRY(children_write_device(ks, (uint32_t)nkid, goff, (uint32_t)gtotal, gp, gm, ge, s), "grandchildren launch");
-      if (int rc = fnnue_eval_groups_device(c, gp, goff, nkid, gtotal, FNNUE_GROUP_STAR, gps, gpo, s)) return rc;
+      HIP_TRY(chess ? children_write_device(static_cast<const DBoard*>(ks), (uint32_t)nkid, goff, (uint32_t)gtotal,
+                                            static_cast<fnnue_pos*>(gp), gm, ge, s)
+                    : vchildren_write_device(k, ks, (uint32_t)nkid, goff, (uint32_t)gtotal,
+                                             static_cast<fnnue_vpos*>(gp), gm, ge, s),
+              "grandchildren launch");
+      if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(gp), goff, nkid, gtotal,
+                                                    FNNUE_GROUP_STAR, gps, gpo, s)
+                         : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(gp), goff, nkid, gtotal,
+                                                     FNNUE_GROUP_STAR, gps, gpo, s))
+        return rc;
       HIP_TRY(launch_best_children_own(gps, gpo, ge, gm, goff, (uint32_t)nkid, (uint32_t)gtotal, kb, s),
               "best_children launch");
       P.searched += gtotal - nkid;
     }
-    HIP_TRY(launch_best_replies(ke, km, coff, n, (uint32_t)total, kb, nullptr,
-                                reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
+    // the variant nets: the variant ranks (FNNUE_END_WON children, every reply loses at once)
+    HIP_TRY((chess ? launch_best_replies : launch_vbest_replies)(ke, km, coff, n, (uint32_t)total, kb, nullptr,
+                                                                 reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
             "best_replies launch");
   } else {
     HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
@@ -1149,7 +1168,8 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           const fnnue_best2& B = gb[q];
           const bool skipped = sk && skip[b + q];
           const bool none = B.kind == FNNUE_BEST_NONE;
-          const bool mate = B.kind == FNNUE_BEST_MATE, mated = B.kind == FNNUE_BEST_MATED;
+          // mated: every move allows a mate in one, or (variants) loses at once
+          const bool mate = B.kind == FNNUE_BEST_MATE, mated = B.kind == FNNUE_BEST_MATED || B.kind == FNNUE_BEST_LOST;
           const uint8_t kind = none ? end_kind : mate || mated ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
           const int64_t score = none ? 0 : mate ? 1 : mated ? -1 : (int64_t)B.value * 100 / nrm;
           const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
@@ -1167,7 +1187,7 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
             continue;
           }
           put_response(r, response_head(q, 0, kind, depth, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
-          if (!none) (void)fnnue_move_uci(B.move, r->best_move);
+          if (!none) (void)(k == kVariantChess ? fnnue_move_uci(B.move, r->best_move) : fnnue_vmove_uci(B.move, r->best_move));
           if (j.reply && !none) j.reply[b + q] = B.reply;
         }
         if (j.cout) {
@@ -1412,6 +1432,7 @@ void fnnue_backend::run(Job& j) {
   fill_ms = wait_ms = 0;
   syncs = rebuilds = 0;
   job_plies = analysis_depth == 2 && j.lines ? 1 : analysis_depth;  // MultiPV is a one-ply search
+  vjob_plies = variant_analysis_depth == 2 && j.lines ? 1 : variant_analysis_depth;
   const size_t nb = j.nb;
   flen.resize(nb);
   mlen.resize(nb);
@@ -1899,6 +1920,15 @@ int fnnue_backend_set_variant_analysis_depth(fnnue_backend* b, int depth) {
   return FNNUE_OK;
 }
 
+int fnnue_backend_set_variant_analysis_plies(fnnue_backend* b, int plies) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (plies < 0 || plies > 2)
+    return fail(FNNUE_E_ARG, "variant analysis plies 0, 1 or 2, not " + std::to_string(plies));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->variant_analysis_depth = plies;
+  return FNNUE_OK;
+}
+
 int fnnue_backend_last_stats(fnnue_backend* b, fnnue_backend_stats* out) {
   if (!b || !out) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->stats_mu);
@@ -1934,7 +1964,8 @@ int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_lin
       if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';  // never from this library
     // the pv's second move (fnnue_backend_go_pv): only behind a first one
     char pv2[8] = {0};
-    if (reply && reply[i] && pv[0] && fnnue_move_uci(reply[i], pv2) != FNNUE_OK) pv2[0] = 0;
+    // a variant's reply may be a drop ("N@f3"); every chess code prints as fnnue_move_uci prints it
+    if (reply && reply[i] && pv[0] && fnnue_vmove_uci(reply[i], pv2) != FNNUE_OK) pv2[0] = 0;
     const size_t nl = line_off && r[i].matrix ? line_off[i + 1] - line_off[i] : 0;  // lines are rows of the matrix form
     if (nl) {
       // Matrix::set per line: row l is `depth` nulls and then the entry

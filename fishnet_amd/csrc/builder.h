@@ -161,6 +161,11 @@ hipError_t launch_child_counts(const uint32_t* d_off, uint32_t ngroups, uint32_t
 hipError_t launch_best_replies(const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups,
                                uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
                                fnnue_best2* d_out, hipStream_t s);
+// The same with the variant ranks (fnnue_vbest_replies_device): FNNUE_END_WON
+// children and children whose every reply loses at once.
+hipError_t launch_vbest_replies(const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups,
+                                uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                                fnnue_best2* d_out, hipStream_t s);
 // The k best children of every group as fnnue_line records: group g's slots are
 // [d_line_off[g], d_line_off[g + 1]), or [g * uniform_k, (g + 1) * uniform_k)
 // when d_line_off is null; nothing is written at or beyond lines_cap.
@@ -201,6 +206,11 @@ hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n,
                                   hipStream_t s, BuilderScratch& ws);
 hipError_t vchildren_write_device(int variant, const void* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
                                   fnnue_vpos* d_out, uint16_t* d_moves, uint8_t* d_end, hipStream_t s);
+// child_states_device over a variant's boards (vstate_bytes(variant) each, in
+// and out; a threecheck child carries its counters): child j of ply i is entry
+// d_off[i] - i + j - 1, total - n entries in all.  Stream-ordered, no sync.
+hipError_t vchild_states_device(int variant, const void* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                void* d_out, uint2* d_map, hipStream_t s);
 
 // Every ply of every game with offsets the caller already knows (ply_off:
 // ngames + 1 entries, ply_off[g + 1] - ply_off[g] = 1 + the game's move

@@ -401,7 +401,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.8: FNNUE_VARIANT_THREECHECK accepted wherever a variant id is (check counters in the FEN, carried by
 //      every replay, host and device)
 // 3.9: fnnue_multi_create_replicas; the fnnue_multi_* messages name the shard and the caller's index
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 9u; }
+// 3.10: the two-ply search for the variants: fnnue_vbest_replies[_device], fnnue_vsearch2[_device],
+//      fnnue_vsearch2_children, fnnue_backend_set_variant_analysis_plies
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 10u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1742,9 +1744,14 @@ int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint3
                       n_groups);
 }
 
-int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
-                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
-                              void* stream) {
+}  // extern "C"
+
+namespace {
+
+// fnnue_best_replies[_device] (vranks = false) and fnnue_vbest_replies[_device].
+int best_replies_device(fnnue_ctx* ctx, bool vranks, const uint8_t* d_end, const fnnue_move* d_moves,
+                        const uint32_t* d_off, size_t ngroups, size_t npos, const fnnue_best* d_child_best,
+                        fnnue_best2* d_out, void* stream) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
   if (ngroups == 0) return FNNUE_OK;
   if (!d_end || !d_off || !d_child_best || !d_out) return fail(FNNUE_E_ARG, "null buffer");
@@ -1760,13 +1767,14 @@ int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_
   HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidOff, (ngroups + 1) * 4, (void**)&base), "device allocation (scratch)");
   HIP_TRY(launch_child_counts(d_off, (uint32_t)ngroups, (uint32_t)npos, cnt, s), "child_counts launch");
   HIP_TRY(builder_exclusive_scan(cnt, base, (uint32_t)ngroups, s, ctx->bscratch), "scan");
-  HIP_TRY(launch_best_replies(d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_child_best, base, d_out, s),
+  HIP_TRY((vranks ? launch_vbest_replies : launch_best_replies)(d_end, d_moves, d_off, (uint32_t)ngroups,
+                                                                (uint32_t)npos, d_child_best, base, d_out, s),
           "best_replies launch");
   return FNNUE_OK;
 }
 
-int fnnue_best_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                       size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
+int best_replies_host(fnnue_ctx* ctx, bool vranks, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                      size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
   if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
   if (ngroups == 0) return FNNUE_OK;
   if (!off || !out || (npos && !end)) return fail(FNNUE_E_ARG, "null buffer");
@@ -1791,14 +1799,40 @@ int fnnue_best_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* mov
     if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
   }
   HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  const int rc = fnnue_best_replies_device(ctx, reinterpret_cast<uint8_t*>(d + o_end),
-                                           moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
-                                           reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
-                                           reinterpret_cast<fnnue_best*>(d), reinterpret_cast<fnnue_best2*>(d + o_out), s);
+  const int rc = best_replies_device(ctx, vranks, reinterpret_cast<uint8_t*>(d + o_end),
+                                     moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
+                                     reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
+                                     reinterpret_cast<fnnue_best*>(d), reinterpret_cast<fnnue_best2*>(d + o_out), s);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, d + o_out, ngroups * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return FNNUE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
+                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
+                              void* stream) {
+  return best_replies_device(ctx, false, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_out, stream);
+}
+
+int fnnue_best_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                       size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
+  return best_replies_host(ctx, false, end, moves, off, ngroups, npos, child_best, out);
+}
+
+int fnnue_vbest_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
+                               size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
+                               void* stream) {
+  return best_replies_device(ctx, true, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_out, stream);
+}
+
+int fnnue_vbest_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                        size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
+  return best_replies_host(ctx, true, end, moves, off, ngroups, npos, child_best, out);
 }
 
 }  // extern "C"
@@ -1853,17 +1887,36 @@ struct Search2Trace {
   }
 };
 
-// fnnue_search2_device; with d_child_best / d_child_map (child_cap entries
-// each) also the children's depth-1 records (fnnue_search2_children).
-int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+// The net a two-ply search of `variant` needs: fnnue_search2* (vcall = false) a
+// chess net, fnnue_vsearch2* fnnue_vsearch1's (never a chess context).
+int search2_arch(const fnnue_ctx* ctx, int variant, bool vcall) {
+  if (!vcall)
+    return ctx->variant == kVariantChess ? (int)FNNUE_OK : fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
+  if (ctx->variant == kVariantChess || variant == kVariantChess)
+    return fail(FNNUE_E_ARCH, "the variant two-ply search needs a variant net");
+  return search1_arch(ctx, variant);
+}
+
+// The variant entry points hand their counts back zeroed on every error path, a null context included.
+void zero_counts(size_t* n_out, size_t* n_groups, size_t* n_children) {
+  if (n_out) *n_out = 0;
+  if (n_groups) *n_groups = 0;
+  if (n_children) *n_children = 0;
+}
+
+// fnnue_search2_device (variant = chess) and fnnue_vsearch2_device; with
+// d_child_best / d_child_map (child_cap entries each) also the children's
+// depth-1 records (fnnue_[v]search2_children).
+int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
                    size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
                    fnnue_best* d_child_best, uint32_t* d_child_map, size_t child_cap, size_t* n_out, size_t* n_groups,
                    size_t* n_children, void* stream) {
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
   if (n_children) *n_children = 0;
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
+  if (int rc = search2_arch(ctx, variant, vcall)) return rc;
   if (ngames == 0) return FNNUE_OK;
+  const bool chess = variant == kVariantChess;
   DeviceGuard g(ctx->device);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   int rc = order_workspace(ctx, s);
@@ -1877,8 +1930,23 @@ int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   ChildrenBufs kids;
   kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
   size_t nrec = 0, nply = 0;
-  rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
-                    nullptr, nullptr, &nrec, &nply, s, &kids);
+  if (chess) {
+    rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
+                      nullptr, nullptr, &nrec, &nply, s, &kids);
+  } else {
+    VChildrenBufs vkids;
+    vkids.max_groups = kids.max_groups;
+    rc = build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
+                       &nrec, &nply, s, &vkids);
+    kids.off = vkids.off;
+    kids.moves = vkids.moves;
+    kids.end = vkids.end;
+    kids.ply_off = vkids.ply_off;
+  }
+  // the second reduction: the chess ranks, or the variants' (FNNUE_END_WON, every reply loses)
+  const auto reduce2 = chess ? launch_best_replies : launch_vbest_replies;
+  // a board of the variant: DBoard for chess, kingofthehill, racingkings and threecheck, vb::VBoard otherwise
+  const size_t state_bytes = chess ? sizeof(DBoard) : vstate_bytes(variant);
   *n_out = nply;
   *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
   if (rc) return rc;
@@ -1887,58 +1955,72 @@ int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   if (n_children) *n_children = nkid;
   if (n_children && (nkid > child_cap || (nkid && (!d_child_best || !d_child_map))))
     return fail(FNNUE_E_CAPACITY, "child buffers too small");
-  const DBoard* plies = static_cast<const DBoard*>(ws.p[W::kStates]);
-  DBoard* kid_states = nullptr;
+  const void* plies = ws.p[W::kStates];
+  char* kid_states = nullptr;
   uint32_t *kid_cnt = nullptr, *kid_off = nullptr, *spans = nullptr;
   fnnue_best* kid_best = nullptr;
-  HIP_TRY(ws.get(W::kKidStates, (nkid + 1) * sizeof(DBoard), (void**)&kid_states), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kKidStates, (nkid + 1) * state_bytes, (void**)&kid_states), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kKidCnt, (nkid + 1) * 4, (void**)&kid_cnt), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kKidOff, (nkid + 1) * 4, (void**)&kid_off), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kKidBest, (nkid + 1) * sizeof(fnnue_best), (void**)&kid_best), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kPlySpans, (nply + 1) * 8, (void**)&spans), "device allocation (search scratch)");
   if (nkid == 0) {  // every ply is a finished game's last
-    HIP_TRY(launch_best_replies(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr,
-                                d_out, s),
+    HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
             "best_replies launch");
     HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
     return FNNUE_OK;
   }
   trace.mark(Search2Trace::kChildStates);
-  HIP_TRY(child_states_device(plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kid_states,
-                              reinterpret_cast<uint2*>(d_child_map), s),
-          "child_states launch");
+  if (chess)
+    HIP_TRY(child_states_device(static_cast<const DBoard*>(plies), (uint32_t)nply, kids.off, (uint32_t)nrec,
+                                reinterpret_cast<DBoard*>(kid_states), reinterpret_cast<uint2*>(d_child_map), s),
+            "child_states launch");
+  else
+    HIP_TRY(vchild_states_device(variant, plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kid_states,
+                                 reinterpret_cast<uint2*>(d_child_map), s),
+            "child_states launch");
   // level 2 sizes: every child's records, and per ply where its children and their records start
   trace.mark(Search2Trace::kCount);
-  HIP_TRY(children_count_device(kid_states, (uint32_t)nkid, kid_cnt, kid_off, s, ws), "children count");
+  if (chess)
+    HIP_TRY(children_count_device(reinterpret_cast<DBoard*>(kid_states), (uint32_t)nkid, kid_cnt, kid_off, s, ws),
+            "children count");
+  else
+    HIP_TRY(vchildren_count_device(variant, kid_states, (uint32_t)nkid, kid_cnt, kid_off, s, ws), "children count");
   HIP_TRY(ply_spans_device(kids.off, kid_off, (uint32_t)nply, spans, spans + nply + 1, s), "ply_spans launch");
   std::vector<uint32_t> h((nply + 1) * 2);
   HIP_TRY(hipMemcpyAsync(h.data(), spans, h.size() * 4, hipMemcpyDeviceToHost, s), "D2H(sizes)");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   const uint32_t *first_kid = h.data(), *first_rec = h.data() + nply + 1;
-  // chunks of whole plies within the budget (one ply alone always fits); the
-  // differences are taken in 32 bits, as the device takes them, so a call whose
-  // grandchild records pass 2^32 in all still cuts and runs chunk by chunk
+  // chunks of whole plies within the budget; a ply larger than the budget (a
+  // crazyhouse ply has no fixed bound) is a chunk of its own.  One ply's records
+  // are the 32-bit difference of two offsets, as the device takes it (a ply's
+  // children times their children: far below 2^32); a chunk's are their sum in
+  // 64 bits, so a call whose grandchild records pass 2^32 in all still cuts
+  // right and runs chunk by chunk, and no chunk's count wraps (budget < 2^32).
   const size_t budget = search2_budget();
   std::vector<uint32_t> cuts{0};
   size_t max_rec = 0, max_kid = 0, all_rec = 0;
   for (size_t p = 0; p < nply;) {
     size_t q = p + 1;
-    while (q < nply && (uint32_t)(first_rec[q + 1] - first_rec[p]) <= budget &&
-           (size_t)(q + 1 - p) * kSearch2MinRecords <= 0xFFFFFFFFu)
+    uint64_t sum = (uint32_t)(first_rec[q] - first_rec[p]);
+    while (q < nply && sum + (uint32_t)(first_rec[q + 1] - first_rec[q]) <= budget) {
+      sum += (uint32_t)(first_rec[q + 1] - first_rec[q]);
       ++q;
-    max_rec = std::max<size_t>(max_rec, first_rec[q] - first_rec[p]);
-    all_rec += first_rec[q] - first_rec[p];
+    }
+    max_rec = std::max<size_t>(max_rec, sum);
+    all_rec += sum;
     max_kid = std::max<size_t>(max_kid, first_kid[q] - first_kid[p]);
     cuts.push_back((uint32_t)q);
     p = q;
   }
   uint32_t* ch_off = nullptr;
-  fnnue_pos* gpos = nullptr;
+  void* gpos = nullptr;
   uint16_t* gmoves = nullptr;
   uint8_t* gend = nullptr;
   int32_t *gps = nullptr, *gpo = nullptr;
   HIP_TRY(ws.get(W::kChunkOff, (max_kid + 1) * 4, (void**)&ch_off), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrand, max_rec * sizeof(fnnue_pos), (void**)&gpos), "device allocation (search scratch)");
+  HIP_TRY(ws.get(W::kGrand, max_rec * (chess ? sizeof(fnnue_pos) : sizeof(fnnue_vpos)), &gpos),
+          "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kGrandMoves, max_rec * 2, (void**)&gmoves), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kGrandEnd, max_rec, (void**)&gend), "device allocation (search scratch)");
   HIP_TRY(ws.get(W::kGrandPsqt, max_rec * 4, (void**)&gps), "device allocation (search scratch)");
@@ -1949,15 +2031,26 @@ int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
     if (nk == 0) continue;  // plies without a legal move
     trace.mark(Search2Trace::kExpand);
     HIP_TRY(rebase_offsets_device(kid_off + k0, nk + 1, ch_off, s), "rebase_offsets launch");
-    HIP_TRY(children_write_device(kid_states + k0, nk, ch_off, nr, gpos, gmoves, gend, s), "children write");
+    const char* chunk_states = kid_states + (size_t)k0 * state_bytes;
+    if (chess)
+      HIP_TRY(children_write_device(reinterpret_cast<const DBoard*>(chunk_states), nk, ch_off, nr,
+                                    static_cast<fnnue_pos*>(gpos), gmoves, gend, s),
+              "children write");
+    else
+      HIP_TRY(vchildren_write_device(variant, chunk_states, nk, ch_off, nr, static_cast<fnnue_vpos*>(gpos), gmoves,
+                                     gend, s),
+              "children write");
     trace.mark(Search2Trace::kEval);
-    if ((rc = fnnue_eval_groups_device(ctx, gpos, ch_off, nk, nr, FNNUE_GROUP_STAR, gps, gpo, s))) return rc;
+    rc = chess ? fnnue_eval_groups_device(ctx, static_cast<fnnue_pos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
+                                          gpo, s)
+               : fnnue_eval_vgroups_device(ctx, static_cast<fnnue_vpos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
+                                           gpo, s);
+    if (rc) return rc;
     trace.mark(Search2Trace::kReduce1);
     HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
   }
   trace.mark(Search2Trace::kReduce2);
-  HIP_TRY(launch_best_replies(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out,
-                              s),
+  HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
           "best_replies launch");
   trace.mark(Search2Trace::kPhases);
   trace.report(nply, nkid, all_rec, cuts.size() - 1);
@@ -1968,14 +2061,14 @@ int search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   return FNNUE_OK;
 }
 
-int search2_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
+int search2_host(fnnue_ctx* ctx, int variant, bool vcall, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
                  size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap, fnnue_best* child_best,
                  uint32_t* child_map, size_t child_cap, size_t* n_out, size_t* n_groups, size_t* n_children) {
   if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
     return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
   if (n_children) *n_children = 0;
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
+  if (int rc = search2_arch(ctx, variant, vcall)) return rc;
   if (ngames == 0) return FNNUE_OK;
   DeviceGuard g(ctx->device);
   char* d_text = nullptr;
@@ -1992,7 +2085,7 @@ int search2_host(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32
   if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
   char* d = static_cast<char*>(buf.p);
   hipStream_t s = ctx->stream;
-  rc = search2_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best2*>(d) : nullptr,
+  rc = search2_device(ctx, variant, vcall, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best2*>(d) : nullptr,
                       room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
                       room && kroom ? reinterpret_cast<fnnue_best*>(d + o_cb) : nullptr,
                       room && kroom ? reinterpret_cast<uint32_t*>(d + o_cm) : nullptr, room ? child_cap : 0, n_out,
@@ -2015,15 +2108,15 @@ extern "C" {
 int fnnue_search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
                          size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
                          size_t* n_groups, void* stream) {
-  return search2_device(ctx, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, nullptr, nullptr, 0,
-                        n_out, n_groups, nullptr, stream);
+  return search2_device(ctx, kVariantChess, false, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
+                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream);
 }
 
 int fnnue_search2(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
                   const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap,
                   size_t* n_out, size_t* n_groups) {
-  return search2_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr, nullptr, 0,
-                      n_out, n_groups, nullptr);
+  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
+                      nullptr, nullptr, 0, n_out, n_groups, nullptr);
 }
 
 int fnnue_search2_children(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
@@ -2031,8 +2124,34 @@ int fnnue_search2_children(fnnue_ctx* ctx, const char* text, size_t text_len, co
                            size_t off_cap, fnnue_best* child_best, uint32_t* child_map, size_t child_cap,
                            size_t* n_out, size_t* n_groups, size_t* n_children) {
   if (!n_children) return fail(FNNUE_E_ARG, "null argument");
-  return search2_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, child_best, child_map,
-                      child_cap, n_out, n_groups, n_children);
+  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
+                      child_best, child_map, child_cap, n_out, n_groups, n_children);
+}
+
+int fnnue_vsearch2_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                          const uint32_t* d_moves_off, size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off,
+                          size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  zero_counts(n_out, n_groups, nullptr);
+  return search2_device(ctx, variant, true, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
+                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream);
+}
+
+int fnnue_vsearch2(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                   const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
+                   size_t off_cap, size_t* n_out, size_t* n_groups) {
+  zero_counts(n_out, n_groups, nullptr);
+  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr,
+                      nullptr, 0, n_out, n_groups, nullptr);
+}
+
+int fnnue_vsearch2_children(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                            const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
+                            size_t off_cap, fnnue_best* child_best, uint32_t* child_map, size_t child_cap,
+                            size_t* n_out, size_t* n_groups, size_t* n_children) {
+  zero_counts(n_out, n_groups, n_children);
+  if (!n_children) return fail(FNNUE_E_ARG, "null argument");
+  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
+                      child_best, child_map, child_cap, n_out, n_groups, n_children);
 }
 
 int fnnue_vmove_uci(fnnue_move m, char out[8]) {

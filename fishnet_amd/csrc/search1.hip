@@ -14,7 +14,8 @@
 // The k best children of every group (fnnue_topk_children_device, MultiPV):
 // topk_children_kernel below, the same key ranked by counting in LDS.
 // The second reduction of the two-ply search (fnnue_best_replies_device):
-// best_replies_kernel below, the same shape over the children's own records.
+// best_replies_kernel below, the same shape over the children's own records;
+// vbest_replies_kernel with the variants' five ranks (fnnue_vbest_replies_device).
 #include <hip/hip_runtime.h>
 
 #include "builder.h"
@@ -293,6 +294,85 @@ __global__ __launch_bounds__(kBlock) void best_replies_kernel(
   if (live && lane < 8) out[(size_t)g * 8 + lane] = w;
 }
 
+// ---- the second reduction with the variant ranks (fnnue_vbest_replies_device) ----
+// best_replies_kernel's shape with five ranks: a child its side to move has
+// already won (FNNUE_END_WON: the mover lost by playing it) below everything,
+// and a child whose every reply loses at once (b_c.kind == FNNUE_BEST_LOST)
+// between the values and the mate in one.  Only the middle rank has a value, so
+// rank and value share one 32-bit score
+//   0 lost, 1 the reply mates, value + 2^29 (|value| <= 2^28: 2^28 .. 3 * 2^28),
+//   2^30 every reply loses, 2^30 + 1 mate in one
+// and the key is score << 32 | ~index: the whole 32-bit child index stays in
+// the key, the tie-break (the lower index) sits in the one 64-bit comparison,
+// and a group may have as many children as its 32-bit offsets can describe
+// (npos <= 2^32 - 1, which the callers check: at most 2^32 - 2 children).
+constexpr uint32_t kScoreLost = 0, kScoreMated = 1, kScoreValue = 1u << 29, kScoreWins = 1u << 30,
+                   kScoreMate = (1u << 30) + 1;
+
+__global__ __launch_bounds__(kBlock) void vbest_replies_kernel(
+    const uint8_t* __restrict__ end, const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off,
+    uint32_t ngroups, uint32_t npos, const uint32_t* __restrict__ child_best, const uint32_t* __restrict__ base_of,
+    uint32_t* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t g = (uint32_t)(t / kGroupLanes), lane = (uint32_t)(t % kGroupLanes);
+  const bool live = g < ngroups;  // no early return: the shuffles below run with the whole wave
+  uint32_t o = 0, e = 0, base = 0;
+  if (live) {
+    e = min(off[g + 1], npos);
+    o = min(off[g], e);
+    base = base_of ? base_of[g] : o - g;
+  }
+  const uint32_t nrec = e - o;
+  constexpr uint32_t kDeciding = kFinalCheck | kFinalExtinct | kFinalVariant;
+  unsigned long long key = 0;  // 0: no child (a child's key is never 0: ~index)
+  uint32_t nodes = 0;
+  for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
+    const uint32_t f = end[o + c];
+    const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
+    const uint32_t kind = (b[5] >> 16) & 0xFFu;
+    uint32_t score;
+    if (f & kFinalWon) score = kScoreLost;
+    else if (f & kFinalNoMoves) score = (f & kDeciding) ? kScoreMate : kScoreValue;
+    else if (kind == FNNUE_BEST_LOST) score = kScoreWins;
+    else if (kind == FNNUE_BEST_MATE) score = kScoreMated;
+    else score = (uint32_t)(kScoreValue - (int32_t)b[2]);
+    nodes += b[3];
+    const unsigned long long k = (unsigned long long)score << 32 | (0xFFFFFFFFu - c);
+    key = k > key ? k : key;
+  }
+#pragma unroll
+  for (int m = kGroupLanes / 2; m >= 1; m >>= 1) {
+    const unsigned long long other = (unsigned long long)__shfl_xor((long long)key, m, kGroupLanes);
+    key = other > key ? other : key;
+    nodes += (uint32_t)__shfl_xor((int)nodes, m, kGroupLanes);
+  }
+  uint32_t w = 0;
+  if (nrec) {  // an empty group: all zero
+    const uint32_t best = key ? 0xFFFFFFFFu - (uint32_t)key : 0u;
+    const uint32_t score = (uint32_t)(key >> 32);
+    const bool one = best && (end[o + best] & (kFinalWon | kFinalNoMoves));  // the pv ends at the child
+    const uint32_t kind = !best                 ? FNNUE_BEST_NONE
+                          : score == kScoreLost ? FNNUE_BEST_LOST
+                          : score == kScoreMated ? FNNUE_BEST_MATED
+                          : score >= kScoreWins ? FNNUE_BEST_MATE
+                                                : FNNUE_BEST_CP;
+    const uint32_t pv_len = !best ? 0u : one ? 1u : 2u;
+    const uint32_t* b = child_best + (size_t)(base + (best ? best - 1 : 0)) * 6;  // read only with a best child
+    switch (lane) {
+      case 0: w = !best ? 0u : one ? 0u - b[0] : b[0]; break;  // a one-move pv: the child's own terms, negated (wrapping)
+      case 1: w = !best ? 0u : one ? 0u - b[1] : b[1]; break;
+      case 2: w = kind == FNNUE_BEST_CP ? score - kScoreValue : 0u; break;
+      case 3: w = nrec - 1 + nodes; break;
+      case 4: w = best; break;
+      case 5: w = best && !one ? b[4] : 0u; break;
+      case 6: w = (best && moves ? (uint32_t)moves[o + best] : 0u) | (best && !one ? (b[5] & 0xFFFFu) << 16 : 0u); break;
+      case 7: w = kind | (uint32_t)end[o] << 8 | pv_len << 16; break;
+      default: break;
+    }
+  }
+  if (live && lane < 8) out[(size_t)g * 8 + lane] = w;
+}
+
 }  // namespace
 
 hipError_t launch_best_children(const int32_t* d_psqt, const int32_t* d_positional, const uint8_t* d_end,
@@ -327,6 +407,17 @@ hipError_t launch_best_replies(const uint8_t* d_end, const uint16_t* d_moves, co
   if (ngroups == 0) return hipSuccess;
   const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
   hipLaunchKernelGGL(best_replies_kernel, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_end,
+                     d_moves, d_off, ngroups, npos, reinterpret_cast<const uint32_t*>(d_child_best), d_base,
+                     reinterpret_cast<uint32_t*>(d_out));
+  return hipGetLastError();
+}
+
+hipError_t launch_vbest_replies(const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups,
+                                uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                                fnnue_best2* d_out, hipStream_t s) {
+  if (ngroups == 0) return hipSuccess;
+  const uint64_t threads = (uint64_t)ngroups * kGroupLanes;
+  hipLaunchKernelGGL(vbest_replies_kernel, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_end,
                      d_moves, d_off, ngroups, npos, reinterpret_cast<const uint32_t*>(d_child_best), d_base,
                      reinterpret_cast<uint32_t*>(d_out));
   return hipGetLastError();

@@ -654,7 +654,78 @@ __global__ __launch_bounds__(64) void pwrite_children_record_kernel(
   end[r] = f;
 }
 
+// ---- the variant two-ply search's child states ----
+// As builder.hip's child_states_kernel: one thread per record of the plies' STAR
+// groups finds its ply and its move; the child's board is stored as it is (not
+// packed), the ply's own record is skipped, so child j of ply i is entry
+// off[i] - i + j - 1 of a dense array that vchildren_count_device and
+// vchildren_write_device expand like any array of boards.  A threecheck child
+// carries its counters (do_move_v), which its own children's flags read.
+// map (optional): entry d -> (ply, 1-based child index).
+__global__ __launch_bounds__(64) void vchild_states_kernel(const vb::VBoard* __restrict__ states, uint32_t n,
+                                                           const uint32_t* __restrict__ off, uint32_t total,
+                                                           vb::VBoard* __restrict__ out, uint2* __restrict__ map) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const uint32_t lo = ply_of_record(off, n, r);
+  const uint32_t j = r - off[lo];
+  if (j == 0) return;
+  const vb::VBoard b = states[lo];
+  vb::VBoard c = b;
+  uint32_t k = 0;
+  vb::for_each_legal(b, [&](const vb::VMove& m) -> bool {
+    if (++k < j) return true;
+    vb::do_move(c, m);
+    return false;
+  });
+  const uint32_t d = r - lo - 1;
+  out[d] = c;
+  if (map) map[d] = make_uint2(lo, j);
+}
+
+template <int V>
+__global__ __launch_bounds__(64) void pchild_states_kernel(const DBoard* __restrict__ states, uint32_t n,
+                                                           const uint32_t* __restrict__ off, uint32_t total,
+                                                           DBoard* __restrict__ out, uint2* __restrict__ map) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const uint32_t lo = ply_of_record(off, n, r);
+  const uint32_t j = r - off[lo];
+  if (j == 0) return;
+  const DBoard b = states[lo];
+  DBoard c = b;
+  uint32_t k = 0;
+  for_each_legal<V>(b, [&](const DMove& m) -> bool {
+    if (++k < j) return true;
+    do_move_v<V>(c, m);
+    return false;
+  });
+  const uint32_t d = r - lo - 1;
+  out[d] = c;
+  if (map) map[d] = make_uint2(lo, j);
+}
+
 }  // namespace
+
+hipError_t vchild_states_device(int variant, const void* d_states, uint32_t n, const uint32_t* d_off, uint32_t total,
+                                void* d_out, uint2* d_map, hipStream_t s) {
+  if (n == 0 || total == 0) return hipSuccess;
+  const uint32_t bs = 64;
+  const dim3 grid((total + bs - 1) / bs);
+  if (variant == kVariantKingOfTheHill)
+    hipLaunchKernelGGL(pchild_states_kernel<kVariantKingOfTheHill>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, static_cast<DBoard*>(d_out), d_map);
+  else if (variant == kVariantRacingKings)
+    hipLaunchKernelGGL(pchild_states_kernel<kVariantRacingKings>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, static_cast<DBoard*>(d_out), d_map);
+  else if (variant == kVariantThreeCheck)
+    hipLaunchKernelGGL(pchild_states_kernel<kVariantThreeCheck>, grid, dim3(bs), 0, s,
+                       static_cast<const DBoard*>(d_states), n, d_off, total, static_cast<DBoard*>(d_out), d_map);
+  else
+    hipLaunchKernelGGL(vchild_states_kernel, grid, dim3(bs), 0, s, static_cast<const vb::VBoard*>(d_states), n, d_off,
+                       total, static_cast<vb::VBoard*>(d_out), d_map);
+  return hipGetLastError();
+}
 
 hipError_t vchildren_count_device(int variant, const void* d_states, uint32_t n, uint32_t* d_cnt, uint32_t* d_off,
                                   hipStream_t s, BuilderScratch& ws) {

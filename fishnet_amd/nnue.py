@@ -671,6 +671,64 @@ class Evaluator:
                                                   C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
+    # The two-ply search of the variants (ABI 3.10)
+    def vbest_replies(self, end, moves, off, child_best) -> np.ndarray:
+        """fnnue_vbest_replies: best_replies with the variants' ranks (END_WON children, children whose
+        every reply loses at once); kind may also be BEST_LOST."""
+        end = np.ascontiguousarray(end, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        child_best = np.ascontiguousarray(child_best, dtype=BEST_DTYPE)
+        if moves is not None:
+            moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        out = np.zeros(len(off) - 1, dtype=BEST2_DTYPE)
+        N.check(N.lib.fnnue_vbest_replies(self._h, N.ptr(end), N.ptr(moves), N.ptr(off), len(off) - 1, len(end),
+                                          N.ptr(child_best), N.ptr(out)))
+        return out
+
+    def vbest_replies_device(self, d_end: int, d_moves: int | None, d_off: int, ngroups: int, npos: int,
+                             d_child_best: int, d_out: int, stream: int | None):
+        N.check(N.lib.fnnue_vbest_replies_device(self._h, C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off),
+                                                 ngroups, npos, C.c_void_p(d_child_best), C.c_void_p(d_out),
+                                                 C.c_void_p(stream)))
+
+    def vsearch2(self, variant: int, games, children: bool = False):
+        """fnnue_vsearch2: a two-ply search per ply of variant games -> (BEST2_DTYPE records, CHAIN offsets).
+        With `children` (fnnue_vsearch2_children) also the children's depth-1 records and their
+        (ply, 1-based child index) pairs: -> (records, offsets, BEST_DTYPE records, (n, 2) uint32)."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=BEST2_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        if not children:
+            N.check(N.lib.fnnue_vsearch2(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                         N.ptr(out), cap, N.ptr(off), len(off), C.byref(n), C.byref(g)))
+            return out[: n.value], off[: g.value + 1]
+        # a crazyhouse ply has no fixed child bound: the count comes back with FNNUE_E_CAPACITY
+        nk = C.c_size_t()
+        rc = N.lib.fnnue_vsearch2_children(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off),
+                                           len(games), N.ptr(out), cap, N.ptr(off), len(off), None, None, 0,
+                                           C.byref(n), C.byref(g), C.byref(nk))
+        if rc != -10 or nk.value == 0:
+            N.check(rc)
+            return out[: n.value], off[: g.value + 1], np.zeros(0, dtype=BEST_DTYPE), np.zeros((0, 2), np.uint32)
+        kcap = nk.value
+        kb = np.zeros(kcap, dtype=BEST_DTYPE)
+        km = np.zeros((kcap, 2), dtype=np.uint32)
+        N.check(N.lib.fnnue_vsearch2_children(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off),
+                                              len(games), N.ptr(out), cap, N.ptr(off), len(off), N.ptr(kb),
+                                              N.ptr(km), kcap, C.byref(n), C.byref(g), C.byref(nk)))
+        return out[: n.value], off[: g.value + 1], kb[: nk.value], km[: nk.value]
+
+    def vsearch2_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int,
+                        cap: int, d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_vsearch2_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch2_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                            C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off),
+                                            off_cap, C.byref(n), C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
     def perft_device(self, fen: str, depth: int) -> int:
         nodes = C.c_uint64()
         N.check(N.lib.fnnue_perft_device(self._h, fen.encode(), depth, C.byref(nodes)))

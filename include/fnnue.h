@@ -660,6 +660,56 @@ int fnnue_search2_children(fnnue_ctx *ctx, const char *text, size_t text_len, co
                            size_t off_cap, fnnue_best *child_best, uint32_t *child_map, size_t child_cap,
                            size_t *n_out, size_t *n_groups, size_t *n_children);
 
+/* ---- two-ply search for the Fairy-Stockfish variants (ABI 3.10) ----
+ * The rule of ABI 3.7 with the variants' ranks.  f_c is child c's end byte as
+ * fnnue_build_vchildren writes it, b_c child c's own depth-1 record
+ * (fnnue_best_children under the ABI 3.6 ranks).  The key of child c from P's
+ * side to move, the conditions tested in this order:
+ *   f_c has FNNUE_END_WON, whatever else is set          rank 0, value 0   FNNUE_BEST_LOST   pv c
+ *   f_c has NO_MOVES and CHECK, EXTINCT or VARIANT       rank 4            FNNUE_BEST_MATE   pv c
+ *   f_c has NO_MOVES alone (stalemate, racingkings draw) rank 2, value 0   FNNUE_BEST_CP     pv c
+ *   b_c.kind == FNNUE_BEST_LOST: every reply loses       rank 3            FNNUE_BEST_MATE   pv c, b_c.move
+ *   b_c.kind == FNNUE_BEST_MATE: the reply wins at once  rank 1            FNNUE_BEST_MATED  pv c, reply
+ *   otherwise                                            rank 2, -b_c.value FNNUE_BEST_CP    pv c, reply
+ * The higher rank wins, then the higher value, then the lower index.  The
+ * record is fnnue_best2 as it is (kind may also be FNNUE_BEST_LOST); psqt /
+ * positional of a two-move pv are b_c's as they are, those of a one-move pv the
+ * child's own terms negated with wrap-around; nodes = children + the sum of
+ * b_c.nodes; a ply without a legal move is FNNUE_BEST_NONE.  On end bytes that
+ * use bits 0 and 1 only and child kinds NONE / CP / MATE the result equals
+ * fnnue_best_replies' byte for byte.  Signature, buffers, clamping and launch
+ * are fnnue_best_replies[_device]'s.  The key keeps the child's whole 32-bit
+ * index, so a group may have as many children as npos <= 2^32 - 1 allows;
+ * anything larger is FNNUE_E_ARG.  Any net. */
+int fnnue_vbest_replies_device(fnnue_ctx *ctx, const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                               size_t ngroups, size_t npos, const fnnue_best *d_child_best, fnnue_best2 *d_out,
+                               void *stream);
+int fnnue_vbest_replies(fnnue_ctx *ctx, const uint8_t *end, const fnnue_move *moves, const uint32_t *off,
+                        size_t ngroups, size_t npos, const fnnue_best *child_best, fnnue_best2 *out);
+/* fnnue_search2[_device] / fnnue_search2_children for a variant net's context:
+ * the same steps (fnnue_build_vchildren's level 1, the children's boards and
+ * counts, chunks of whole plies within FNNUE_SEARCH2_RECORDS, per chunk the
+ * expansion, fnnue_eval_vgroups STAR and the first reduction, then
+ * fnnue_vbest_replies), the same capacity protocol and FNNUE_SEARCH2_TRACE.  A
+ * ply whose records alone exceed the budget (a crazyhouse ply has no fixed
+ * bound) is a chunk of its own; the results do not depend on the budget.  The
+ * children's boards stay resident for the call: 88 bytes (kingofthehill,
+ * racingkings, threecheck) or 104 (crazyhouse, atomic) per child, plus its
+ * 24-byte record.  `variant` as for fnnue_vsearch1;
+ * FNNUE_E_ARCH otherwise, and on a chess context.  Move codes are
+ * fnnue_vmove_uci's.  The counts come back zeroed on every error that is not
+ * FNNUE_E_CAPACITY, a null context included. */
+int fnnue_vsearch2_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                          const uint32_t *d_moves_off, size_t ngames, fnnue_best2 *d_out, size_t cap, uint32_t *d_off,
+                          size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_vsearch2(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                   const uint32_t *moves_off, size_t ngames, fnnue_best2 *out, size_t cap, uint32_t *off,
+                   size_t off_cap, size_t *n_out, size_t *n_groups);
+int fnnue_vsearch2_children(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                            const uint32_t *moves_off, size_t ngames, fnnue_best2 *out, size_t cap, uint32_t *off,
+                            size_t off_cap, fnnue_best *child_best, uint32_t *child_map, size_t child_cap,
+                            size_t *n_out, size_t *n_groups, size_t *n_children);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

@@ -369,7 +369,8 @@ int fnnue_backend_set_analysis_plies(fnnue_backend *b, int plies);
 /* fnnue_backend_go_timeout plus the pv's second move: reply[i] is parallel to
  * out[i] (cap entries), the reply's fnnue_move code (fnnue_move_uci prints it)
  * or 0 for none: a channel below 2 plies, a one-move pv, a ply without a legal
- * move, skipped ids, move work, variant batches, failed batches.  The
+ * move, skipped ids, move work, variant batches (below 2 variant plies, see
+ * fnnue_backend_set_variant_analysis_plies), failed batches.  The
  * responses are those of go() / go_timeout() on the same channel. */
 int fnnue_backend_go_pv(fnnue_backend *b, const fnnue_acquired *batches, size_t nbatches,
                         fnnue_position_response *out, size_t cap, uint32_t *off, int32_t *batch_rc, fnnue_move *reply,
@@ -381,6 +382,29 @@ int fnnue_backend_go_pv(fnnue_backend *b, const fnnue_acquired *batches, size_t 
  * are fnnue_backend_analysis_json's. */
 int fnnue_backend_analysis_json_pv(const fnnue_position_response *r, size_t n, const fnnue_move *reply, char *buf,
                                    size_t cap, size_t *len);
+
+/* ---- variant analysis at two plies (ABI 3.10) ----
+ * fnnue_backend_set_variant_analysis_plies(b, plies): 0, 1 or 2, anything else
+ * FNNUE_E_ARG.  0 and 1 are fnnue_backend_set_variant_analysis_depth(b, 0 / 1),
+ * on the same field (that setter keeps refusing 2); the chess setting is
+ * another field and neither setter moves the other's.  At 2 every non-skipped
+ * ply of a crazyhouse, atomic, kingOfTheHill, racingKings or threeCheck
+ * analysis batch is answered with fnnue_vsearch2's two-ply search under the
+ * variant's rules and ranks: Cp(value * 100 / normalize_to_pawn); Mate(1) for
+ * FNNUE_BEST_MATE, at a one-move pv (the move ends the game) or a two-move pv
+ * (every reply loses at once); Mate(-1) for FNNUE_BEST_MATED (every move
+ * allows a reply that wins at once) and FNNUE_BEST_LOST (every move loses at
+ * once); depth = the pv's length; nodes = children + grandchildren; best_move
+ * spelled by fnnue_vmove_uci.  fnnue_backend_go_pv's reply is then a variant
+ * move code (fnnue_vmove_uci prints it; fnnue_backend_analysis_json_pv does:
+ * "pv":"N@f3 e7e5").  Staging is the chess channel's at two plies: pieces cut at
+ * a 256th of FNNUE_BACKEND_PIECE_PLIES (at least 16 plies; four times the
+ * chess cut measured fastest on crazyhouse), two bounded sizing waits per piece, a
+ * piece with a rejected game skips the search and is recovered as at depth 1,
+ * positions counts plies + children + grandchildren.  fnnue_backend_go_lines on
+ * such a channel is a one-ply search with lines, as on a one-ply channel.  Move
+ * work is unchanged. */
+int fnnue_backend_set_variant_analysis_plies(fnnue_backend *b, int plies);
 
 #ifdef __cplusplus
 }

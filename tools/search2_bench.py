@@ -2,6 +2,7 @@
 at two plies.  GPU box only.  One JSON line per measurement.
 
     python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor]
+                                  [--variant crazyhouse|atomic|kingofthehill|racingkings|threecheck]
 
 The shape: N random legal games of L plies each from the start position
 (default 200 x 60: ~12k plies, ~400k children, ~13M grandchild records, a few
@@ -19,6 +20,12 @@ the second reduction.  records_per_s counts the records each search evaluates
 child once more).
 `--actor` adds the engine actor's go_pv() at 1 and 2 plies on 1 and 64
 lichess-shaped chess batches.
+`--variant NAME` measures fnnue_vsearch1_device / fnnue_vsearch2_device on
+random legal games of that variant instead (a synthetic variant net; the atomic
+net for kingofthehill, racingkings and threecheck), and with `--actor` the
+actor's go_pv() at 1 and 2 variant plies on batches of that variant;
+`--piece-plies A,B,...` repeats the 2-plies actor lines with those values of
+FNNUE_BACKEND_PIECE_PLIES (a two-plies piece is a 1024th of it).
 """
 import argparse
 import ctypes as C
@@ -33,6 +40,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 START = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
+VARIANTS = {"crazyhouse": ("VARIANT_CRAZYHOUSE", START.replace(" w", "[] w"), "crazyhouse"),
+            "atomic": ("VARIANT_ATOMIC", START, "atomic"),
+            "kingofthehill": ("VARIANT_KINGOFTHEHILL", START, "kingOfTheHill"),
+            "racingkings": ("VARIANT_RACINGKINGS", "8/8/8/8/8/8/krbnNBRK/qrbnNBRQ w - - 0 1", "racingKings"),
+            "threecheck": ("VARIANT_THREECHECK", START, "threeCheck")}
 
 
 def main():
@@ -43,19 +55,30 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--actor", action="store_true")
+    ap.add_argument("--variant", choices=sorted(VARIANTS), default=None)
+    ap.add_argument("--piece-plies", default="")
     a = ap.parse_args()
     import torch
     import fishnet_amd as F
     from fishnet_amd import _native as N
 
-    games = [(START, F.random_game(a.seed * 1_000_003 + i, START, a.plies)) for i in range(a.games)]
+    vid = getattr(N, VARIANTS[a.variant][0]) if a.variant else 0
+    if a.variant:
+        root = VARIANTS[a.variant][1]
+        games = [(root, F.random_vgame(a.seed * 1_000_003 + i, vid, root, a.plies)) for i in range(a.games)]
+    else:
+        games = [(START, F.random_game(a.seed * 1_000_003 + i, START, a.plies)) for i in range(a.games)]
     text, fen_off, mv_off = F.pack_games(games)
     dev = torch.device("cuda", 0)
     d_text = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev)
     d_fo = torch.from_numpy(fen_off.view(np.int32)).to(dev)
     d_mo = torch.from_numpy(mv_off.view(np.int32)).to(dev)
     T, FO, MO, ng = d_text.data_ptr(), d_fo.data_ptr(), d_mo.data_ptr(), len(games)
-    ev = F.Evaluator(F.Net.from_bytes(F.synthesize_net(1, a.hd, 0)), 0)
+    if a.variant:  # the atomic net also serves kingofthehill, racingkings and threecheck
+        made_as = N.VARIANT_CRAZYHOUSE if vid == N.VARIANT_CRAZYHOUSE else N.VARIANT_ATOMIC
+        ev = F.Evaluator(F.Net.from_bytes_variant(F.synthesize_variant_net(5, a.hd, made_as), made_as), 0)
+    else:
+        ev = F.Evaluator(F.Net.from_bytes(F.synthesize_net(1, a.hd, 0)), 0)
     stream = torch.cuda.Stream(dev)
     S = stream.cuda_stream
     plies = sum(len(m.split()) + 1 for _, m in games)
@@ -65,10 +88,16 @@ def main():
     torch.cuda.synchronize(dev)
 
     def search1():
-        ev.search1_device(T, FO, MO, ng, d_b1.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+        if a.variant:
+            ev.vsearch1_device(vid, T, FO, MO, ng, d_b1.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+        else:
+            ev.search1_device(T, FO, MO, ng, d_b1.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
 
     def search2():
-        ev.search2_device(T, FO, MO, ng, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+        if a.variant:
+            ev.vsearch2_device(vid, T, FO, MO, ng, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
+        else:
+            ev.search2_device(T, FO, MO, ng, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
 
     phases = [("search1", search1), ("search2", search2)]
 
@@ -94,8 +123,8 @@ def main():
     b2 = d_b2.cpu().numpy().view(F.BEST2_DTYPE).reshape(-1)
     children = int(b1["nodes"].sum())
     grand_records = int(b2["nodes"].sum())  # every child's own record + its children
-    assert int(b2["nodes"].max()) <= 219 * 219
-    base = {"games": ng, "hd": a.hd, "plies": plies, "children": children, "grandchild_records": grand_records,
+    assert a.variant or int(b2["nodes"].max()) <= 219 * 219
+    base = {"variant": a.variant or "chess", "games": ng, "hd": a.hd, "plies": plies, "children": children, "grandchild_records": grand_records,
             "budget": int(os.environ.get("FNNUE_SEARCH2_RECORDS", 16 << 20))}
     for k, (name, _) in enumerate(phases):
         ms = sorted(r[k] for r in runs)
@@ -114,7 +143,9 @@ def main():
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     ev.close()
-    if a.actor:
+    if a.actor and a.variant:
+        vactor_lines(a, vid)
+    elif a.actor:
         actor_lines(a)
 
 
@@ -147,6 +178,50 @@ def actor_lines(a):
                               "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
                   flush=True)
             actor.close()
+
+
+def vactor_lines(a, vid):
+    """The engine actor at 1 and 2 variant plies on lichess-shaped batches of one variant (40-160 plies
+    each), the two-plies lines once per piece size asked for."""
+    import fishnet_amd as F
+    from fishnet_amd import _native as N
+    from fishnet_amd import backend as B
+    _, root, name = VARIANTS[a.variant]
+    made_as = N.VARIANT_CRAZYHOUSE if vid == N.VARIANT_CRAZYHOUSE else N.VARIANT_ATOMIC
+    data = F.synthesize_variant_net(5, a.hd, made_as)
+    rng = np.random.default_rng(11)
+    cuts = [None] + [int(x) for x in a.piece_plies.split(",") if x]
+    for nb in (1, 64):
+        bodies = [B.AcquireResponseBody(f"b{i}", root, F.random_vgame(11_000_033 + i, vid, root, int(rng.integers(40, 161))),
+                                        variant=name) for i in range(nb)]
+        plies = sum(len(b.moves.split()) + 1 for b in bodies)
+        for n, cut in [(1, None)] + [(2, c) for c in cuts]:
+            if cut is None:
+                os.environ.pop("FNNUE_BACKEND_PIECE_PLIES", None)
+            else:
+                os.environ["FNNUE_BACKEND_PIECE_PLIES"] = str(cut)
+            stub, actor = B.channel(None, 0, **{a.variant: F.Net.from_bytes_variant(data, vid)},
+                                    variant_analysis_plies=n)
+            t0 = time.perf_counter()
+            stub.go_pv(bodies)
+            while time.perf_counter() - t0 < 0.3:
+                stub.go_pv(bodies)
+            calls, stats = [], None
+            for _ in range(a.runs):
+                stub.go_pv(bodies)
+                calls.append(stub.last_call_s * 1e3)
+                stats = B.last_stats(actor)
+            calls.sort()
+            med = calls[len(calls) // 2]
+            print(json.dumps({"variant": a.variant, "actor_plies": n, "piece_plies": cut or 524288, "batches": nb,
+                              "plies": plies, "positions": stats["positions"],
+                              "ms_per_call": [round(x, 3) for x in calls], "median_ms": round(med, 3),
+                              "plies_per_s": round(plies / (med * 1e-3)),
+                              "positions_per_s": round(stats["positions"] / (med * 1e-3)),
+                              "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
+                  flush=True)
+            actor.close()
+    os.environ.pop("FNNUE_BACKEND_PIECE_PLIES", None)
 
 
 if __name__ == "__main__":
