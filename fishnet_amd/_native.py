@@ -35,6 +35,8 @@ BEST2_BYTES = 32  # fnnue_best2
 BEST_MATED = 4
 LINE_BYTES = 20  # fnnue_line
 PV_LINE_BYTES = 24  # fnnue_pv_line
+LINE2_BYTES = 28  # fnnue_line2
+PV_LINE2_BYTES = 32  # fnnue_pv_line2
 MAX_CHILDREN = 218  # FNNUE_MAX_CHILDREN
 VPOS_BYTES = 48
 
@@ -191,6 +193,21 @@ SIGNATURES = {
     "fnnue_vsearch2_children": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz,
                                  _P(_sz), _P(_sz), _P(_sz)], _i32),
     "fnnue_backend_set_variant_analysis_plies": ([_vp, _i32], _i32),
+    # MultiPV at two plies (ABI 3.11)
+    "fnnue_topk_replies_device": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp], _i32),
+    "fnnue_topk_replies": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz], _i32),
+    "fnnue_vtopk_replies_device": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp], _i32),
+    "fnnue_vtopk_replies": ([_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz], _i32),
+    "fnnue_search2_lines_device": ([_vp, _vp, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp],
+                                   _i32),
+    "fnnue_search2_lines": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                             _P(_sz)], _i32),
+    "fnnue_vsearch2_lines_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                                     _P(_sz), _vp], _i32),
+    "fnnue_vsearch2_lines": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz),
+                              _P(_sz)], _i32),
+    "fnnue_backend_go_lines_pv": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32], _i32),
+    "fnnue_backend_analysis_json_lines_pv": ([_vp, _sz, _vp, _vp, C.c_char_p, _sz, _P(_sz)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

@@ -49,6 +49,11 @@ class _PvLine(C.Structure):
                 ("score_kind", C.c_uint8)]
 
 
+class _PvLine2(C.Structure):
+    _fields_ = [("score", C.c_int64), ("psqt", C.c_int32), ("positional", C.c_int32), ("pv", C.c_char * 14),
+                ("score_kind", C.c_uint8), ("pv_len", C.c_uint8)]
+
+
 class _Compact(C.Structure):
     _fields_ = [("psqt", C.c_int32), ("positional", C.c_int32), ("score", C.c_int32), ("score_kind", C.c_uint8),
                 ("depth", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8)]
@@ -89,6 +94,15 @@ class PvLine:
 
 
 @dataclass
+class PvLine2:
+    """One MultiPV line with its whole pv (fnnue_pv_line2): `pv` holds one or two UCI moves."""
+    score: Score
+    pv: list[str]
+    psqt: int = 0
+    positional: int = 0
+
+
+@dataclass
 class PositionResponse:
     position_id: int
     score: Score | None               # None for Skip::Skip
@@ -101,7 +115,8 @@ class PositionResponse:
     best_move: str | None = None
     skipped: bool = False
     matrix: bool = False              # AnalysisPart::Matrix (the batch asked for multipv)
-    lines: list[PvLine] | None = None  # go_lines: the MultiPV lines, best first (None: go() / no line)
+    # go_lines: the MultiPV lines, best first (None: go() / no line); go_lines_pv: PvLine2 lines
+    lines: list[PvLine] | list[PvLine2] | None = None
     reply: str | None = None          # go_pv on a 2-plies channel: the pv's second move (None: no reply)
 
 
@@ -193,7 +208,17 @@ class GpuEvalStub:
         response has reply = None."""
         return self._go(bodies, timeout_ms, None, with_reply=True)
 
-    def _go(self, bodies, timeout_ms, lines_cap, with_reply=False):
+    def go_lines_pv(self, bodies: Sequence[AcquireResponseBody], timeout_ms: int = 0,
+                    lines_cap: int | None = None) -> list[list[PositionResponse] | PositionFailed]:
+        """go_pv() with the MultiPV lines and their whole pvs (fnnue_backend_go_lines_pv): the rows and
+        their `reply` are go_pv()'s; on a 2-plies setting every non-skipped ply with a legal move of an
+        analysis batch with multipv = k carries `lines`, its min(k, legal moves) best PvLine2 lines
+        (`pv`: one or two UCI moves), best first; on a 1-ply setting go_lines' lines as one-move
+        PvLine2; every other response has lines = None."""
+        return self._go(bodies, timeout_ms, lines_bound(bodies) if lines_cap is None else int(lines_cap),
+                        with_reply=True, pv2=True)
+
+    def _go(self, bodies, timeout_ms, lines_cap, with_reply=False, pv2=False):
         nb = len(bodies)
         if nb == 0:
             return []
@@ -207,7 +232,14 @@ class GpuEvalStub:
         rc = np.zeros(nb, dtype=np.int32)
         self.last_batch_rc = rc
         t0 = time.perf_counter()
-        if with_reply:
+        if pv2:
+            reply = np.zeros(max(1, cap), dtype=np.uint16)
+            pv = (_PvLine2 * max(1, lines_cap))()
+            loff = np.zeros(cap + 1, dtype=np.uint32)
+            t0 = time.perf_counter()
+            ret = N.lib.fnnue_backend_go_lines_pv(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc), pv, lines_cap,
+                                                  N.ptr(loff), N.ptr(reply), int(timeout_ms))
+        elif with_reply:
             reply = np.zeros(max(1, cap), dtype=np.uint16)
             ret = N.lib.fnnue_backend_go_pv(self._actor._h, a, nb, out, cap, N.ptr(off), N.ptr(rc), N.ptr(reply),
                                             int(timeout_ms))
@@ -239,7 +271,12 @@ class GpuEvalStub:
                     matrix=bool(r.matrix)))
                 if with_reply and reply[k]:
                     rows[-1].reply = vmove_uci(int(reply[k]))  # a chess code prints as move_uci prints it
-                if lines_cap is not None and loff[k + 1] > loff[k]:
+                if pv2 and loff[k + 1] > loff[k]:
+                    rows[-1].lines = [
+                        PvLine2(Score("mate" if l.score_kind == SCORE_MATE else "cp", int(l.score)),
+                                l.pv.decode().split(), l.psqt, l.positional)
+                        for l in pv[int(loff[k]):int(loff[k + 1])]]
+                elif lines_cap is not None and loff[k + 1] > loff[k]:
                     rows[-1].lines = [
                         PvLine(Score("mate" if l.score_kind == SCORE_MATE else "cp", int(l.score)), l.move.decode(),
                                l.psqt, l.positional) for l in pv[int(loff[k]):int(loff[k + 1])]]
@@ -387,7 +424,8 @@ def _move_code(uci: str | None) -> int:
 
 def into_analysis(responses: Sequence[PositionResponse]) -> str:
     """The `analysis` JSON array of a completed analysis batch (fnnue_backend_analysis_json; with
-    MultiPV lines, fnnue_backend_analysis_json_lines; with a row's `reply`, the two-move pv of
+    MultiPV lines, fnnue_backend_analysis_json_lines, or for go_lines_pv's PvLine2 lines
+    fnnue_backend_analysis_json_lines_pv; with a row's `reply`, the two-move pv of
     fnnue_backend_analysis_json_pv)."""
     arr = (_Response * max(1, len(responses)))()
     for i, r in enumerate(responses):
@@ -398,6 +436,21 @@ def into_analysis(responses: Sequence[PositionResponse]) -> str:
         arr[i] = _Response(r.position_id, 0, kind, r.depth, 1 if r.matrix else 0, r.score.value, r.psqt,
                            r.positional, r.nodes, r.time_ms, r.nps, (r.best_move or "").encode())
     n = C.c_size_t()
+    if any(isinstance(l, PvLine2) for r in responses for l in r.lines or ()):  # go_lines_pv rows: whole pvs
+        loff = np.zeros(len(responses) + 1, dtype=np.uint32)
+        loff[1:] = np.cumsum([len(r.lines or ()) for r in responses])
+        pv2 = (_PvLine2 * max(1, int(loff[-1])))()
+        at = 0
+        for r in responses:
+            for l in r.lines or ():
+                pv2[at] = _PvLine2(l.score.value, l.psqt, l.positional, " ".join(l.pv).encode(),
+                                   SCORE_MATE if l.score.kind == "mate" else SCORE_CP, len(l.pv))
+                at += 1
+        N.lib.fnnue_backend_analysis_json_lines_pv(arr, len(responses), pv2, N.ptr(loff), None, 0, C.byref(n))
+        buf = C.create_string_buffer(n.value + 1)
+        N.check(N.lib.fnnue_backend_analysis_json_lines_pv(arr, len(responses), pv2, N.ptr(loff), buf, len(buf),
+                                                           C.byref(n)))
+        return buf.value.decode()
     if any(r.lines for r in responses):  # MultiPV: the matrix with one row per line
         loff = np.zeros(len(responses) + 1, dtype=np.uint32)
         loff[1:] = np.cumsum([len(r.lines or ()) for r in responses])

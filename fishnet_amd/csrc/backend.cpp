@@ -53,6 +53,12 @@
 // are on the device anyway into a `lines` section behind the fnnue_best
 // records; fill() converts each ply's first min(k, nodes) lines.  go() and
 // go_compact() stage no slots and launch exactly what they did before.
+//
+// MultiPV at two plies (fnnue_backend_go_lines_pv): the call searches at the
+// channel's own plies; a two-plies piece with slots launches
+// fnnue_topk_replies_device's kernel beside the second reduction instead, over
+// the same end bytes, moves and children's records, and its `lines` section
+// holds fnnue_line2 records (move, reply); a one-ply piece ranks as go_lines.
 #include "../../include/fnnue_backend.h"
 
 #include <algorithm>
@@ -111,6 +117,8 @@ struct Job {
   fnnue_pv_line* lines = nullptr;
   uint32_t* line_off = nullptr;
   fnnue_move* reply = nullptr;  // fnnue_backend_go_pv: the pv's second move beside `out`
+  fnnue_pv_line2* lines2 = nullptr;  // fnnue_backend_go_lines_pv: the lines with their whole pv, instead of `lines`
+  bool with_lines() const { return lines || lines2; }
   int ret = 0;
   std::string err;  // fnnue_last_error of a failed call
 };
@@ -202,6 +210,9 @@ uint32_t line_slots(const fnnue_acquired& a) {
 static_assert(sizeof(fnnue_pv_line) == 24 && offsetof(fnnue_pv_line, move) == 16 &&
                   offsetof(fnnue_pv_line, score_kind) == 23,
               "fnnue_pv_line layout");
+static_assert(sizeof(fnnue_pv_line2) == 32 && offsetof(fnnue_pv_line2, pv) == 16 &&
+                  offsetof(fnnue_pv_line2, score_kind) == 30 && offsetof(fnnue_pv_line2, pv_len) == 31,
+              "fnnue_pv_line2 layout");
 
 // A full response written in place as four stores — bytes 0-15 (position id,
 // the four flag bytes, score), 16-31 (psqt, positional, nodes), 32-47 and
@@ -352,7 +363,8 @@ struct Piece {
   size_t searched = 0;
   // MultiPV (fnnue_backend_go_lines at depth 1): the plies' slot offsets go up
   // at o_loff (n + 1 words: min(multipv, 218) slots for every ply of a batch
-  // that asked), and the results image ends with the nslots fnnue_line slots.
+  // that asked), and the results image ends with the nslots fnnue_line slots
+  // (a two-plies piece of a go_lines_pv(): fnnue_line2 slots).
   size_t nslots = 0, o_loff = 0, o_lines = 0;
   bool pending = false;                           // evaluation enqueued, results not yet read
 };
@@ -669,7 +681,7 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.depth1 = depth1(k) && ng;
   P.depth2 = depth2(k) && ng;
   P.nslots = 0;
-  if (j.lines && P.depth1)
+  if (j.with_lines() && P.depth1)
     for (size_t i : P.games) P.nslots += (size_t)(j.off[i + 1] - j.off[i]) * line_slots(j.batches[i]);
   P.o_fen = align16(text);
   P.o_mv = P.o_fen + 4 * (ng + 1);
@@ -682,7 +694,7 @@ void fnnue_backend::layout(const Job& j, int k, Piece& P) {
   P.o_po = P.o_ps + 4 * (n + nk);
   P.o_best = align16(P.o_po + 4 * (n + nk));
   P.o_lines = P.o_best + n * (P.depth2 ? sizeof(fnnue_best2) : sizeof(fnnue_best));
-  P.end = P.depth1 ? P.o_lines + P.nslots * sizeof(fnnue_line) : P.o_po + 4 * (n + nk);
+  P.end = P.depth1 ? P.o_lines + P.nslots * (P.depth2 ? sizeof(fnnue_line2) : sizeof(fnnue_line)) : P.o_po + 4 * (n + nk);
 }
 
 // Cuts the net's games into pieces and places them in its (grow-only) buffers.
@@ -999,7 +1011,12 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                                  reinterpret_cast<fnnue_best*>(dimg + P.o_best), s),
             "best_children launch");
   }
-  if (P.nslots)  // a go_lines() call whose piece has a batch that asked for MultiPV
+  if (P.nslots && P.depth2)  // a go_lines_pv() call at two plies: the lines with their replies
+    HIP_TRY(launch_topk_replies(!chess, ke, km, coff, n, (uint32_t)total, W.kid_best.at<fnnue_best>(0), nullptr,
+                                reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
+                                reinterpret_cast<fnnue_line2*>(dimg + P.o_lines), P.nslots, s),
+            "topk_replies launch");
+  else if (P.nslots)  // a go_lines() call whose piece has a batch that asked for MultiPV
     HIP_TRY(launch_topk_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
                                  reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
                                  reinterpret_cast<fnnue_line*>(dimg + P.o_lines), P.nslots, s),
@@ -1140,8 +1157,11 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   filled += P.n + P.nk + P.searched;
   const fnnue_best* best = P.depth1 && !P.depth2 ? reinterpret_cast<const fnnue_best*>(res + (P.o_best - P.o_res)) : nullptr;
   const fnnue_best2* best2 = P.depth2 ? reinterpret_cast<const fnnue_best2*>(res + (P.o_best - P.o_res)) : nullptr;
-  const bool with_lines = P.depth1 && P.nslots && j.lines;
-  const fnnue_line* dlines = with_lines ? reinterpret_cast<const fnnue_line*>(res + (P.o_lines - P.o_res)) : nullptr;
+  const bool with_lines = P.depth1 && P.nslots && j.with_lines();
+  const fnnue_line* dlines =
+      with_lines && !P.depth2 ? reinterpret_cast<const fnnue_line*>(res + (P.o_lines - P.o_res)) : nullptr;
+  const fnnue_line2* dlines2 =
+      with_lines && P.depth2 ? reinterpret_cast<const fnnue_line2*>(res + (P.o_lines - P.o_res)) : nullptr;
   const uint32_t* loff = with_lines ? W.up.at<uint32_t>(P.up0 + P.o_loff) : nullptr;
   const double el = ms_since(t0);
   const uint64_t ms = (uint64_t)el;
@@ -1164,6 +1184,7 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
         // Two plies: every ply from its fnnue_best2; a ply without a child as at depth 0.
         const fnnue_best2* gb = best2 + ply[g];
         const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
+        const uint32_t kk = dlines2 ? line_slots(j.batches[i]) : 0;
         for (uint32_t q = 0; q < len; ++q) {
           const fnnue_best2& B = gb[q];
           const bool skipped = sk && skip[b + q];
@@ -1189,6 +1210,29 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           put_response(r, response_head(q, 0, kind, depth, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
           if (!none) (void)(k == kVariantChess ? fnnue_move_uci(B.move, r->best_move) : fnnue_vmove_uci(B.move, r->best_move));
           if (j.reply && !none) j.reply[b + q] = B.reply;
+          if (none || !kk) continue;
+          // MultiPV at two plies: the ply's lines until the first unused slot
+          // (the slots beyond its legal moves are all-zero), at the batch's
+          // provisional place (close_lines() packs them afterwards)
+          const fnnue_line2* src = dlines2 + loff[ply[g] + q];
+          fnnue_pv_line2* dst = j.lines2 + lbase[i] + (size_t)q * kk;
+          uint32_t nl = 0;
+          for (; nl < kk && src[nl].kind != FNNUE_BEST_NONE; ++nl) {
+            const fnnue_line2& L = src[nl];
+            const bool lm = L.kind == FNNUE_BEST_MATE, ld = L.kind == FNNUE_BEST_MATED || L.kind == FNNUE_BEST_LOST;
+            char mv[8], rp[8] = {0};
+            (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
+            if (L.pv_len == 2) (void)(k == kVariantChess ? fnnue_move_uci(L.reply, rp) : fnnue_vmove_uci(L.reply, rp));
+            fnnue_pv_line2 out{};
+            out.score = lm ? 1 : ld ? -1 : (int64_t)L.value * 100 / nrm;
+            out.psqt = L.psqt;
+            out.positional = L.positional;
+            std::snprintf(out.pv, sizeof(out.pv), "%s%s%s", mv, rp[0] ? " " : "", rp);
+            out.score_kind = lm || ld ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+            out.pv_len = rp[0] ? 2 : 1;
+            dst[nl] = out;
+          }
+          j.line_off[b + q + 1] = nl;  // a count for now
         }
         if (j.cout) {
           fnnue_batch_compact& B = j.bout[i];
@@ -1234,12 +1278,24 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           // batch's provisional place (close_lines() packs them afterwards)
           const uint32_t nl = std::min(kk, B.nodes);
           const fnnue_line* src = dlines + loff[ply[g] + q];
-          fnnue_pv_line* dst = j.lines + lbase[i] + (size_t)q * kk;
+          const size_t at = lbase[i] + (size_t)q * kk;
+          fnnue_pv_line* dst = j.lines ? j.lines + at : nullptr;
           for (uint32_t l = 0; l < nl; ++l) {
             const fnnue_line& L = src[l];
             const bool lm = L.kind == FNNUE_BEST_MATE, ll = L.kind == FNNUE_BEST_LOST;
             char mv[8];
             (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
+            if (!dst) {  // go_lines_pv at one ply: the same line in the two-ply record
+              fnnue_pv_line2 out2{};
+              out2.score = lm ? 1 : ll ? -1 : (int64_t)L.value * 100 / nrm;
+              out2.psqt = L.psqt;
+              out2.positional = L.positional;
+              std::memcpy(out2.pv, mv, 6);
+              out2.score_kind = lm || ll ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+              out2.pv_len = 1;
+              j.lines2[at + l] = out2;
+              continue;
+            }
             fnnue_pv_line out{};
             out.score = lm ? 1 : ll ? -1 : (int64_t)L.value * 100 / nrm;
             out.psqt = L.psqt;
@@ -1409,7 +1465,9 @@ void fnnue_backend::fill_hostonly(Job& j, const std::vector<size_t>& all_skipped
 // count in line_off; here the lines are packed in response order and the
 // counts become offsets.  A batch that failed keeps an empty range.
 void fnnue_backend::close_lines(Job& j) {
-  if (!j.lines) return;
+  if (!j.with_lines()) return;
+  char* const base = j.lines ? reinterpret_cast<char*>(j.lines) : reinterpret_cast<char*>(j.lines2);
+  const size_t sz = j.lines ? sizeof(fnnue_pv_line) : sizeof(fnnue_pv_line2);
   size_t w = 0;
   j.line_off[0] = 0;
   for (size_t i = 0; i < j.nb; ++i) {
@@ -1417,7 +1475,7 @@ void fnnue_backend::close_lines(Job& j) {
     for (uint32_t r = j.off[i]; r < j.off[i + 1]; ++r) {
       const uint32_t nl = j.rc[i] ? 0 : j.line_off[r + 1];
       const size_t from = lbase[i] + (size_t)(r - j.off[i]) * kk;
-      if (nl && from != w) std::memmove(j.lines + w, j.lines + from, nl * sizeof(fnnue_pv_line));
+      if (nl && from != w) std::memmove(base + w * sz, base + from * sz, nl * sz);
       w += nl;
       j.line_off[r + 1] = (uint32_t)w;
     }
@@ -1496,7 +1554,7 @@ void fnnue_backend::run(Job& j) {
   }
   for (NetWork& W : net) W.clear();
   if (j.reply) std::memset(j.reply, 0, (size_t)j.off[nb] * sizeof(fnnue_move));  // none until fill() says otherwise
-  if (j.lines) {  // every response without lines until fill() says otherwise
+  if (j.with_lines()) {  // every response without lines until fill() says otherwise
     std::memset(j.line_off, 0, ((size_t)j.off[nb] + 1) * sizeof(uint32_t));
     lbase.resize(nb);
     size_t at = 0;
@@ -1880,6 +1938,28 @@ int fnnue_backend_go_lines(fnnue_backend* b, const fnnue_acquired* batches, size
   return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
 }
 
+int fnnue_backend_go_lines_pv(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches,
+                              fnnue_position_response* out, size_t cap, uint32_t* off, int32_t* batch_rc,
+                              fnnue_pv_line2* lines, size_t lines_cap, uint32_t* line_off, fnnue_move* reply,
+                              uint32_t timeout_ms) {
+  if (!b || !off || !batch_rc || !line_off || (nbatches && !batches) || (cap && !out) || (lines_cap && !lines))
+    return fail(FNNUE_E_ARG, "null argument");
+  if (nbatches > (1u << 24)) return fail(FNNUE_E_ARG, "too many batches");
+  size_t bound = 0;
+  if (int rc = fnnue_backend_lines_bound(batches, nbatches, &bound)) return rc;
+  if (bound > UINT32_MAX) return fail(FNNUE_E_ARG, "the batches ask for more than 2^32 - 1 lines");
+  if (lines_cap < bound)
+    return fail(FNNUE_E_CAPACITY, "line buffer holds " + std::to_string(lines_cap) + ", batches may need " +
+                                      std::to_string(bound));
+  fnnue_pv_line2 none;  // a call that can have no line still runs as a go_lines_pv() call
+  Job j;
+  j.out = out;
+  j.lines2 = lines ? lines : &none;
+  j.line_off = line_off;
+  j.reply = reply;
+  return go_job(b, j, batches, nbatches, cap, off, batch_rc, timeout_ms);
+}
+
 int fnnue_backend_go_pv(fnnue_backend* b, const fnnue_acquired* batches, size_t nbatches, fnnue_position_response* out,
                         size_t cap, uint32_t* off, int32_t* batch_rc, fnnue_move* reply, uint32_t timeout_ms) {
   if (!b || !off || !batch_rc || (nbatches && !batches) || (cap && (!out || !reply)))
@@ -1941,7 +2021,8 @@ int fnnue_backend_last_stats(fnnue_backend* b, fnnue_backend_stats* out) {
 namespace {
 // Both JSON forms: without `lines` every response has its own one line.
 int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_line* lines, const uint32_t* line_off,
-                  char* buf, size_t cap, size_t* len, const fnnue_move* reply = nullptr) {
+                  char* buf, size_t cap, size_t* len, const fnnue_move* reply = nullptr,
+                  const fnnue_pv_line2* lines2 = nullptr) {
   std::string s = "[";
   char tmp[192];
   for (size_t i = 0; i < n; ++i) {
@@ -1969,22 +2050,29 @@ int analysis_json(const fnnue_position_response* r, size_t n, const fnnue_pv_lin
     const size_t nl = line_off && r[i].matrix ? line_off[i + 1] - line_off[i] : 0;  // lines are rows of the matrix form
     if (nl) {
       // Matrix::set per line: row l is `depth` nulls and then the entry
-      const fnnue_pv_line* L = lines + (line_off[i] - line_off[0]);
+      const fnnue_pv_line* L = lines ? lines + (line_off[i] - line_off[0]) : nullptr;
+      const fnnue_pv_line2* L2 = lines2 ? lines2 + (line_off[i] - line_off[0]) : nullptr;
       std::string nulls;
       for (unsigned d = 0; d < r[i].depth; ++d) nulls += "null,";
       s += "{\"pv\":[";
       for (size_t l = 0; l < nl; ++l) {
-        char mv[8] = {0};
-        std::memcpy(mv, L[l].move, 7);
-        mv[6] = 0;
-        for (char* c = mv; *c; ++c)
+        // the line's own pv: one move (fnnue_pv_line), or one or two separated by a space (fnnue_pv_line2)
+        char mv[16] = {0};
+        if (L2) std::memcpy(mv, L2[l].pv, sizeof(L2[l].pv) - 1);
+        else std::memcpy(mv, L[l].move, 6);
+        std::string entry;
+        for (char* c = mv; *c; ++c) {
           if (*c == '"' || *c == '\\' || (unsigned char)*c < 0x20) *c = '?';
-        s += (l ? ",[" : "[") + nulls + (mv[0] ? std::string("[\"") + mv + "\"]" : std::string("[]")) + "]";
+          if (*c == ' ') entry += "\",\"";
+          else entry += *c;
+        }
+        s += (l ? ",[" : "[") + nulls + (mv[0] ? "[\"" + entry + "\"]" : std::string("[]")) + "]";
       }
       s += "],\"score\":[";
       for (size_t l = 0; l < nl; ++l) {
-        std::snprintf(tmp, sizeof(tmp), "{\"%s\":%lld}]", L[l].score_kind == FNNUE_SCORE_MATE ? "mate" : "cp",
-                      (long long)L[l].score);
+        std::snprintf(tmp, sizeof(tmp), "{\"%s\":%lld}]",
+                      (L2 ? L2[l].score_kind : L[l].score_kind) == FNNUE_SCORE_MATE ? "mate" : "cp",
+                      (long long)(L2 ? L2[l].score : L[l].score));
         s += (l ? ",[" : "[") + nulls + tmp;
       }
       std::snprintf(tmp, sizeof(tmp), "],\"depth\":%u,\"nodes\":%llu,\"time\":%llu", (unsigned)r[i].depth,
@@ -2044,6 +2132,15 @@ int fnnue_backend_analysis_json_lines(const fnnue_position_response* r, size_t n
   for (size_t i = 0; i < n; ++i)
     if (line_off[i] > line_off[i + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
   return analysis_json(r, n, lines, line_off, buf, cap, len);
+}
+
+int fnnue_backend_analysis_json_lines_pv(const fnnue_position_response* r, size_t n, const fnnue_pv_line2* lines,
+                                         const uint32_t* line_off, char* buf, size_t cap, size_t* len) {
+  if ((n && !r) || !line_off || !len || (cap && !buf)) return fail(FNNUE_E_ARG, "null argument");
+  if (line_off[n] != line_off[0] && !lines) return fail(FNNUE_E_ARG, "null argument");
+  for (size_t i = 0; i < n; ++i)
+    if (line_off[i] > line_off[i + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
+  return analysis_json(r, n, nullptr, line_off, buf, cap, len, nullptr, lines);
 }
 
 }  // extern "C"

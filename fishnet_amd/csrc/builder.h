@@ -173,6 +173,12 @@ hipError_t launch_topk_children(const int32_t* d_psqt, const int32_t* d_position
                                 const uint16_t* d_moves, const uint32_t* d_off, uint32_t ngroups, uint32_t npos,
                                 const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line* d_lines, size_t lines_cap,
                                 hipStream_t s);
+// The k best lines of every ply at two plies as fnnue_line2 records: the second
+// reduction's inputs and key (vranks: the variants'), launch_topk_children's slots.
+hipError_t launch_topk_replies(bool vranks, const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off,
+                               uint32_t ngroups, uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                               const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line2* d_lines, size_t lines_cap,
+                               hipStream_t s);
 hipError_t launch_gather_parents(const int32_t* d_psqt, const int32_t* d_positional, const uint32_t* d_off,
                                  uint32_t ngroups, uint32_t npos, int32_t* d_ps_out, int32_t* d_po_out, hipStream_t s);
 

@@ -403,7 +403,9 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.9: fnnue_multi_create_replicas; the fnnue_multi_* messages name the shard and the caller's index
 // 3.10: the two-ply search for the variants: fnnue_vbest_replies[_device], fnnue_vsearch2[_device],
 //      fnnue_vsearch2_children, fnnue_backend_set_variant_analysis_plies
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 10u; }
+// 3.11: MultiPV at two plies: fnnue_line2 / fnnue_[v]topk_replies[_device], fnnue_[v]search2_lines[_device],
+//       fnnue_backend_go_lines_pv, fnnue_backend_analysis_json_lines_pv
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 11u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1809,9 +1811,109 @@ int best_replies_host(fnnue_ctx* ctx, bool vranks, const uint8_t* end, const fnn
   return FNNUE_OK;
 }
 
+// fnnue_topk_replies_device (vranks = false) and fnnue_vtopk_replies_device:
+// best_replies_device's base offsets, then the ranking kernel.
+int topk_replies_device(fnnue_ctx* ctx, bool vranks, const uint8_t* d_end, const fnnue_move* d_moves,
+                        const uint32_t* d_off, size_t ngroups, size_t npos, const fnnue_best* d_child_best,
+                        const uint32_t* d_line_off, fnnue_line2* d_lines, size_t lines_cap, void* stream) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!d_end || !d_off || !d_child_best || !d_line_off || (lines_cap && !d_lines))
+    return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  if (lines_cap == 0) return FNNUE_OK;  // no slot may be written
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  int rc = order_workspace(ctx, s);
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  uint32_t *cnt = nullptr, *base = nullptr;
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidCnt, (ngroups + 1) * 4, (void**)&cnt), "device allocation (scratch)");
+  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidOff, (ngroups + 1) * 4, (void**)&base), "device allocation (scratch)");
+  HIP_TRY(launch_child_counts(d_off, (uint32_t)ngroups, (uint32_t)npos, cnt, s), "child_counts launch");
+  HIP_TRY(builder_exclusive_scan(cnt, base, (uint32_t)ngroups, s, ctx->bscratch), "scan");
+  HIP_TRY(launch_topk_replies(vranks, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_child_best, base,
+                              d_line_off, 0, d_lines, lines_cap, s),
+          "topk_replies launch");
+  return FNNUE_OK;
+}
+
+int topk_replies_host(fnnue_ctx* ctx, bool vranks, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                      size_t ngroups, size_t npos, const fnnue_best* child_best, const uint32_t* line_off,
+                      fnnue_line2* lines, size_t lines_cap) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (ngroups == 0) return FNNUE_OK;
+  if (!off || !line_off || (npos && !end)) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  for (size_t g = 0; g < ngroups; ++g)
+    if (line_off[g] > line_off[g + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
+  const size_t nl = line_off[ngroups];
+  if (nl > lines_cap) return fail(FNNUE_E_CAPACITY, "line buffer too small");
+  if (nl && !lines) return fail(FNNUE_E_ARG, "null buffer");
+  size_t nchild = 0;  // as the kernel clamps the offsets
+  for (size_t i = 0; i < ngroups; ++i) {
+    const size_t e = std::min<size_t>(off[i + 1], npos), o = std::min<size_t>(off[i], e);
+    if (e > o) nchild += e - o - 1;
+  }
+  if (nchild && !child_best) return fail(FNNUE_E_ARG, "null buffer");
+  if (nl == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  // [child_best | off | line_off | lines | moves | end]: 4-byte parts first
+  const size_t o_off = (nchild + 1) * sizeof(fnnue_best), o_loff = o_off + (ngroups + 1) * 4;
+  const size_t o_lines = o_loff + (ngroups + 1) * 4, o_mv = o_lines + nl * sizeof(fnnue_line2), o_end = o_mv + npos * 2;
+  TempDev buf;
+  if (int rc = buf.get(o_end + npos)) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  if (nchild) HIP_TRY(hipMemcpyAsync(d, child_best, nchild * sizeof(fnnue_best), hipMemcpyHostToDevice, s), "H2D");
+  if (npos) {
+    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
+    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  HIP_TRY(hipMemcpyAsync(d + o_loff, line_off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
+  // the caller's lines go up first, so that slots no group writes (empty groups) come back as they were
+  HIP_TRY(hipMemcpyAsync(d + o_lines, lines, nl * sizeof(fnnue_line2), hipMemcpyHostToDevice, s), "H2D");
+  const int rc = topk_replies_device(ctx, vranks, reinterpret_cast<uint8_t*>(d + o_end),
+                                     moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
+                                     reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
+                                     reinterpret_cast<fnnue_best*>(d), reinterpret_cast<uint32_t*>(d + o_loff),
+                                     reinterpret_cast<fnnue_line2*>(d + o_lines), nl, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(lines, d + o_lines, nl * sizeof(fnnue_line2), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fnnue_topk_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
+                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, const uint32_t* d_line_off,
+                              fnnue_line2* d_lines, size_t lines_cap, void* stream) {
+  return topk_replies_device(ctx, false, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_line_off, d_lines,
+                             lines_cap, stream);
+}
+
+int fnnue_topk_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off, size_t ngroups,
+                       size_t npos, const fnnue_best* child_best, const uint32_t* line_off, fnnue_line2* lines,
+                       size_t lines_cap) {
+  return topk_replies_host(ctx, false, end, moves, off, ngroups, npos, child_best, line_off, lines, lines_cap);
+}
+
+int fnnue_vtopk_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
+                               size_t ngroups, size_t npos, const fnnue_best* d_child_best, const uint32_t* d_line_off,
+                               fnnue_line2* d_lines, size_t lines_cap, void* stream) {
+  return topk_replies_device(ctx, true, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_line_off, d_lines,
+                             lines_cap, stream);
+}
+
+int fnnue_vtopk_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
+                        size_t ngroups, size_t npos, const fnnue_best* child_best, const uint32_t* line_off,
+                        fnnue_line2* lines, size_t lines_cap) {
+  return topk_replies_host(ctx, true, end, moves, off, ngroups, npos, child_best, line_off, lines, lines_cap);
+}
 
 int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
                               size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
@@ -1853,7 +1955,7 @@ size_t search2_budget() {
 // prints the phases' device times to stderr, one JSON line — diagnostics only
 // (tools/search2_bench.py).
 struct Search2Trace {
-  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kPhases };
+  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kPhases };
   bool on = false;
   hipStream_t s = nullptr;
   std::vector<std::pair<int, hipEvent_t>> marks;
@@ -1868,7 +1970,7 @@ struct Search2Trace {
     if (ev) marks.emplace_back(phase, ev);
   }
   void report(size_t plies, size_t kids, size_t records, size_t chunks) {
-    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1", "reduce2"};
+    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1", "reduce2", "topk"};
     if (on && !marks.empty() && hipEventSynchronize(marks.back().second) == hipSuccess) {
       double ms[kPhases] = {};
       for (size_t i = 0; i + 1 < marks.size(); ++i) {
@@ -1906,11 +2008,14 @@ void zero_counts(size_t* n_out, size_t* n_groups, size_t* n_children) {
 
 // fnnue_search2_device (variant = chess) and fnnue_vsearch2_device; with
 // d_child_best / d_child_map (child_cap entries each) also the children's
-// depth-1 records (fnnue_[v]search2_children).
+// depth-1 records (fnnue_[v]search2_children); with k >= 1 also ply p's k best
+// lines at d_lines[p * k ..] (fnnue_[v]search2_lines_device): one more kernel
+// behind the second reduction, over the same arrays.
 int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
                    size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
                    fnnue_best* d_child_best, uint32_t* d_child_map, size_t child_cap, size_t* n_out, size_t* n_groups,
-                   size_t* n_children, void* stream) {
+                   size_t* n_children, void* stream, uint32_t k = 0, fnnue_line2* d_lines = nullptr,
+                   size_t lines_cap = 0) {
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
   if (n_children) *n_children = 0;
@@ -1929,6 +2034,7 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
   // level 1: the plies' boards (scratch) and their STAR groups' offsets, moves and end flags
   ChildrenBufs kids;
   kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  if (k) kids.max_groups = d_lines ? std::min(kids.max_groups, lines_cap / k) : 0;
   size_t nrec = 0, nply = 0;
   if (chess) {
     rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
@@ -1967,6 +2073,10 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
   if (nkid == 0) {  // every ply is a finished game's last
     HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
             "best_replies launch");
+    if (k)  // every slot all-zero
+      HIP_TRY(launch_topk_replies(!chess, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best,
+                                  nullptr, nullptr, k, d_lines, lines_cap, s),
+              "topk_replies launch");
     HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
     return FNNUE_OK;
   }
@@ -2052,6 +2162,12 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
   trace.mark(Search2Trace::kReduce2);
   HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
           "best_replies launch");
+  if (k) {
+    trace.mark(Search2Trace::kTopk);
+    HIP_TRY(launch_topk_replies(!chess, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best,
+                                nullptr, nullptr, k, d_lines, lines_cap, s),
+            "topk_replies launch");
+  }
   trace.mark(Search2Trace::kPhases);
   trace.report(nply, nkid, all_rec, cuts.size() - 1);
   if (n_children && nkid)
@@ -2063,7 +2179,8 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
 
 int search2_host(fnnue_ctx* ctx, int variant, bool vcall, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
                  size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap, fnnue_best* child_best,
-                 uint32_t* child_map, size_t child_cap, size_t* n_out, size_t* n_groups, size_t* n_children) {
+                 uint32_t* child_map, size_t child_cap, size_t* n_out, size_t* n_groups, size_t* n_children,
+                 uint32_t k = 0, fnnue_line2* lines = nullptr, size_t lines_cap = 0) {
   if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
     return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
@@ -2075,13 +2192,14 @@ int search2_host(fnnue_ctx* ctx, int variant, bool vcall, const char* text, size
   uint32_t *d_fo = nullptr, *d_mo = nullptr;
   int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
   if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1;
+  const bool room = out && off && off_cap >= ngames + 1 && (!k || lines);
   const bool kroom = n_children && child_best && child_map;
   if (!kroom) child_cap = 0;
-  // [best2 | child_best | child_map | off]
+  // [best2 | child_best | child_map | lines | off]: the lines' room is cut to whole plies the records have room for
+  const size_t nl = k ? std::min(lines_cap / k, cap) * k : 0;
   TempDev buf;
   const size_t o_cb = cap * sizeof(fnnue_best2), o_cm = o_cb + child_cap * sizeof(fnnue_best);
-  const size_t o_off = o_cm + child_cap * 8;
+  const size_t o_lines = o_cm + child_cap * 8, o_off = o_lines + nl * sizeof(fnnue_line2);
   if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
   char* d = static_cast<char*>(buf.p);
   hipStream_t s = ctx->stream;
@@ -2089,9 +2207,11 @@ int search2_host(fnnue_ctx* ctx, int variant, bool vcall, const char* text, size
                       room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
                       room && kroom ? reinterpret_cast<fnnue_best*>(d + o_cb) : nullptr,
                       room && kroom ? reinterpret_cast<uint32_t*>(d + o_cm) : nullptr, room ? child_cap : 0, n_out,
-                      n_groups, n_children, s);
+                      n_groups, n_children, s, k, room && k ? reinterpret_cast<fnnue_line2*>(d + o_lines) : nullptr,
+                      room ? nl : 0);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
+  if (k) HIP_TRY(hipMemcpyAsync(lines, d + o_lines, *n_out * k * sizeof(fnnue_line2), hipMemcpyDeviceToHost, s), "D2H");
   if (n_children && *n_children) {
     HIP_TRY(hipMemcpyAsync(child_best, d + o_cb, *n_children * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
     HIP_TRY(hipMemcpyAsync(child_map, d + o_cm, *n_children * 8, hipMemcpyDeviceToHost, s), "D2H");
@@ -2152,6 +2272,48 @@ int fnnue_vsearch2_children(fnnue_ctx* ctx, int variant, const char* text, size_
   if (!n_children) return fail(FNNUE_E_ARG, "null argument");
   return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
                       child_best, child_map, child_cap, n_out, n_groups, n_children);
+}
+
+static int lines2_k(uint32_t k, size_t* n_out, size_t* n_groups) {
+  zero_counts(n_out, n_groups, nullptr);
+  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
+  return FNNUE_OK;
+}
+
+int fnnue_search2_lines_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                               const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best2* d_out, size_t cap,
+                               uint32_t* d_off, size_t off_cap, fnnue_line2* d_lines, size_t lines_cap, size_t* n_out,
+                               size_t* n_groups, void* stream) {
+  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
+  return search2_device(ctx, kVariantChess, false, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
+                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream, k, d_lines, lines_cap);
+}
+
+int fnnue_search2_lines(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                        const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best2* out, size_t cap,
+                        uint32_t* off, size_t off_cap, fnnue_line2* lines, size_t lines_cap, size_t* n_out,
+                        size_t* n_groups) {
+  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
+  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
+                      nullptr, nullptr, 0, n_out, n_groups, nullptr, k, lines, lines_cap);
+}
+
+int fnnue_vsearch2_lines_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                                const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best2* d_out, size_t cap,
+                                uint32_t* d_off, size_t off_cap, fnnue_line2* d_lines, size_t lines_cap, size_t* n_out,
+                                size_t* n_groups, void* stream) {
+  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
+  return search2_device(ctx, variant, true, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
+                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream, k, d_lines, lines_cap);
+}
+
+int fnnue_vsearch2_lines(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                         const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best2* out, size_t cap,
+                         uint32_t* off, size_t off_cap, fnnue_line2* lines, size_t lines_cap, size_t* n_out,
+                         size_t* n_groups) {
+  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
+  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr,
+                      nullptr, 0, n_out, n_groups, nullptr, k, lines, lines_cap);
 }
 
 int fnnue_vmove_uci(fnnue_move m, char out[8]) {

@@ -16,6 +16,8 @@
 // The second reduction of the two-ply search (fnnue_best_replies_device):
 // best_replies_kernel below, the same shape over the children's own records;
 // vbest_replies_kernel with the variants' five ranks (fnnue_vbest_replies_device).
+// The k best lines of every ply at two plies (fnnue_topk_replies_device):
+// topk_replies_kernel, the second reduction's key ranked by counting in LDS.
 #include <hip/hip_runtime.h>
 
 #include "builder.h"
@@ -218,6 +220,55 @@ __global__ __launch_bounds__(kBlock) void gather_parents_kernel(const int32_t* _
 // count of the children of the groups before, child_counts_kernel and a scan).
 static_assert(sizeof(fnnue_best2) == 32, "fnnue_best2 is eight dwords");
 
+// The variants' scores (vbest_replies_kernel below explains them).
+constexpr uint32_t kScoreLost = 0, kScoreMated = 1, kScoreValue = 1u << 29, kScoreWins = 1u << 30,
+                   kScoreMate = (1u << 30) + 1;
+
+// The key of child c from its end byte f and its own depth-1 record b: the one
+// function behind both reductions and the ranking (topk_replies_kernel), so
+// that slot 0 of a ply's lines is its fnnue_best2 by construction.
+template <bool kVariant>
+__device__ __forceinline__ unsigned long long reply_key(uint32_t f, const uint32_t* __restrict__ b, uint32_t c) {
+  constexpr uint32_t kDeciding = kFinalCheck | kFinalExtinct | kFinalVariant;
+  const uint32_t kind = (b[5] >> 16) & 0xFFu;
+  if constexpr (kVariant) {
+    uint32_t score;
+    if (f & kFinalWon) score = kScoreLost;
+    else if (f & kFinalNoMoves) score = (f & kDeciding) ? kScoreMate : kScoreValue;
+    else if (kind == FNNUE_BEST_LOST) score = kScoreWins;
+    else if (kind == FNNUE_BEST_MATE) score = kScoreMated;
+    else score = (uint32_t)(kScoreValue - (int32_t)b[2]);
+    return (unsigned long long)score << 32 | (0xFFFFFFFFu - c);
+  } else {
+    uint32_t rank = 2;
+    int32_t v = 0;
+    if (f & kFinalNoMoves) {
+      rank = (f & kDeciding) ? 3u : 2u;
+    } else {
+      if (kind == FNNUE_BEST_MATE) rank = 1;
+      else v = -(int32_t)b[2];
+    }
+    return (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+  }
+}
+// What a key says about its child: the FNNUE_BEST_* kind and the value (FNNUE_BEST_CP only, else 0).
+template <bool kVariant>
+__device__ __forceinline__ uint32_t reply_kind(unsigned long long key) {
+  if constexpr (kVariant) {
+    const uint32_t score = (uint32_t)(key >> 32);
+    return score == kScoreLost ? FNNUE_BEST_LOST : score == kScoreMated ? FNNUE_BEST_MATED
+           : score >= kScoreWins ? FNNUE_BEST_MATE : FNNUE_BEST_CP;
+  } else {
+    const uint32_t rank = (uint32_t)(key >> 62);
+    return rank == 3 ? FNNUE_BEST_MATE : rank == 1 ? FNNUE_BEST_MATED : FNNUE_BEST_CP;
+  }
+}
+template <bool kVariant>
+__device__ __forceinline__ uint32_t reply_value(unsigned long long key) {
+  if constexpr (kVariant) return (uint32_t)(key >> 32) - kScoreValue;
+  else return (uint32_t)((int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29));
+}
+
 __global__ __launch_bounds__(kBlock) void child_counts_kernel(const uint32_t* __restrict__ off, uint32_t ngroups,
                                                               uint32_t npos, uint32_t* __restrict__ cnt) {
   const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
@@ -244,24 +295,12 @@ __global__ __launch_bounds__(kBlock) void best_replies_kernel(
     base = base_of ? base_of[g] : o - g;
   }
   const uint32_t nrec = e - o;
-  constexpr uint32_t kDeciding = kFinalCheck | kFinalExtinct | kFinalVariant;
   unsigned long long key = 0;  // 0: no child (a child's key is never 0: ~index)
   uint32_t nodes = 0;
   for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
-    const uint32_t f = end[o + c];
     const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
-    uint32_t rank = 2;
-    int32_t v = 0;
-    if (f & kFinalNoMoves) {
-      rank = (f & kDeciding) ? 3u : 2u;
-    } else {
-      const uint32_t kind = (b[5] >> 16) & 0xFFu;
-      if (kind == FNNUE_BEST_MATE) rank = 1;
-      else v = -(int32_t)b[2];
-    }
     nodes += b[3];
-    const unsigned long long k =
-        (unsigned long long)rank << 62 | (unsigned long long)(uint32_t)(v + (1 << 29)) << 32 | (0xFFFFFFFFu - c);
+    const unsigned long long k = reply_key<false>(end[o + c], b, c);
     key = k > key ? k : key;
   }
 #pragma unroll
@@ -306,8 +345,7 @@ __global__ __launch_bounds__(kBlock) void best_replies_kernel(
 // the key, the tie-break (the lower index) sits in the one 64-bit comparison,
 // and a group may have as many children as its 32-bit offsets can describe
 // (npos <= 2^32 - 1, which the callers check: at most 2^32 - 2 children).
-constexpr uint32_t kScoreLost = 0, kScoreMated = 1, kScoreValue = 1u << 29, kScoreWins = 1u << 30,
-                   kScoreMate = (1u << 30) + 1;
+// (the constants sit above reply_key.)
 
 __global__ __launch_bounds__(kBlock) void vbest_replies_kernel(
     const uint8_t* __restrict__ end, const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off,
@@ -323,21 +361,12 @@ __global__ __launch_bounds__(kBlock) void vbest_replies_kernel(
     base = base_of ? base_of[g] : o - g;
   }
   const uint32_t nrec = e - o;
-  constexpr uint32_t kDeciding = kFinalCheck | kFinalExtinct | kFinalVariant;
   unsigned long long key = 0;  // 0: no child (a child's key is never 0: ~index)
   uint32_t nodes = 0;
   for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
-    const uint32_t f = end[o + c];
     const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
-    const uint32_t kind = (b[5] >> 16) & 0xFFu;
-    uint32_t score;
-    if (f & kFinalWon) score = kScoreLost;
-    else if (f & kFinalNoMoves) score = (f & kDeciding) ? kScoreMate : kScoreValue;
-    else if (kind == FNNUE_BEST_LOST) score = kScoreWins;
-    else if (kind == FNNUE_BEST_MATE) score = kScoreMated;
-    else score = (uint32_t)(kScoreValue - (int32_t)b[2]);
     nodes += b[3];
-    const unsigned long long k = (unsigned long long)score << 32 | (0xFFFFFFFFu - c);
+    const unsigned long long k = reply_key<true>(end[o + c], b, c);
     key = k > key ? k : key;
   }
 #pragma unroll
@@ -371,6 +400,104 @@ __global__ __launch_bounds__(kBlock) void vbest_replies_kernel(
     }
   }
   if (live && lane < 8) out[(size_t)g * 8 + lane] = w;
+}
+
+// ---- the k best lines per ply of the two-ply search (fnnue_topk_replies_device, MultiPV) ----
+// topk_children_kernel's ranking applied to the second reduction's keys
+// (reply_key): 32 lanes per ply, up to kTopkFast children staged once in LDS as
+// 64-bit keys, every lane counting the keys above each of its own (at most
+// kTopkRegs, in registers) by same-address ds_read_b64 broadcasts; a child whose
+// count is below the ply's slot count writes its own 28-byte line at that slot.
+// A ply with more children (crazyhouse, hand-made input) recomputes the keys
+// from global memory.  Slots beyond the children are zeroed; an empty group or
+// one without a slot writes nothing; nothing is written at or beyond lines_cap.
+static_assert(sizeof(fnnue_line2) == 28, "fnnue_line2 is seven dwords");
+
+template <bool kVariant>
+__device__ __forceinline__ void write_line2(uint32_t* __restrict__ lines, uint64_t slot, unsigned long long key,
+                                            const uint8_t* __restrict__ end, const uint16_t* __restrict__ moves,
+                                            const uint32_t* __restrict__ child_best, uint32_t o, uint32_t base) {
+  const uint32_t c = 0xFFFFFFFFu - (uint32_t)key;
+  const uint32_t kind = reply_kind<kVariant>(key);
+  const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
+  const bool one = end[o + c] & (kVariant ? (kFinalWon | kFinalNoMoves) : kFinalNoMoves);  // the pv ends at the child
+  uint32_t* w = lines + slot * 7;
+  w[0] = one ? 0u - b[0] : b[0];  // a one-move pv: the child's own terms, negated (wrapping)
+  w[1] = one ? 0u - b[1] : b[1];
+  w[2] = kind == FNNUE_BEST_CP ? reply_value<kVariant>(key) : 0u;
+  w[3] = c;
+  w[4] = one ? 0u : b[4];
+  w[5] = (moves ? (uint32_t)moves[o + c] : 0u) | (one ? 0u : (b[5] & 0xFFFFu) << 16);
+  w[6] = kind | (one ? 1u : 2u) << 8;
+}
+
+template <bool kVariant>
+__global__ __launch_bounds__(kBlock) void topk_replies_kernel(
+    const uint8_t* __restrict__ end, const uint16_t* __restrict__ moves, const uint32_t* __restrict__ off,
+    uint32_t ngroups, uint32_t npos, const uint32_t* __restrict__ child_best, const uint32_t* __restrict__ base_of,
+    const uint32_t* __restrict__ line_off, uint32_t uniform_k, uint32_t* __restrict__ lines, uint64_t lines_cap) {
+  __shared__ unsigned long long staged[kTopkGroups][kTopkFast];
+  const uint32_t hw = threadIdx.x / kGroupLanes, lane = threadIdx.x % kGroupLanes;
+  const uint64_t g64 = (uint64_t)blockIdx.x * kTopkGroups + hw;
+  const bool live = g64 < ngroups;  // no early return: the barrier below runs with the whole block
+  const uint32_t g = (uint32_t)g64;
+  uint32_t o = 0, e = 0, base = 0;
+  uint64_t lo = 0, k = 0;  // the group's slots [lo, lo + k), cut at lines_cap
+  if (live) {
+    e = min(off[g + 1], npos);
+    o = min(off[g], e);
+    base = base_of ? base_of[g] : o - g;
+    if (line_off) {
+      lo = line_off[g];
+      const uint64_t hi = line_off[g + 1];
+      k = hi > lo ? hi - lo : 0;
+    } else {
+      lo = (uint64_t)g * uniform_k;
+      k = uniform_k;
+    }
+    k = lo < lines_cap ? min(k, lines_cap - lo) : 0;
+  }
+  const uint32_t nrec = e - o;
+  const uint32_t nkids = nrec && k ? nrec - 1 : 0;  // nothing to rank without a slot
+  const bool fast = nkids <= kTopkFast;
+  unsigned long long key[kTopkRegs];
+#pragma unroll
+  for (uint32_t i = 0; i < kTopkRegs; ++i) {
+    const uint32_t q = lane + kGroupLanes * i;  // child q + 1
+    key[i] = 0;
+    if (fast && q < nkids) {
+      key[i] = reply_key<kVariant>(end[o + q + 1], child_best + (size_t)(base + q) * 6, q + 1);
+      staged[hw][q] = key[i];
+    }
+  }
+  __syncthreads();
+  if (fast) {
+    uint32_t above[kTopkRegs];
+#pragma unroll
+    for (uint32_t i = 0; i < kTopkRegs; ++i) above[i] = 0;
+    for (uint32_t q = 0; q < nkids; ++q) {
+      const unsigned long long other = staged[hw][q];  // the same address in every lane of the half wave
+#pragma unroll
+      for (uint32_t i = 0; i < kTopkRegs; ++i) above[i] += other > key[i] ? 1u : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kTopkRegs; ++i)
+      if (key[i] && above[i] < k) write_line2<kVariant>(lines, lo + above[i], key[i], end, moves, child_best, o, base);
+  } else {
+    for (uint32_t c = 1 + lane; c < nrec; c += kGroupLanes) {
+      const unsigned long long mine = reply_key<kVariant>(end[o + c], child_best + (size_t)(base + c - 1) * 6, c);
+      uint64_t above = 0;
+      for (uint32_t q = 1; q < nrec && above < k; ++q)
+        above += reply_key<kVariant>(end[o + q], child_best + (size_t)(base + q - 1) * 6, q) > mine ? 1u : 0u;
+      if (above < k) write_line2<kVariant>(lines, lo + above, mine, end, moves, child_best, o, base);
+    }
+  }
+  // slots beyond the group's children: all zero (an empty group writes nothing)
+  if (nrec)
+    for (uint64_t j = (uint64_t)nkids + lane; j < k; j += kGroupLanes) {
+      uint32_t* w = lines + (lo + j) * 7;
+      w[0] = w[1] = w[2] = w[3] = w[4] = w[5] = w[6] = 0u;
+    }
 }
 
 }  // namespace
@@ -431,6 +558,23 @@ hipError_t launch_topk_children(const int32_t* d_psqt, const int32_t* d_position
   hipLaunchKernelGGL(topk_children_kernel, dim3((uint32_t)(((uint64_t)ngroups + kTopkGroups - 1) / kTopkGroups)), dim3(kBlock), 0, s, d_psqt,
                      d_positional, d_end, d_moves, d_off, ngroups, npos, d_line_off, uniform_k,
                      reinterpret_cast<uint32_t*>(d_lines), (uint64_t)lines_cap);
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_replies(bool vranks, const uint8_t* d_end, const uint16_t* d_moves, const uint32_t* d_off,
+                               uint32_t ngroups, uint32_t npos, const fnnue_best* d_child_best, const uint32_t* d_base,
+                               const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line2* d_lines, size_t lines_cap,
+                               hipStream_t s) {
+  if (ngroups == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)ngroups + kTopkGroups - 1) / kTopkGroups));
+  const uint32_t* kb = reinterpret_cast<const uint32_t*>(d_child_best);
+  uint32_t* out = reinterpret_cast<uint32_t*>(d_lines);
+  if (vranks)
+    hipLaunchKernelGGL(topk_replies_kernel<true>, grid, dim3(kBlock), 0, s, d_end, d_moves, d_off, ngroups, npos, kb,
+                       d_base, d_line_off, uniform_k, out, (uint64_t)lines_cap);
+  else
+    hipLaunchKernelGGL(topk_replies_kernel<false>, grid, dim3(kBlock), 0, s, d_end, d_moves, d_off, ngroups, npos, kb,
+                       d_base, d_line_off, uniform_k, out, (uint64_t)lines_cap);
   return hipGetLastError();
 }
 

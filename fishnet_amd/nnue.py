@@ -243,6 +243,10 @@ class Line(C.Structure):
 LINE_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"), ("move", "<u2"),
                        ("kind", "u1"), ("reserved", "u1")])
 MAX_CHILDREN = N.MAX_CHILDREN
+# fnnue_line2: one of a ply's k best lines at two plies (move, reply); kind BEST_NONE = an unused slot
+LINE2_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"),
+                        ("reply_index", "<u4"), ("move", "<u2"), ("reply", "<u2"), ("kind", "u1"), ("pv_len", "u1"),
+                        ("reserved", "<u2")])
 
 
 def move_uci(code: int) -> str:
@@ -727,6 +731,98 @@ class Evaluator:
         N.check(N.lib.fnnue_vsearch2_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
                                             C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off),
                                             off_cap, C.byref(n), C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    # MultiPV at two plies (ABI 3.11)
+    def _topk_replies(self, fn, end, moves, off, child_best, k_or_line_off, lines_cap, fill):
+        end = np.ascontiguousarray(end, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        child_best = np.ascontiguousarray(child_best, dtype=BEST_DTYPE)
+        if moves is not None:
+            moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        ng = len(off) - 1
+        if np.ndim(k_or_line_off) == 0:
+            line_off = (np.arange(ng + 1, dtype=np.uint64) * int(k_or_line_off)).astype(np.uint32)
+        else:
+            line_off = np.ascontiguousarray(k_or_line_off, dtype=np.uint32)
+        cap = int(line_off[-1]) if lines_cap is None else int(lines_cap)
+        lines = np.full(max(cap, 1) * N.LINE2_BYTES, fill, dtype=np.uint8).view(LINE2_DTYPE)
+        N.check(fn(self._h, N.ptr(end), N.ptr(moves), N.ptr(off), ng, len(end), N.ptr(child_best), N.ptr(line_off),
+                   N.ptr(lines), cap))
+        return lines[:cap], line_off
+
+    def topk_replies(self, end, moves, off, child_best, k_or_line_off, lines_cap: int | None = None,
+                     fill: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_topk_replies: the k best lines of every STAR group from best_replies' arrays ->
+        (LINE2_DTYPE slots, line_off).  `k_or_line_off`, `lines_cap` and `fill` as for topk_children."""
+        return self._topk_replies(N.lib.fnnue_topk_replies, end, moves, off, child_best, k_or_line_off, lines_cap, fill)
+
+    def vtopk_replies(self, end, moves, off, child_best, k_or_line_off, lines_cap: int | None = None,
+                      fill: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_vtopk_replies: topk_replies with the variants' ranks (vbest_replies' order)."""
+        return self._topk_replies(N.lib.fnnue_vtopk_replies, end, moves, off, child_best, k_or_line_off, lines_cap,
+                                  fill)
+
+    def topk_replies_device(self, d_end: int, d_moves: int | None, d_off: int, ngroups: int, npos: int,
+                            d_child_best: int, d_line_off: int, d_lines: int, lines_cap: int, stream: int | None):
+        N.check(N.lib.fnnue_topk_replies_device(self._h, C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off),
+                                                ngroups, npos, C.c_void_p(d_child_best), C.c_void_p(d_line_off),
+                                                C.c_void_p(d_lines), lines_cap, C.c_void_p(stream)))
+
+    def vtopk_replies_device(self, d_end: int, d_moves: int | None, d_off: int, ngroups: int, npos: int,
+                             d_child_best: int, d_line_off: int, d_lines: int, lines_cap: int, stream: int | None):
+        N.check(N.lib.fnnue_vtopk_replies_device(self._h, C.c_void_p(d_end), C.c_void_p(d_moves), C.c_void_p(d_off),
+                                                 ngroups, npos, C.c_void_p(d_child_best), C.c_void_p(d_line_off),
+                                                 C.c_void_p(d_lines), lines_cap, C.c_void_p(stream)))
+
+    def search2_lines(self, games, k: int, lines_cap: int | None = None):
+        """fnnue_search2_lines: search2 plus each ply's k best lines ->
+        (BEST2_DTYPE records, CHAIN offsets per game, LINE2_DTYPE slots of shape (plies, k)).
+        `lines_cap` (default: plies * k) sizes the line buffer."""
+        return self._search2_lines(None, games, k, lines_cap)
+
+    def vsearch2_lines(self, variant: int, games, k: int, lines_cap: int | None = None):
+        """fnnue_vsearch2_lines: vsearch2 plus each ply's k best lines (search2_lines' shapes)."""
+        return self._search2_lines(int(variant), games, k, lines_cap)
+
+    def _search2_lines(self, variant, games, k, lines_cap):
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        k = int(k)
+        out = np.zeros(max(cap, 1), dtype=BEST2_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        lcap = cap * max(k, 0) if lines_cap is None else int(lines_cap)
+        lines = np.zeros(max(lcap, 1), dtype=LINE2_DTYPE)
+        n, g = C.c_size_t(), C.c_size_t()
+        self.last_counts = (n, g)  # set also when the call is refused (FNNUE_E_CAPACITY)
+        tail = (text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), k, N.ptr(out), cap, N.ptr(off), len(off),
+                N.ptr(lines), lcap, C.byref(n), C.byref(g))
+        if variant is None:
+            N.check(N.lib.fnnue_search2_lines(self._h, *tail))
+        else:
+            N.check(N.lib.fnnue_vsearch2_lines(self._h, variant, *tail))
+        return out[: n.value], off[: g.value + 1], lines[: n.value * k].reshape(n.value, k)
+
+    def search2_lines_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, k: int, d_out: int,
+                             cap: int, d_off: int, off_cap: int, d_lines: int, lines_cap: int,
+                             stream: int | None) -> tuple[int, int]:
+        """fnnue_search2_lines_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when a buffer is too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_search2_lines_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                 C.c_void_p(d_moves_off), ngames, int(k), C.c_void_p(d_out), cap,
+                                                 C.c_void_p(d_off), off_cap, C.c_void_p(d_lines), lines_cap,
+                                                 C.byref(n), C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    def vsearch2_lines_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, k: int,
+                              d_out: int, cap: int, d_off: int, off_cap: int, d_lines: int, lines_cap: int,
+                              stream: int | None) -> tuple[int, int]:
+        """fnnue_vsearch2_lines_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when a buffer is too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vsearch2_lines_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                  C.c_void_p(d_moves_off), ngames, int(k), C.c_void_p(d_out), cap,
+                                                  C.c_void_p(d_off), off_cap, C.c_void_p(d_lines), lines_cap,
+                                                  C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
     def perft_device(self, fen: str, depth: int) -> int:

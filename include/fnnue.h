@@ -710,6 +710,79 @@ int fnnue_vsearch2_children(fnnue_ctx *ctx, int variant, const char *text, size_
                             size_t off_cap, fnnue_best *child_best, uint32_t *child_map, size_t child_cap,
                             size_t *n_out, size_t *n_groups, size_t *n_children);
 
+/* ---- MultiPV at two plies: the k best lines of a ply (ABI 3.11) ----
+ * The second reduction's key extended to a total order, as fnnue_topk_children
+ * extends the first's (the tie-break, the lower child index, is part of the
+ * key, so the keys of a group are unique).  Best first, chess ranks:
+ *   the mates in one, in index order;
+ *   the values descending (a stalemating move 0, any other child -b_c.value),
+ *     equal values by lower index;
+ *   the children whose reply mates (FNNUE_BEST_MATED), in index order.
+ * Variant ranks (descending fnnue_vbest_replies score): mate in one; every
+ * reply loses at once (FNNUE_BEST_MATE, pv c, b_c.move); the values; the reply
+ * wins at once (FNNUE_BEST_MATED); the FNNUE_END_WON children (FNNUE_BEST_LOST,
+ * a one-move pv); each class in index order, the values as above. */
+typedef struct {
+  int32_t psqt, positional; /* of the pv's last position from the ply's side to move, exactly as fnnue_best2
+                               reports them when this child is the best: a two-move pv -> b_c's as they are;
+                               a one-move pv -> the child's own terms negated with wrap-around */
+  int32_t value;            /* FNNUE_BEST_CP only, else 0 */
+  uint32_t child;           /* 1-based record index in the ply's group */
+  uint32_t reply_index;     /* 0 for a one-move pv */
+  fnnue_move move, reply;   /* reply 0 for a one-move pv */
+  uint8_t kind;             /* FNNUE_BEST_CP / _MATE / _MATED / _LOST; FNNUE_BEST_NONE = unused slot (all zero) */
+  uint8_t pv_len;           /* 1 or 2 */
+  uint16_t reserved;        /* 0 */
+} fnnue_line2;
+/* The ranking alone, one kernel on `stream` (no atomics, no host
+ * synchronisation): fnnue_best_replies' arrays (end, moves or NULL, off,
+ * child_best: dense, in record order; offsets beyond npos are clamped) and
+ * fnnue_topk_children's slots: group g owns lines[line_off[g] .. line_off[g + 1])
+ * (ngroups + 1 non-decreasing entries; the count may differ per group), slot j
+ * receives the j-th child in the order above, slots beyond the group's children
+ * are written all-zero, an empty group or one without a slot writes nothing.
+ * Slot 0 equals the group's fnnue_best2 on every shared field (psqt,
+ * positional, value, best == child, reply_index, move, reply, kind, pv_len).
+ * The device form never writes at or beyond lines_cap; the host form refuses
+ * line_off[ngroups] > lines_cap with FNNUE_E_CAPACITY.  fnnue_vtopk_replies:
+ * the variants' ranks; npos > 2^32 - 1 is FNNUE_E_ARG.  Any net. */
+int fnnue_topk_replies_device(fnnue_ctx *ctx, const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                              size_t ngroups, size_t npos, const fnnue_best *d_child_best,
+                              const uint32_t *d_line_off, fnnue_line2 *d_lines, size_t lines_cap, void *stream);
+int fnnue_topk_replies(fnnue_ctx *ctx, const uint8_t *end, const fnnue_move *moves, const uint32_t *off,
+                       size_t ngroups, size_t npos, const fnnue_best *child_best, const uint32_t *line_off,
+                       fnnue_line2 *lines, size_t lines_cap);
+int fnnue_vtopk_replies_device(fnnue_ctx *ctx, const uint8_t *d_end, const fnnue_move *d_moves, const uint32_t *d_off,
+                               size_t ngroups, size_t npos, const fnnue_best *d_child_best,
+                               const uint32_t *d_line_off, fnnue_line2 *d_lines, size_t lines_cap, void *stream);
+int fnnue_vtopk_replies(fnnue_ctx *ctx, const uint8_t *end, const fnnue_move *moves, const uint32_t *off,
+                        size_t ngroups, size_t npos, const fnnue_best *child_best, const uint32_t *line_off,
+                        fnnue_line2 *lines, size_t lines_cap);
+/* fnnue_search2[_device] / fnnue_vsearch2[_device] plus, per ply p, its k best
+ * lines at lines[p * k .. p * k + k) (k in 1..FNNUE_MAX_CHILDREN, anything else
+ * FNNUE_E_ARG; a crazyhouse ply may have more children, k stays 1..218).  The
+ * fnnue_best2 records and the offsets are fnnue_[v]search2's byte for byte;
+ * the ranking runs once after the last chunk, beside the second reduction, and
+ * adds no host wait.  The capacity protocol is fnnue_search1_lines':
+ * lines_cap < plies * k is FNNUE_E_CAPACITY too (before anything is expanded,
+ * *n_out set).  Nets and errors as fnnue_search2 / fnnue_vsearch2. */
+int fnnue_search2_lines_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off,
+                               const uint32_t *d_moves_off, size_t ngames, uint32_t k, fnnue_best2 *d_out, size_t cap,
+                               uint32_t *d_off, size_t off_cap, fnnue_line2 *d_lines, size_t lines_cap, size_t *n_out,
+                               size_t *n_groups, void *stream);
+int fnnue_search2_lines(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                        const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best2 *out, size_t cap,
+                        uint32_t *off, size_t off_cap, fnnue_line2 *lines, size_t lines_cap, size_t *n_out,
+                        size_t *n_groups);
+int fnnue_vsearch2_lines_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                                const uint32_t *d_moves_off, size_t ngames, uint32_t k, fnnue_best2 *d_out,
+                                size_t cap, uint32_t *d_off, size_t off_cap, fnnue_line2 *d_lines, size_t lines_cap,
+                                size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_vsearch2_lines(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                         const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best2 *out, size_t cap,
+                         uint32_t *off, size_t off_cap, fnnue_line2 *lines, size_t lines_cap, size_t *n_out,
+                         size_t *n_groups);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

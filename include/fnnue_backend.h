@@ -358,8 +358,8 @@ int fnnue_backend_analysis_json_lines(const fnnue_position_response *r, size_t n
  * side to move).  A ply without a legal move is answered as at depth 0;
  * skipped ids, move work and variant batches are unchanged; go_compact gives
  * score and depth only.  fnnue_backend_go_lines on a 2-plies channel behaves
- * as on a 1-ply channel: depth-1 responses and lines (MultiPV at two plies is
- * not built).  Pieces are cut at a 1024th of FNNUE_BACKEND_PIECE_PLIES (at
+ * as on a 1-ply channel: depth-1 responses and lines; MultiPV at two plies is
+ * fnnue_backend_go_lines_pv (below).  Pieces are cut at a 1024th of FNNUE_BACKEND_PIECE_PLIES (at
  * least 16 plies), so that a piece's grandchildren (about 1000 per ply) take
  * the room a depth-0 piece's plies do; each piece has two bounded sizing waits
  * (children, grandchildren) inside the call's budget; a piece with a rejected
@@ -402,9 +402,56 @@ int fnnue_backend_analysis_json_pv(const fnnue_position_response *r, size_t n, c
  * chess cut measured fastest on crazyhouse), two bounded sizing waits per piece, a
  * piece with a rejected game skips the search and is recovered as at depth 1,
  * positions counts plies + children + grandchildren.  fnnue_backend_go_lines on
- * such a channel is a one-ply search with lines, as on a one-ply channel.  Move
- * work is unchanged. */
+ * such a channel is a one-ply search with lines, as on a one-ply channel;
+ * fnnue_backend_go_lines_pv gives the k best two-move lines.  Move work is
+ * unchanged. */
 int fnnue_backend_set_variant_analysis_plies(fnnue_backend *b, int plies);
+
+/* ---- MultiPV at two plies (ABI 3.11) ----
+ * One line of a response with its whole pv, as the reference keeps one
+ * Vec<Uci> per MultiPV line at the searched depth ([ref] src/ipc.rs:68-93). */
+typedef struct {
+  int64_t score;        /* as fnnue_pv_line */
+  int32_t psqt;         /* of the pv's last position, from the ply's side to move (fnnue_line2) */
+  int32_t positional;
+  char pv[14];          /* "e7e8q e2e1q": one or two UCI moves, space-separated, NUL-terminated; variant moves
+                           as fnnue_vmove_uci spells them ("N@f3 e7e5") */
+  uint8_t score_kind;   /* FNNUE_SCORE_* */
+  uint8_t pv_len;       /* 1 or 2 */
+} fnnue_pv_line2;
+/* fnnue_backend_go_lines with every line's whole pv, and fnnue_backend_go_pv's
+ * `reply` (cap entries, or NULL).  The responses and the replies are
+ * fnnue_backend_go_pv's on the same channel, field by field but for time_ms /
+ * nps: the call searches at the channel's own plies.  A response has lines iff
+ * it belongs to an analysis batch with multipv >= 1, it is not skipped, its
+ * ply has a legal move and its net's setting (chess and the variants each have
+ * their own) is at one or two plies.  At two plies it has min(multipv, the
+ * ply's legal moves) lines in fnnue_topk_replies' order (the variants:
+ * fnnue_vtopk_replies'), line 0 being the response's own score, score_kind,
+ * best move, reply, psqt and positional; scores are Cp(value * 100 /
+ * normalize_to_pawn), Mate(1) for FNNUE_BEST_MATE, Mate(-1) for
+ * FNNUE_BEST_MATED and FNNUE_BEST_LOST.  At one ply the lines are
+ * fnnue_backend_go_lines' own in this record, pv_len 1.  Every other response
+ * has none.  fnnue_backend_lines_bound stays the bound: lines_cap below it is
+ * FNNUE_E_CAPACITY before any work.  One more kernel per piece
+ * (fnnue_topk_replies_device's, beside the second reduction), the lines travel
+ * in the piece's results image; no new wait; budget, errors and the recovery
+ * of a piece with a rejected game as fnnue_backend_go_timeout. */
+int fnnue_backend_go_lines_pv(fnnue_backend *b, const fnnue_acquired *batches, size_t nbatches,
+                              fnnue_position_response *out, size_t cap, uint32_t *off, int32_t *batch_rc,
+                              fnnue_pv_line2 *lines, size_t lines_cap, uint32_t *line_off, fnnue_move *reply,
+                              uint32_t timeout_ms);
+/* fnnue_backend_analysis_json_lines for these lines: a response with L >= 1
+ * lines at depth d is L rows of d nulls and the entry, each entry holding that
+ * line's own pv whatever its length: {"pv":[[null,null,["e2e4","e7e5"]],
+ * [null,null,["d2d4","d7d5"]]],"score":[[null,null,{"cp":31}],[null,null,
+ * {"cp":28}]],"depth":2,...}.  A response with one line prints as
+ * fnnue_backend_analysis_json_pv prints it with that line's reply; a response
+ * without lines, or not in `matrix` form, as fnnue_backend_analysis_json_pv
+ * prints it without a reply (the call takes none: a batch that is not in
+ * matrix form goes through fnnue_backend_analysis_json_pv with its replies). */
+int fnnue_backend_analysis_json_lines_pv(const fnnue_position_response *r, size_t n, const fnnue_pv_line2 *lines,
+                                         const uint32_t *line_off, char *buf, size_t cap, size_t *len);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Times of the two-ply search (fnnue_search2_device) and of the engine actor
 at two plies.  GPU box only.  One JSON line per measurement.
 
-    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor]
+    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218]
                                   [--variant crazyhouse|atomic|kingofthehill|racingkings|threecheck]
 
 The shape: N random legal games of L plies each from the start position
@@ -18,8 +18,13 @@ the grandchild expansion, their STAR evaluation and the first reduction, and
 the second reduction.  records_per_s counts the records each search evaluates
 (search1: plies + children; search2: the grandchild records, which hold every
 child once more).
+`--lines K,...` adds fnnue_[v]search2_lines_device at those k (phases
+search2_lines_kK, in the same process on the same games, behind search2), and
+the traced call then runs with the first k, so that its line carries the
+ranking kernel's own time (topk_ms).
 `--actor` adds the engine actor's go_pv() at 1 and 2 plies on 1 and 64
-lichess-shaped chess batches.
+lichess-shaped chess batches; with `--lines` also go_lines_pv() on the same
+2-plies channel and the same batches asking for multipv 3.
 `--variant NAME` measures fnnue_vsearch1_device / fnnue_vsearch2_device on
 random legal games of that variant instead (a synthetic variant net; the atomic
 net for kingofthehill, racingkings and threecheck), and with `--actor` the
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--variant", choices=sorted(VARIANTS), default=None)
     ap.add_argument("--piece-plies", default="")
+    ap.add_argument("--lines", default="")
     a = ap.parse_args()
     import torch
     import fishnet_amd as F
@@ -99,7 +105,20 @@ def main():
         else:
             ev.search2_device(T, FO, MO, ng, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1, S)
 
-    phases = [("search1", search1), ("search2", search2)]
+    ks = [int(x) for x in a.lines.split(",") if x]
+    d_lines = torch.zeros((plies * max(ks + [0]), N.LINE2_BYTES), dtype=torch.uint8, device=dev)
+
+    def search2_lines(k):
+        def run():
+            if a.variant:
+                ev.vsearch2_lines_device(vid, T, FO, MO, ng, k, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1,
+                                         d_lines.data_ptr(), plies * k, S)
+            else:
+                ev.search2_lines_device(T, FO, MO, ng, k, d_b2.data_ptr(), plies, d_goff.data_ptr(), ng + 1,
+                                        d_lines.data_ptr(), plies * k, S)
+        return run
+
+    phases = [("search1", search1), ("search2", search2)] + [(f"search2_lines_k{k}", search2_lines(k)) for k in ks]
 
     def once(timed):
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)] if timed else None
@@ -139,7 +158,7 @@ def main():
     os.environ["FNNUE_SEARCH2_TRACE"] = "1"
     for _ in range(a.runs):
         with torch.cuda.stream(stream):
-            search2()
+            (search2_lines(ks[0]) if ks else search2)()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     ev.close()
@@ -177,6 +196,23 @@ def actor_lines(a):
                               "positions_per_s": round(stats["positions"] / (med * 1e-3)),
                               "last_stats": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats.items()}}),
                   flush=True)
+            if n == 2 and a.lines:  # MultiPV 3 on the same channel and batches: go_lines_pv() beside go_pv()
+                asking = [B.AcquireResponseBody(b.batch_id, b.position, b.moves, b.work, b.variant, b.skip_positions, 3)
+                          for b in bodies]
+                for name, fn, bs in (("go_pv", stub.go_pv, asking), ("go_lines_pv", stub.go_lines_pv, asking)):
+                    t0 = time.perf_counter()
+                    fn(bs)
+                    while time.perf_counter() - t0 < 0.3:
+                        fn(bs)
+                    calls = []
+                    for _ in range(a.runs):
+                        res = fn(bs)
+                        calls.append(stub.last_call_s * 1e3)
+                    calls.sort()
+                    nlines = sum(len(r.lines or ()) for rows in res for r in rows)
+                    print(json.dumps({"actor_plies": 2, "call": name, "multipv": 3, "batches": nb, "plies": plies,
+                                      "lines": nlines, "ms_per_call": [round(x, 3) for x in calls],
+                                      "median_ms": round(calls[len(calls) // 2], 3)}), flush=True)
             actor.close()
 
 
