@@ -118,14 +118,22 @@ __global__ __launch_bounds__(kScatterPositions) void plan_scatter_kernel(const f
 // the end of the unit holds the clamped last item and rewrites its identical
 // values (a store skipped on some path would make hipcc's vmcnt bookkeeping
 // wait for every store before the next pass's rows).
-template <int HD, bool kSwar, bool kPsqt, int kPStride>
-__device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict__ lb, int lane, int it_in_wave, int s,
-                                           int q, const char* base, u16x4 b_lo, u16x4 b_hi, int krow,
-                                           const int32_t* ptile, __amdgpu_buffer_rsrc_t psqt_rsrc,
-                                           __amdgpu_buffer_rsrc_t x_rsrc) {
+//
+// kClaim: the wave also claims its next pass(es) of the unit from the
+// workgroup's counter (claim_passes) and returns the claim, still in flight.
+// The add goes ahead of the list-buffer write: the pass waits for its list
+// reads before the first row, so the claim has returned long before the next
+// pass's fetch asks for it and adds no wait of its own.
+template <int HD, bool kSwar, bool kPsqt, int kPStride, bool kClaim>
+__device__ __forceinline__ uint32_t slice_pass(const PassFetch& f, uint2* __restrict__ lb, int lane, int it_in_wave,
+                                               int s, int q, const char* base, u16x4 b_lo, u16x4 b_hi, int krow,
+                                               const int32_t* ptile, __amdgpu_buffer_rsrc_t psqt_rsrc,
+                                               __amdgpu_buffer_rsrc_t x_rsrc, uint32_t* next_pass) {
   constexpr int kLastItemLane = 48;  // lane_item: lane 48 holds pass item 7, the longest list
   const uint32_t rec = f.rec;
   const int maxn = (int)(__builtin_amdgcn_readlane(rec, kLastItemLane) >> 24);
+  uint32_t claim = 0;
+  if constexpr (kClaim) claim = claim_passes(next_pass, lane);
   // LDS ops of one wave complete in order: this write lands after the previous
   // pass's reads of lb and before this pass's reads.
   lb[lane] = f.lst;
@@ -168,6 +176,7 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
     __builtin_amdgcn_raw_buffer_store_b32((int32_t)a2, psqt_rsrc,
                                           (lane & 7) == 0 ? (reci & kItemRowMask) * 4u : kDroppedOffset, 0, 0);
   }
+  return claim;
 }
 
 // The LDS of a workgroup (tile, PSQT tile, one list buffer per wave), declared
@@ -175,7 +184,8 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
 #define FT_SLICES_LDS(G)                                                                                      \
   __shared__ uint4 img[G::kTileU4];                                                                           \
   __shared__ int32_t ptile[psqt_tile_words(G::kTileRows)]; /* slice 0 only: PSQT rows, bucket-major */        \
-  __shared__ uint2 lbuf[16][64];                         /* per wave: one pass's 8 feature lists */
+  __shared__ uint2 lbuf[16][64];                         /* per wave: one pass's 8 feature lists */        \
+  __shared__ uint32_t next_pass;                         /* the unit's claim counter (claim_passes) */
 
 // One workgroup = one (unit, slice).  16 waves x 8 items per pass; records and
 // lists are fetched two passes ahead while the current pass reads the LDS tile.
@@ -184,7 +194,7 @@ __device__ __forceinline__ void slice_pass(const PassFetch& f, uint2* __restrict
 // words on its way into LDS and rows are summed as 32-bit words (swar_tile_words).
 // Tiles sit in HBM as plain int16 either way, so the choice is the slice's own.
 template <int HD, bool kSwar, class G>
-__device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2 (*lbuf)[64],
+__device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2 (*lbuf)[64], uint32_t* next_pass,
                                                const uint4* __restrict__ tiles,
                                                const int16_t* __restrict__ ftb, const uint32_t* __restrict__ ctr,
                                                const int4* __restrict__ units, const uint32_t* __restrict__ items,
@@ -233,9 +243,9 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
   const __amdgpu_buffer_rsrc_t flist_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(flist), 0, kBufferAll, kBufferFlags);
   const int last = u.z - 1;
-  int base = u.y + wv * 8;
-  PassFetch fa = fetch_pass(items_rsrc, flist_rsrc, base, last, lane, it_in_wave);
-  PassFetch fb = fetch_pass(items_rsrc, flist_rsrc, base + 128, last, lane, it_in_wave);
+  int base_a = u.y + wv * 8, base_b = base_a + 128;  // the wave's own two passes
+  PassFetch fa = fetch_pass(items_rsrc, flist_rsrc, base_a, last, lane, it_in_wave);
+  PassFetch fb = fetch_pass(items_rsrc, flist_rsrc, base_b, last, lane, it_in_wave);
 #pragma unroll
   for (int k = 0; k < kTileLoads; ++k)
     if ((int)threadIdx.x + 1024 * k < kTileU4) {
@@ -257,7 +267,9 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
       }
     }
   }
+  if (threadIdx.x == 0) *next_pass = claim_start();  // passes 0..31 are the waves' own
   __syncthreads();
+  uint32_t claim = claim_passes(next_pass, lane);  // in flight under the king row's read
   {  // the own-king row (every item of the unit has it) joins the bias
     const u32x4 kv = *reinterpret_cast<const u32x4*>(lbase + 16 * krow);
     if constexpr (kSwar) {
@@ -272,20 +284,31 @@ __device__ __forceinline__ void ft_slices_body(uint4* img, int32_t* ptile, uint2
   }
   // Slice 0 also sums the PSQT part; the other slices run a copy of the loop
   // without that code (a runtime branch in the shared loop cost them 8 %).
+  // base_a / base_b: the first item of the pass that fa / fb holds.  A wave's
+  // passes come in increasing order (wv, wv + 16, then its claims, each made
+  // after the one before), so the first pass at or past u.z ends the wave:
+  // whatever fa / fb still hold then lies past the unit as well, was fetched
+  // clamped and is dropped unprocessed.  Each claim refills the register set
+  // whose pass was just taken, two passes ahead of its use, and is made one
+  // pass before that fetch (slice_pass).
   auto run = [&](auto psqt) {
     constexpr bool kPsqt = decltype(psqt)::value;
-    while (base < u.z) {
+    constexpr bool kClaimB = kClaimPasses == 1;  // two per claim: the second pass makes none
+    while (base_a < u.z) {
       const PassFetch cur = fa;
-      fa = fetch_pass(items_rsrc, flist_rsrc, base + 256, last, lane, it_in_wave);
-      slice_pass<HD, kSwar, kPsqt, kPStride>(cur, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile, psqt_rsrc,
-                                             x_rsrc);
-      base += 128;
-      if (base >= u.z) break;
+      const int na = u.y + 8 * claimed_pass(claim);
+      fa = fetch_pass(items_rsrc, flist_rsrc, na, last, lane, it_in_wave);
+      claim = slice_pass<HD, kSwar, kPsqt, kPStride, true>(cur, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile,
+                                                           psqt_rsrc, x_rsrc, next_pass);
+      base_a = na;
+      if (base_b >= u.z) break;
       const PassFetch cur2 = fb;
-      fb = fetch_pass(items_rsrc, flist_rsrc, base + 256, last, lane, it_in_wave);
-      slice_pass<HD, kSwar, kPsqt, kPStride>(cur2, lb, lane, it_in_wave, s, q, lbase, b_lo, b_hi, krow, ptile,
-                                             psqt_rsrc, x_rsrc);
-      base += 128;
+      const int nb = kClaimPasses == 1 ? u.y + 8 * claimed_pass(claim) : na + 8;
+      fb = fetch_pass(items_rsrc, flist_rsrc, nb, last, lane, it_in_wave);
+      const uint32_t c2 = slice_pass<HD, kSwar, kPsqt, kPStride, kClaimB>(cur2, lb, lane, it_in_wave, s, q, lbase, b_lo,
+                                                                          b_hi, krow, ptile, psqt_rsrc, x_rsrc, next_pass);
+      if constexpr (kClaimB) claim = c2;
+      base_b = nb;
     }
   };
   if (s == 0)
@@ -305,7 +328,7 @@ __global__ __launch_bounds__(1024) void ft_slices_kernel(const uint4* __restrict
                                                          int32_t* __restrict__ psqt_part,
                                                          uint8_t* __restrict__ x) {
   FT_SLICES_LDS(G)
-  ft_slices_body<HD, kSwar, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+  ft_slices_body<HD, kSwar, G>(img, ptile, lbuf, &next_pass, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
 }
 
 // A net whose slices do not all pass the SWAR bound (slice_bounds in net.h):
@@ -325,9 +348,9 @@ __global__ __launch_bounds__(1024) void ft_slices_mixed_kernel(const uint4* __re
   FT_SLICES_LDS(G)
   const uint32_t s = (blockIdx.x >> 3) % S;
   if ((swar >> s) & 1)
-    ft_slices_body<HD, true, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+    ft_slices_body<HD, true, G>(img, ptile, lbuf, &next_pass, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
   else
-    ft_slices_body<HD, false, G>(img, ptile, lbuf, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
+    ft_slices_body<HD, false, G>(img, ptile, lbuf, &next_pass, tiles, ftb, ctr, units, items, flist, psqw, psqt_part, x);
 }
 
 template <int HD>

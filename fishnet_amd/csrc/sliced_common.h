@@ -555,6 +555,33 @@ __device__ __forceinline__ PassFetch fetch_pass(__amdgpu_buffer_rsrc_t items, __
   return f;
 }
 
+#ifndef FT_CLAIM
+#define FT_CLAIM 2
+#endif
+// Passes of a unit are numbered from its first item, 8 items each.  A wave of
+// ft_slices owns passes wv and wv + 16; every later pass is claimed from one
+// LDS word of the workgroup, so a wave that runs ahead takes more passes and
+// the sixteen waves of a task end within a few passes of each other.
+// kClaimPasses = passes per claim: 1, or 2 (one for each of the loop's two
+// fetch registers; the faster of the two on every workload).
+// The word counts claims, the first unclaimed pass is
+// kClaimPasses times it (claim_start after the tile barrier = pass 32).  One
+// lane increments it and the returned count stays in flight in a VGPR until
+// claimed_pass() makes it wave-uniform where the next fetch needs it.  The
+// increment is ds_inc_rtn_u32 with no wrap, not a fetch-add: hipcc rewrites an
+// LDS fetch-add into a wave reduction that waits for the result on the spot.
+constexpr int kClaimPasses = FT_CLAIM;
+static_assert(kClaimPasses == 1 || kClaimPasses == 2, "FT_CLAIM: 1 or 2 passes per claim");
+constexpr uint32_t claim_start() { return 32 / kClaimPasses; }
+__device__ __forceinline__ uint32_t claim_passes(uint32_t* next_claim, int lane) {
+  uint32_t c = 0;
+  if (lane == 0) c = __builtin_amdgcn_atomic_inc32(next_claim, 0xFFFFFFFFu, __ATOMIC_RELAXED, "workgroup");
+  return c;
+}
+__device__ __forceinline__ int claimed_pass(uint32_t claim) {
+  return kClaimPasses * __builtin_amdgcn_readfirstlane((int)claim);
+}
+
 // LDS byte address of this lane's chunk of the row named by the low / high u16
 // entry of `word`: base (= plane q) + entry; hipcc emits one v_add_u32_sdwa.
 __device__ __forceinline__ const u32x4* row_addr(const char* base, uint32_t word, int t) {

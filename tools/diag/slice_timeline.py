@@ -2,8 +2,10 @@
 (tools/exp/diag_slicetrace.patch -> exp/libfnnue_diag_slicetrace.so): which CU /
 XCD ran each task, when it started, when each of its 16 waves finished, and
 the unit's item range.  Reports, for config 2's positions: per-XCD last end,
-CU occupancy per twentieth of the launch, slice-0 tasks against the others, and
-a least-squares fit of the task duration
+CU occupancy per twentieth of the launch, slice-0 tasks against the others, how
+far apart the sixteen waves of a task end (wave_ends: first-to-last end over the
+task's duration, mean live waves; mean / p50 / p90, slice 0 / others), and a
+least-squares fit of the task duration
 
     us = fill + passes * a + rows * b        (x slice0 for slice-0 tasks)
 
@@ -23,6 +25,36 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def wave_end_spread(start, ends, passes, sl):
+    """How the sixteen waves of a task end (all times in ns; ends[task, wave]).
+    spread_frac: first-to-last wave end over the task's duration.  live_waves:
+    the mean number of waves still running over the task, sum of the waves'
+    lifetimes over the task's duration (16 = all waves end together).
+    spread_over_pass: the spread in units of the task's own mean pass step
+    (duration / 128-item pass steps).  Tasks of fewer than 16 passes leave
+    waves idle from the start and are reported apart (short_tasks)."""
+    dur = (ends.max(axis=1) - start).astype(np.float64)
+    spread = (ends.max(axis=1) - ends.min(axis=1)).astype(np.float64)
+    live = (ends - start[:, None]).sum(axis=1) / dur
+
+    def stats(v):
+        if len(v) == 0:
+            return None
+        return {"mean": round(float(v.mean()), 4), "p50": round(float(np.median(v)), 4),
+                "p90": round(float(np.percentile(v, 90)), 4)}
+
+    out = {}
+    full = passes >= 2  # every wave has at least its two static passes
+    for name, m in (("all", full), ("slice0", full & (sl == 0)), ("others", full & (sl != 0))):
+        out[name] = {"tasks": int(m.sum()), "spread_frac": stats(spread[m] / dur[m]), "live_waves": stats(live[m]),
+                     "spread_us": stats(spread[m] / 1e3),
+                     "spread_over_pass": stats(spread[m] / (dur[m] / passes[m]))}
+    out["short_tasks"] = int((~full).sum())
+    # time-weighted: the share of resident wave slots that hold a running wave
+    out["live_waves_time_weighted"] = round(float((ends - start[:, None]).sum() / dur.sum()), 3)
+    return out
 
 
 def main():
@@ -95,6 +127,7 @@ def main():
         for a, b in zip(edges[:-1], edges[1:])]
     res["task_us_by_slice"] = {"slice0": round(float(dur[sl == 0].mean()) / 1e3, 2),
                                "others": round(float(dur[sl != 0].mean()) / 1e3, 2)}
+    res["wave_ends"] = wave_end_spread(start, ends, passes, sl)
     fit = {}
     for name, m in (("others", sl != 0), ("slice0", sl == 0)):
         A = np.stack([np.ones(m.sum()), passes[m], rows[m]], axis=1)

@@ -4,7 +4,7 @@
 # never edited: the csrc tree is copied to build/exp_<name>/, the optional
 # patch (git diff format, paths relative to the repo root) is applied there,
 # extra -D flags (the tunables FT_UNIT_WORK, FT_UNIT_ITEMS, SEG_UNIT_PLIES, PLAN_WG,
-# FT_DEPTH) go to every HIP source.
+# FT_DEPTH, FT_CLAIM) go to every HIP source.
 #   usage: tools/exp_build.sh <name> [file.patch] [-DFLAG ...]
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
