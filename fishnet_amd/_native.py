@@ -38,6 +38,8 @@ PV_LINE_BYTES = 24  # fnnue_pv_line
 LINE2_BYTES = 28  # fnnue_line2
 PV_LINE2_BYTES = 32  # fnnue_pv_line2
 MAX_CHILDREN = 218  # FNNUE_MAX_CHILDREN
+END_DRAW = 0x10  # FNNUE_END_DRAW
+PLY_HISTORY_BYTES = 4  # fnnue_ply_history
 VPOS_BYTES = 48
 
 
@@ -208,6 +210,14 @@ SIGNATURES = {
                               _P(_sz)], _i32),
     "fnnue_backend_go_lines_pv": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32], _i32),
     "fnnue_backend_analysis_json_lines_pv": ([_vp, _sz, _vp, _vp, C.c_char_p, _sz, _P(_sz)], _i32),
+    # repetition and fifty-move draws (ABI 3.12)
+    "fnnue_game_history": ([C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_game_history_device": ([_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_ctx_game_history": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_set_search_draws": ([_vp, _i32], _i32),
+    "fnnue_get_search_draws": ([_vp, _P(_i32)], _i32),
+    "fnnue_backend_set_draw_rules": ([_vp, _i32], _i32),
+    "fnnue_backend_draw_rules": ([_vp, _P(_i32)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

@@ -346,6 +346,16 @@ class GpuEvalStub:
         search per variant analysis ply under the variant's rules (the reply in go_pv's rows, drops included)."""
         N.check(N.lib.fnnue_backend_set_variant_analysis_plies(self._actor._h, int(plies)))
 
+    def set_draw_rules(self, on: bool) -> None:
+        """fnnue_backend_set_draw_rules: chess analysis batches at 1 or 2 plies score the moves that repeat a
+        position for the third time or reach the fifty-move rule as draws (Cp 0, the pv ends there)."""
+        N.check(N.lib.fnnue_backend_set_draw_rules(self._actor._h, 1 if on else 0))
+
+    def draw_rules(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_backend_draw_rules(self._actor._h, C.byref(on)))
+        return bool(on.value)
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -375,7 +385,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
             atomic=None, kingofthehill=None, racingkings=None, threecheck=None, timeout_ms: int = 0,
             analysis_depth: int = 0, variant_analysis_depth: int = 0,
             analysis_plies: int | None = None,
-            variant_analysis_plies: int | None = None) -> tuple[GpuEvalStub, GpuEvalActor]:
+            variant_analysis_plies: int | None = None,
+            draw_rules: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -385,7 +396,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     for the variant nets' batches (GpuEvalStub.set_variant_analysis_depth); `analysis_plies`: 0, 1 or 2
     (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`); `variant_analysis_plies`: 0, 1
     or 2 for the variant nets' batches (GpuEvalStub.set_variant_analysis_plies; it takes the place of
-    `variant_analysis_depth`)."""
+    `variant_analysis_depth`); `draw_rules`: repetition and fifty-move draws in the chess searches
+    (GpuEvalStub.set_draw_rules; off by default)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -408,6 +420,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_analysis_plies(analysis_plies)
     if variant_analysis_plies is not None:
         stub.set_variant_analysis_plies(variant_analysis_plies)
+    if draw_rules:
+        stub.set_draw_rules(True)
     return stub, actor
 
 

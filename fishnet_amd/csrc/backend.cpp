@@ -471,6 +471,7 @@ struct fnnue_backend {
   // fnnue_backend_set_analysis_depth / _plies: 1 = a one-ply search per chess analysis ply, 2 = two plies
   int analysis_depth = 0;
   int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
+  bool draw_rules = false;  // fnnue_backend_set_draw_rules: repetition and fifty-move draws in the chess searches
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
   int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
@@ -943,6 +944,20 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                                         static_cast<fnnue_pos*>(kp), km, ke, s)
                 : vchildren_write_device(k, states, n, coff, (uint32_t)total, static_cast<fnnue_vpos*>(kp), km, ke, s),
           "children launch");
+  // The draw rules (fnnue_backend_set_draw_rules, chess batches): a piece holds
+  // whole games (plan() never cuts one), so the history of its plies is
+  // complete; the marks go on the listed plies' children here and on their
+  // grandchildren behind the second expansion, before the reductions.
+  const bool draws = chess && draw_rules;
+  DrawHistory hist;
+  if (draws) {
+    HIP_TRY(game_history_device(dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
+                                reinterpret_cast<const uint32_t*>(dimg + P.o_mv),
+                                reinterpret_cast<const uint32_t*>(dimg + P.o_ply), P.ng,
+                                static_cast<const DBoard*>(states), n, draw_key_bits(), s, W.bscratch, &hist),
+            "game history launch");
+    HIP_TRY(mark_draws_level1(hist, static_cast<const DBoard*>(states), n, coff, km, ke, s), "draw marks launch");
+  }
   if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(kp), coff, n, total, FNNUE_GROUP_STAR,
                                                 kps, kpo, s)
                      : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(kp), coff, n, total,
@@ -993,6 +1008,10 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                     : vchildren_write_device(k, ks, (uint32_t)nkid, goff, (uint32_t)gtotal,
                                              static_cast<fnnue_vpos*>(gp), gm, ge, s),
               "grandchildren launch");
+      if (draws)
+        HIP_TRY(mark_draws_level2(hist, static_cast<const DBoard*>(states), 0, n, coff, static_cast<const DBoard*>(ks),
+                                  goff, 0, gm, ge, s),
+                "draw marks launch");
       if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(gp), goff, nkid, gtotal,
                                                     FNNUE_GROUP_STAR, gps, gpo, s)
                          : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(gp), goff, nkid, gtotal,
@@ -1000,6 +1019,8 @@ int fnnue_backend::stage_search(int k, size_t pi) {
         return rc;
       HIP_TRY(launch_best_children_own(gps, gpo, ge, gm, goff, (uint32_t)nkid, (uint32_t)gtotal, kb, s),
               "best_children launch");
+      if (draws)  // a drawn child's pv ends at it: its own terms into its record
+        HIP_TRY(draw_own_terms(hist, 0, n, coff, ke, goff, 0, gps, gpo, kb, s), "draw terms launch");
       P.searched += gtotal - nkid;
     }
     // the variant nets: the variant ranks (FNNUE_END_WON children, every reply loses at once)
@@ -1989,6 +2010,20 @@ int fnnue_backend_set_analysis_plies(fnnue_backend* b, int plies) {
   if (plies < 0 || plies > 2) return fail(FNNUE_E_ARG, "analysis plies 0, 1 or 2, not " + std::to_string(plies));
   std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
   b->analysis_depth = plies;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_draw_rules(fnnue_backend* b, int on) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->draw_rules = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_draw_rules(fnnue_backend* b, int* on) {
+  if (!b || !on) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);
+  *on = b->draw_rules ? 1 : 0;
   return FNNUE_OK;
 }
 

@@ -249,6 +249,26 @@ fnnue_pos Board::pack() const {
   return p;
 }
 
+bool BoardIdentity::operator==(const BoardIdentity& o) const {
+  return std::memcmp(sq, o.sq, 64) == 0 && stm == o.stm && ep == o.ep &&
+         std::memcmp(castle_rook, o.castle_rook, 4) == 0;
+}
+
+BoardIdentity Board::identity() const {
+  BoardIdentity id;
+  std::memcpy(id.sq, sq, 64);
+  id.stm = (int8_t)stm;
+  id.ep = -1;
+  if (ep >= 0 && ep < 64) {  // a pawn of the side to move attacks the square (pseudo-legal)
+    const int from_rank = (ep >> 3) + (stm == WHITE ? -1 : 1), f = ep & 7, own = make_piece(stm, PAWN);
+    if (from_rank >= 0 && from_rank < 8)
+      if ((f > 0 && sq[from_rank * 8 + f - 1] == own) || (f < 7 && sq[from_rank * 8 + f + 1] == own)) id.ep = (int8_t)ep;
+  }
+  for (int c = 0; c < 2; ++c)
+    for (int side = 0; side < 2; ++side) id.castle_rook[2 * c + side] = (int8_t)castle_rook[c][side];
+  return id;
+}
+
 std::string Board::fen() const {
   std::ostringstream o;
   for (int r = 7; r >= 0; --r) {

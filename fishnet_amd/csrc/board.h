@@ -27,6 +27,15 @@ struct Move {
   uint8_t castle;       // 1 if castling
 };
 
+// What makes two positions the same under the repetition rule (include/fnnue.h,
+// ABI 3.12): placement, side to move, castling rooks, and the en-passant square
+// only when a pawn of the side to move attacks it.
+struct BoardIdentity {
+  uint8_t sq[64];
+  int8_t stm, ep, castle_rook[4];
+  bool operator==(const BoardIdentity& o) const;
+};
+
 struct Board {
   uint8_t sq[64];       // piece code per square, 0 = empty
   uint64_t byColor[2];
@@ -57,6 +66,7 @@ struct Board {
   std::string fen() const;
   std::string uci(const Move& m, bool chess960_castling) const;
   fnnue_pos pack() const;
+  BoardIdentity identity() const;
 };
 
 // Parses a FEN (X-FEN/Shredder castling accepted). Returns false on malformed input.

@@ -457,6 +457,52 @@ BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, co
   return R;
 }
 
+BuildResult replay_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+                                 uint32_t ngames, size_t max_plies, hipStream_t s, BuilderScratch& ws,
+                                 const DBoard** d_states, const uint32_t** d_ply_off) {
+  BuildResult R;
+  auto fail = [&](hipError_t e) {
+    R.hip = e;
+    return R;
+  };
+  hipError_t e;
+  uint32_t *plies = nullptr, *ply_off = nullptr, *err = nullptr;
+  DBoard* states = nullptr;
+  using W = BuilderScratch;
+  if ((e = ws.get(W::kPlies, (size_t)(ngames + 1) * 4, (void**)&plies)) != hipSuccess) return fail(e);
+  if ((e = ws.get(W::kPlyOff, (size_t)(ngames + 1) * 4, (void**)&ply_off)) != hipSuccess) return fail(e);
+  if ((e = ws.get(W::kErr, 16, (void**)&err)) != hipSuccess) return fail(e);
+  if ((e = hipMemsetAsync(err, 0, 16, s)) != hipSuccess) return fail(e);
+  if ((e = hipMemsetAsync(plies + ngames, 0, 4, s)) != hipSuccess) return fail(e);
+  const uint32_t bs = 64;
+  hipLaunchKernelGGL(count_plies_kernel, dim3((ngames + bs - 1) / bs), dim3(bs), 0, s, d_text, d_fen_off, d_mv_off,
+                     ngames, plies);
+  if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+  if ((e = builder_exclusive_scan(plies, ply_off, ngames, s, ws)) != hipSuccess) return fail(e);
+  uint32_t total_plies = 0;
+  if ((e = hipMemcpyAsync(&total_plies, ply_off + ngames, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
+  R.n_out = total_plies;
+  R.n_groups = ngames;
+  if (total_plies > max_plies) {
+    R.capacity = true;
+    return R;
+  }
+  if ((e = ws.get(W::kStates, (size_t)total_plies * sizeof(DBoard), (void**)&states)) != hipSuccess) return fail(e);
+  if ((e = launch_chess_replay(d_text, d_fen_off, d_mv_off, ply_off, ngames, nullptr, states, nullptr, err, s)) !=
+      hipSuccess)
+    return fail(e);
+  uint32_t herr[4];
+  if ((e = hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
+  R.err_code = herr[0];
+  R.err_game = herr[1];
+  R.err_ply = herr[2];
+  *d_states = states;
+  *d_ply_off = ply_off;
+  return R;
+}
+
 hipError_t perft_device(const std::vector<DBoard>& frontier, int depth, uint64_t* nodes) {
   *nodes = 0;
   if (frontier.empty()) return hipSuccess;

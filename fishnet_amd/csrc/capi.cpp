@@ -405,7 +405,11 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //      fnnue_vsearch2_children, fnnue_backend_set_variant_analysis_plies
 // 3.11: MultiPV at two plies: fnnue_line2 / fnnue_[v]topk_replies[_device], fnnue_[v]search2_lines[_device],
 //       fnnue_backend_go_lines_pv, fnnue_backend_analysis_json_lines_pv
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 11u; }
+// 3.12: repetition and fifty-move draws in the device search: FNNUE_END_DRAW (honoured by the four
+//       reductions and their variant forms), fnnue_ply_history / fnnue_game_history[_device],
+//       fnnue_ctx_game_history, fnnue_set_search_draws / fnnue_get_search_draws,
+//       fnnue_backend_set_draw_rules / fnnue_backend_draw_rules
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 12u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1666,6 +1670,15 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
     kids.ply_off = vkids.ply_off;
   }
   if (rc) return rc;
+  if (variant == kVariantChess && ctx->search_draws) {
+    // the draw rules: the plies' history from the boards the replay left, then the marks on the listed plies' children
+    DrawHistory hist;
+    const DBoard* plies = static_cast<const DBoard*>(ctx->bscratch.p[BuilderScratch::kStates]);
+    HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, plies, (uint32_t)nply,
+                                draw_key_bits(), s, ctx->bscratch, &hist),
+            "game history launch");
+    HIP_TRY(mark_draws_level1(hist, plies, (uint32_t)nply, kids.off, kids.moves, kids.end, s), "draw marks launch");
+  }
   HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
           "best_children launch");
   if (k)
@@ -1955,7 +1968,7 @@ size_t search2_budget() {
 // prints the phases' device times to stderr, one JSON line — diagnostics only
 // (tools/search2_bench.py).
 struct Search2Trace {
-  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kPhases };
+  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kHistory, kMark, kPhases };
   bool on = false;
   hipStream_t s = nullptr;
   std::vector<std::pair<int, hipEvent_t>> marks;
@@ -1969,8 +1982,10 @@ struct Search2Trace {
     if (hipEventCreate(&ev) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) on = false;
     if (ev) marks.emplace_back(phase, ev);
   }
+  long listed = -1;  // the plies on the draw rules' list (read back for the report only)
   void report(size_t plies, size_t kids, size_t records, size_t chunks) {
-    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1", "reduce2", "topk"};
+    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1",
+                                               "reduce2", "topk", "history", "mark"};
     if (on && !marks.empty() && hipEventSynchronize(marks.back().second) == hipSuccess) {
       double ms[kPhases] = {};
       for (size_t i = 0; i + 1 < marks.size(); ++i) {
@@ -1980,6 +1995,7 @@ struct Search2Trace {
       std::string line = "FNNUE_SEARCH2_TRACE {\"plies\":" + std::to_string(plies) + ",\"children\":" +
                          std::to_string(kids) + ",\"grandchild_records\":" + std::to_string(records) +
                          ",\"chunks\":" + std::to_string(chunks);
+      if (listed >= 0) line += ",\"draw_list\":" + std::to_string(listed);
       for (int k = 0; k < kPhases; ++k) line += std::string(",\"") + kName[k] + "_ms\":" + std::to_string(ms[k]);
       std::fprintf(stderr, "%s}\n", line.c_str());
     }
@@ -2080,6 +2096,20 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
     HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
     return FNNUE_OK;
   }
+  // The draw rules (chess, fnnue_set_search_draws): the plies' history and the
+  // marks on the listed plies' children here, their grandchildren per chunk.
+  const bool draws = chess && ctx->search_draws;
+  DrawHistory hist;
+  if (draws) {
+    trace.mark(Search2Trace::kHistory);
+    HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames,
+                                static_cast<const DBoard*>(plies), (uint32_t)nply, draw_key_bits(), s, ws, &hist),
+            "game history launch");
+    trace.mark(Search2Trace::kMark);
+    HIP_TRY(mark_draws_level1(hist, static_cast<const DBoard*>(plies), (uint32_t)nply, kids.off, kids.moves, kids.end,
+                              s),
+            "draw marks launch");
+  }
   trace.mark(Search2Trace::kChildStates);
   if (chess)
     HIP_TRY(child_states_device(static_cast<const DBoard*>(plies), (uint32_t)nply, kids.off, (uint32_t)nrec,
@@ -2150,6 +2180,13 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
       HIP_TRY(vchildren_write_device(variant, chunk_states, nk, ch_off, nr, static_cast<fnnue_vpos*>(gpos), gmoves,
                                      gend, s),
               "children write");
+    if (draws) {  // behind the expansion, before the reduction reads the end bytes; offsets relative to the chunk
+      trace.mark(Search2Trace::kMark);
+      HIP_TRY(mark_draws_level2(hist, static_cast<const DBoard*>(plies), cuts[i], cuts[i + 1], kids.off,
+                                reinterpret_cast<const DBoard*>(kid_states), kid_off, first_rec[cuts[i]], gmoves, gend,
+                                s),
+              "draw marks launch");
+    }
     trace.mark(Search2Trace::kEval);
     rc = chess ? fnnue_eval_groups_device(ctx, static_cast<fnnue_pos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
                                           gpo, s)
@@ -2158,6 +2195,12 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
     if (rc) return rc;
     trace.mark(Search2Trace::kReduce1);
     HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
+    if (draws) {  // a drawn child's pv ends at it: its own terms, while the chunk still holds them
+      trace.mark(Search2Trace::kMark);
+      HIP_TRY(draw_own_terms(hist, cuts[i], cuts[i + 1], kids.off, kids.end, kid_off, first_rec[cuts[i]], gps, gpo,
+                             kid_best, s),
+              "draw terms launch");
+    }
   }
   trace.mark(Search2Trace::kReduce2);
   HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
@@ -2169,6 +2212,12 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
             "topk_replies launch");
   }
   trace.mark(Search2Trace::kPhases);
+  if (draws && trace.on) {
+    uint32_t listed = 0;
+    HIP_TRY(hipMemcpyAsync(&listed, hist.list, 4, hipMemcpyDeviceToHost, s), "D2H(draw list)");
+    HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+    trace.listed = (long)listed;
+  }
   trace.report(nply, nkid, all_rec, cuts.size() - 1);
   if (n_children && nkid)
     HIP_TRY(hipMemcpyAsync(d_child_best, kid_best, nkid * sizeof(fnnue_best), hipMemcpyDeviceToDevice, s),
@@ -2499,4 +2548,85 @@ int fnnue_random_game(uint64_t seed, const char* fen, uint32_t plies, char* move
   std::memcpy(moves, out.c_str(), out.size() + 1);
   return FNNUE_OK;
 }
+}  // extern "C"
+
+// ---- repetition and fifty-move draws (ABI 3.12; the kernels: draws.hip) ----
+extern "C" {
+
+int fnnue_set_search_draws(fnnue_ctx* ctx, int on) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  ctx->search_draws = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_get_search_draws(const fnnue_ctx* ctx, int* on) {
+  if (!ctx || !on) return fail(FNNUE_E_ARG, "null argument");
+  *on = ctx->search_draws ? 1 : 0;
+  return FNNUE_OK;
+}
+
+int fnnue_game_history_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                              const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap,
+                              uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (ngames == 0) return FNNUE_OK;
+  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  int rc = order_workspace(ctx, s);  // the scratch is the context's: ordered like its workspace
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  const DBoard* states = nullptr;
+  const uint32_t* ply_off = nullptr;
+  const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  const BuildResult R = replay_states_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s, ctx->bscratch,
+                                             &states, &ply_off);
+  if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
+  *n_out = R.n_out;
+  *n_groups = R.n_groups;
+  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(R.err_game));
+  if (R.err_code)
+    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
+                                  std::to_string(R.err_game));
+  DrawHistory hist;
+  HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, ply_off, (uint32_t)ngames, states, (uint32_t)R.n_out,
+                              draw_key_bits(), s, ctx->bscratch, &hist),
+          "game history launch");
+  HIP_TRY(hipMemcpyAsync(d_out, hist.hist, R.n_out * sizeof(fnnue_ply_history), hipMemcpyDeviceToDevice, s),
+          "D2D(history)");
+  HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
+  return FNNUE_OK;
+}
+
+int fnnue_ctx_game_history(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                           const uint32_t* moves_off, size_t ngames, fnnue_ply_history* out, size_t cap, uint32_t* off,
+                           size_t off_cap, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  const bool room = out && off && off_cap >= ngames + 1;
+  TempDev buf;  // [history | off]
+  const size_t o_off = cap * sizeof(fnnue_ply_history);
+  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  rc = fnnue_game_history_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_ply_history*>(d) : nullptr,
+                                 room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
+                                 room ? off_cap : 0, n_out, n_groups, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_ply_history), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return FNNUE_OK;
+}
+
 }  // extern "C"

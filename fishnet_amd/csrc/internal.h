@@ -41,6 +41,7 @@ struct fnnue_ctx {
   size_t btext_cap = 0;
   fnnue::BuilderScratch bscratch;  // the device batch builder's temporaries, grow-only
   int ft_impl = FNNUE_FT_AUTO;
+  bool search_draws = false;   // fnnue_set_search_draws: repetition and fifty-move draws in fnnue_search1 / 2
   int32_t acc_bound = 0;       // accumulator_bound of the net (the largest slice bound)
   uint64_t swar_eligible = 0;  // bit s: slice s's bound < 2^15, SWAR rows allowed (plan.swar: the enabled ones)
   fnnue::SlicedPlan plan{};

@@ -42,8 +42,9 @@ __device__ __forceinline__ unsigned long long child_key(const int32_t* __restric
   int32_t v = 0;
   if (f & kFinalWon) {
     rank = 0;
-  } else if (f & kFinalNoMoves) {
-    rank = (f & (kFinalCheck | kFinalExtinct | kFinalVariant)) ? 2u : 1u;  // mate in one / stalemate (worth 0)
+  } else if (f & (kFinalNoMoves | kFinalDraw)) {
+    // mate in one / stalemate or a drawn record (kFinalDraw: worth 0 like a stalemate; a mate stays a mate)
+    rank = ((f & kFinalNoMoves) && (f & (kFinalCheck | kFinalExtinct | kFinalVariant))) ? 2u : 1u;
   } else {
     v = (int32_t)-(((long long)psqt[x] + (long long)positional[x]) / 16);
   }
@@ -234,7 +235,7 @@ __device__ __forceinline__ unsigned long long reply_key(uint32_t f, const uint32
   if constexpr (kVariant) {
     uint32_t score;
     if (f & kFinalWon) score = kScoreLost;
-    else if (f & kFinalNoMoves) score = (f & kDeciding) ? kScoreMate : kScoreValue;
+    else if (f & (kFinalNoMoves | kFinalDraw)) score = ((f & kFinalNoMoves) && (f & kDeciding)) ? kScoreMate : kScoreValue;
     else if (kind == FNNUE_BEST_LOST) score = kScoreWins;
     else if (kind == FNNUE_BEST_MATE) score = kScoreMated;
     else score = (uint32_t)(kScoreValue - (int32_t)b[2]);
@@ -242,8 +243,8 @@ __device__ __forceinline__ unsigned long long reply_key(uint32_t f, const uint32
   } else {
     uint32_t rank = 2;
     int32_t v = 0;
-    if (f & kFinalNoMoves) {
-      rank = (f & kDeciding) ? 3u : 2u;
+    if (f & (kFinalNoMoves | kFinalDraw)) {  // a drawn record (kFinalDraw) ranks as a stalemating move; a mate stays a mate
+      rank = ((f & kFinalNoMoves) && (f & kDeciding)) ? 3u : 2u;
     } else {
       if (kind == FNNUE_BEST_MATE) rank = 1;
       else v = -(int32_t)b[2];
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void best_replies_kernel(
     const uint32_t best = key ? 0xFFFFFFFFu - (uint32_t)key : 0u;
     const uint32_t rank = (uint32_t)(key >> 62);
     const int32_t value = (int32_t)((uint32_t)(key >> 32) & 0x3FFFFFFFu) - (1 << 29);
-    const bool one = best && (end[o + best] & kFinalNoMoves);  // the pv ends at the child
+    const bool one = best && (end[o + best] & (kFinalNoMoves | kFinalDraw));  // the pv ends at the child
     const uint32_t kind = !best ? FNNUE_BEST_NONE : rank == 3 ? FNNUE_BEST_MATE : rank == 1 ? FNNUE_BEST_MATED : FNNUE_BEST_CP;
     const uint32_t pv_len = !best ? 0u : one ? 1u : 2u;
     const uint32_t* b = child_best + (size_t)(base + (best ? best - 1 : 0)) * 6;  // read only with a best child
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(kBlock) void vbest_replies_kernel(
   if (nrec) {  // an empty group: all zero
     const uint32_t best = key ? 0xFFFFFFFFu - (uint32_t)key : 0u;
     const uint32_t score = (uint32_t)(key >> 32);
-    const bool one = best && (end[o + best] & (kFinalWon | kFinalNoMoves));  // the pv ends at the child
+    const bool one = best && (end[o + best] & (kFinalWon | kFinalNoMoves | kFinalDraw));  // the pv ends at the child
     const uint32_t kind = !best                 ? FNNUE_BEST_NONE
                           : score == kScoreLost ? FNNUE_BEST_LOST
                           : score == kScoreMated ? FNNUE_BEST_MATED
@@ -420,7 +421,7 @@ __device__ __forceinline__ void write_line2(uint32_t* __restrict__ lines, uint64
   const uint32_t c = 0xFFFFFFFFu - (uint32_t)key;
   const uint32_t kind = reply_kind<kVariant>(key);
   const uint32_t* b = child_best + (size_t)(base + c - 1) * 6;
-  const bool one = end[o + c] & (kVariant ? (kFinalWon | kFinalNoMoves) : kFinalNoMoves);  // the pv ends at the child
+  const bool one = end[o + c] & (kVariant ? (kFinalWon | kFinalNoMoves | kFinalDraw) : (kFinalNoMoves | kFinalDraw));  // the pv ends at the child
   uint32_t* w = lines + slot * 7;
   w[0] = one ? 0u - b[0] : b[0];  // a one-move pv: the child's own terms, negated (wrapping)
   w[1] = one ? 0u - b[1] : b[1];

@@ -183,6 +183,28 @@ END_VARIANT = 8  # the game is decided by the variant's own rule (kingofthehill,
 END_WON = 0x40   # on a child of build_vchildren: its side to move has already won (the mover lost by playing it)
 
 
+END_DRAW = N.END_DRAW  # on a searched record: drawn by repetition or the fifty-move rule (ABI 3.12)
+# fnnue_ply_history: a ply's halfmove clock and the number of earlier plies of its game with its identity
+PLY_HISTORY_DTYPE = np.dtype([("clock", "<u2"), ("seen", "u1"), ("reserved", "u1")])
+
+
+def _game_history(fn, head, games) -> tuple[np.ndarray, np.ndarray]:
+    text, fen_off, mv_off = pack_games(games)
+    cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+    out = np.zeros(max(cap, 1), dtype=PLY_HISTORY_DTYPE)
+    off = np.zeros(len(games) + 1, dtype=np.uint32)
+    n, g = C.c_size_t(), C.c_size_t()
+    N.check(fn(*head, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), N.ptr(out), cap, N.ptr(off),
+               len(off), C.byref(n), C.byref(g)))
+    return out[: n.value], off[: g.value + 1]
+
+
+def game_history(games) -> tuple[np.ndarray, np.ndarray]:
+    """fnnue_game_history (host replay): every ply's clock and `seen` of every (fen, moves) game
+    -> (PLY_HISTORY_DTYPE records, CHAIN offsets per game)."""
+    return _game_history(N.lib.fnnue_game_history, (), games)
+
+
 def game_end(fen: str, moves: str | list[str] = "", variant: int = 0) -> int:
     """FNNUE_END_* flags of the position after `moves` (host replay): no legal
     move, side to move in check, its king exploded (atomic)."""
@@ -484,6 +506,31 @@ class Evaluator:
         N.check(N.lib.fnnue_search1_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
                                            ngames, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n),
                                            C.byref(g), C.c_void_p(stream)))
+        return n.value, g.value
+
+    # repetition and fifty-move draws (ABI 3.12)
+    def set_search_draws(self, on: bool) -> None:
+        """fnnue_set_search_draws: search1 / search1_lines / search2 / search2_lines mark the searched
+        positions drawn by repetition or the fifty-move rule (END_DRAW: worth 0, the pv ends there)."""
+        N.check(N.lib.fnnue_set_search_draws(self._h, 1 if on else 0))
+
+    def search_draws(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_get_search_draws(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def game_history(self, games) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_ctx_game_history: game_history() computed on the device from the replay's boards."""
+        return _game_history(N.lib.fnnue_ctx_game_history, (self._h,), games)
+
+    def game_history_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, d_out: int, cap: int,
+                            d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_game_history_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_game_history_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                                C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap,
+                                                C.c_void_p(d_off), off_cap, C.byref(n), C.byref(g),
+                                                C.c_void_p(stream)))
         return n.value, g.value
 
     # the two-ply search (ABI 3.7)

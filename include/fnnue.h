@@ -375,6 +375,8 @@ int fnnue_game_children(const char *fen, const char *moves, fnnue_pos *out, size
  * the child's side to move has already won by the variant's rule (racingkings:
  * the mover failed to catch up), so the parent's mover lost by playing it. */
 #define FNNUE_END_WON 0x40
+/* (FNNUE_END_DRAW, 0x10: only on a searched record, set by the searches' draw
+ * rules, ABI 3.12 below; never from fnnue_game_end or a builder.) */
 int fnnue_game_end(int variant, const char *fen, const char *moves, int *flags);
 /* Seeded random playouts from the start position (splitmix64; L ~ U[min,max]
  * plies of uniformly random legal moves, stopping at mate, stalemate or the
@@ -782,6 +784,94 @@ int fnnue_vsearch2_lines(fnnue_ctx *ctx, int variant, const char *text, size_t t
                          const uint32_t *moves_off, size_t ngames, uint32_t k, fnnue_best2 *out, size_t cap,
                          uint32_t *off, size_t off_cap, fnnue_line2 *lines, size_t lines_cap, size_t *n_out,
                          size_t *n_groups);
+
+/* ---- repetition and fifty-move draws in the device search (ABI 3.12) ----
+ * Stockfish scores a node as a draw when its rule-50 counter has reached 100
+ * and the node is not checkmate, and when the position stands for the third
+ * time, counting the game before the root; fishnet sends `position fen ...
+ * moves ...` so that the engine has that history ([ref] src/stockfish.rs:
+ * 274-283).  The rule, per game, plies 0..n, ply 0 the root FEN:
+ *  - clock(0) is the FEN's fifth field when it is an unsigned decimal number,
+ *    saturating at 65535; 0 when the field is missing or not a number.
+ *  - clock(i+1) is 0 when move i moves a pawn or captures (en passant
+ *    included), else clock(i) + 1 (saturating).  Castling counts up.
+ *  - The identity of a position is its piece placement, side to move, castling
+ *    rights (the rooks' squares as the rules keep them) and en-passant square,
+ *    the square counting only when a pawn of the side to move attacks it (the
+ *    pseudo-legal test of SF 15.1).  The boards set the square on every double
+ *    push and a root's comes verbatim from its FEN; the identity normalises it.
+ *  - A searched position X is reached from ply P by one move (a child) or two
+ *    (a grandchild).  Its history is the game's plies 0..P and the path's
+ *    intermediate position; seen(X) is the number of history positions with X's
+ *    identity; clock(X) follows the clock rule from clock(P).
+ *  - X is drawn when seen(X) >= 2 (the third occurrence: Stockfish's is_draw
+ *    with the search ply at most 2, where a first repetition inside the tree
+ *    cannot happen), or when clock(X) >= 100 and X is not checkmate (its end
+ *    byte is not NO_MOVES with CHECK).
+ *  - P itself is never tested (the engine does not test its root): a ply with
+ *    clock 120, or one that stands for the third time, is searched as usual.
+ * A 64-bit key finds candidates; a record is marked only after the identity
+ * has been compared on the boards themselves, so a key collision cannot change
+ * a result.  (Equal identities cannot straddle an irreversible move, so only
+ * the plies since the last one are looked at: an optimisation, never a
+ * condition.)
+ *
+ * A drawn record carries FNNUE_END_DRAW in its end byte and ranks, in
+ * fnnue_best_children, fnnue_topk_children, fnnue_best_replies and
+ * fnnue_topk_replies (and the variants' forms, whose callers never set it),
+ * exactly as a record whose end byte is FNNUE_END_NO_MOVES alone: worth 0, the
+ * pv ends there, kind FNNUE_BEST_CP, its terms those of a one-move pv.
+ * Checkmate (NO_MOVES with a deciding flag) and FNNUE_END_WON take precedence,
+ * and the search never sets the bit on those.  `nodes` does not change: the
+ * same records are generated, a drawn child's own grandchildren are counted,
+ * and its depth-1 record is ignored as a stalemating child's is (the search
+ * stores the drawn child's own terms in that record's psqt / positional, as for
+ * a child without a legal move).  End bytes without the bit give the results of
+ * ABI 3.11 byte for byte.
+ *
+ * Out of scope: variant batches and the fnnue_vsearch* calls (crazyhouse
+ * identities need the pockets, and Fairy-Stockfish's n-move rules differ per
+ * variant: the shared key functions honour the bit, nothing sets it there);
+ * move work; insufficient material; draw tests on the root. */
+#define FNNUE_END_DRAW 0x10
+/* One per ply: its clock and the number of earlier plies of the same game with
+ * its identity (saturating at 255). */
+typedef struct {
+  uint16_t clock;
+  uint8_t seen;
+  uint8_t reserved; /* 0 */
+} fnnue_ply_history;
+/* Every ply's history of every game: the builder's text layout, fnnue_search1's
+ * capacity protocol (out: cap records, off: CHAIN offsets per game, ngames + 1
+ * entries; *n_out = plies and *n_groups = games are set also with
+ * FNNUE_E_CAPACITY), FNNUE_E_FEN / FNNUE_E_MOVE naming the game.  Chess rules.
+ * fnnue_game_history is host only (the host replay, as fnnue_game_end);
+ * the other two run on the device over the boards the replay leaves behind
+ * (any net's context): a kernel that reads each game's clock field, one thread
+ * per ply for the key and the move's reversibility, one thread per ply walking
+ * back to the last irreversible move.  fnnue_ctx_game_history stages host
+ * buffers through the context's stream. */
+int fnnue_game_history(const char *text, size_t text_len, const uint32_t *fen_off, const uint32_t *moves_off,
+                       size_t ngames, fnnue_ply_history *out, size_t cap, uint32_t *off, size_t off_cap,
+                       size_t *n_out, size_t *n_groups);
+int fnnue_game_history_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off,
+                              const uint32_t *d_moves_off, size_t ngames, fnnue_ply_history *d_out, size_t cap,
+                              uint32_t *d_off, size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_ctx_game_history(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                           const uint32_t *moves_off, size_t ngames, fnnue_ply_history *out, size_t cap,
+                           uint32_t *off, size_t off_cap, size_t *n_out, size_t *n_groups);
+/* The switch (default off) for fnnue_search1, fnnue_search1_lines,
+ * fnnue_search2, fnnue_search2_children, fnnue_search2_lines and their _device
+ * forms on a chess net's context: behind the expansion the history is computed,
+ * the plies with a descendant that can be drawn at all (clock >= 98, or an
+ * identity that already stands twice since the last irreversible move) are
+ * compacted into a list, and a marking pass over that list alone applies each
+ * record's move code to its parent board and ORs FNNUE_END_DRAW into the end
+ * bytes, before the reductions.  A variant net's context accepts the setting
+ * and ignores it.  FNNUE_DRAW_KEY_BITS in the environment (read per call, for
+ * tests) truncates the key to that many bits (1..63). */
+int fnnue_set_search_draws(fnnue_ctx *ctx, int on);
+int fnnue_get_search_draws(const fnnue_ctx *ctx, int *on);
 
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware

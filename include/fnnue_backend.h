@@ -407,6 +407,19 @@ int fnnue_backend_analysis_json_pv(const fnnue_position_response *r, size_t n, c
  * unchanged. */
 int fnnue_backend_set_variant_analysis_plies(fnnue_backend *b, int plies);
 
+/* ---- repetition and fifty-move draws (ABI 3.12) ----
+ * fnnue_backend_set_draw_rules(b, on) (default off): on, every chess analysis
+ * batch searched at 1 or 2 plies (go, go_timeout, go_pv, go_lines, go_lines_pv,
+ * go_compact) marks the searched positions that are drawn by repetition or the
+ * fifty-move rule, the game before the ply counted (fnnue.h: FNNUE_END_DRAW,
+ * fnnue_set_search_draws): such a move is worth 0 and ends the pv, so a drawn
+ * best move answers as a stalemating one does: Score::Cp(0), depth = the pv's
+ * length, "pv":"f6g8".  A piece holds whole games, so the history is complete.
+ * The ply itself is never tested; nodes do not change.  Depth 0, move work and
+ * variant batches are unchanged. */
+int fnnue_backend_set_draw_rules(fnnue_backend *b, int on);
+int fnnue_backend_draw_rules(fnnue_backend *b, int *on);
+
 /* ---- MultiPV at two plies (ABI 3.11) ----
  * One line of a response with its whole pv, as the reference keeps one
  * Vec<Uci> per MultiPV line at the searched depth ([ref] src/ipc.rs:68-93). */

@@ -1,7 +1,7 @@
 """Times of the two-ply search (fnnue_search2_device) and of the engine actor
 at two plies.  GPU box only.  One JSON line per measurement.
 
-    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218]
+    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218] [--draws N]
                                   [--variant crazyhouse|atomic|kingofthehill|racingkings|threecheck]
 
 The shape: N random legal games of L plies each from the start position
@@ -29,6 +29,10 @@ lichess-shaped chess batches; with `--lines` also go_lines_pv() on the same
 random legal games of that variant instead (a synthetic variant net; the atomic
 net for kingofthehill, racingkings and threecheck), and with `--actor` the
 actor's go_pv() at 1 and 2 variant plies on batches of that variant;
+`--draws N` (chess) adds N interleaved rounds of search2 with the draw rules
+(fnnue_set_search_draws) off and on, in this process on the same games (phases
+search2_draws_off / _on: median, min, max), and traced calls with the rules on,
+whose line carries history_ms, mark_ms and draw_list (the plies on the list).
 `--piece-plies A,B,...` repeats the 2-plies actor lines with those values of
 FNNUE_BACKEND_PIECE_PLIES (a two-plies piece is a 1024th of it).
 """
@@ -63,6 +67,7 @@ def main():
     ap.add_argument("--variant", choices=sorted(VARIANTS), default=None)
     ap.add_argument("--piece-plies", default="")
     ap.add_argument("--lines", default="")
+    ap.add_argument("--draws", type=int, default=0)
     a = ap.parse_args()
     import torch
     import fishnet_amd as F
@@ -161,11 +166,48 @@ def main():
             (search2_lines(ks[0]) if ks else search2)()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
+    if a.draws and not a.variant:
+        draws_rounds(a, ev, stream, search2, base)
     ev.close()
     if a.actor and a.variant:
         vactor_lines(a, vid)
     elif a.actor:
         actor_lines(a)
+
+
+def draws_rounds(a, ev, stream, search2, base):
+    """search2 with the draw rules off and on, interleaved in this process on the same games; then traced
+    calls with the rules on (history_ms, mark_ms and draw_list in the library's line)."""
+    import torch
+
+    def timed():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record(stream)
+            search2()
+            e1.record(stream)
+        stream.synchronize()
+        ev.check()
+        return e0.elapsed_time(e1)
+
+    ms = {False: [], True: []}
+    for _ in range(a.draws):
+        for on in (False, True):
+            ev.set_search_draws(on)
+            ms[on].append(timed())
+    for on in (False, True):
+        v = sorted(ms[on])
+        print(json.dumps(dict(base, phase="search2_draws_" + ("on" if on else "off"), rounds=a.draws,
+                              ms=[round(x, 4) for x in v], median_ms=round(v[len(v) // 2], 4), min_ms=round(v[0], 4),
+                              max_ms=round(v[-1], 4))), flush=True)
+    ev.set_search_draws(True)
+    os.environ["FNNUE_SEARCH2_TRACE"] = "1"
+    for _ in range(a.runs):
+        with torch.cuda.stream(stream):
+            search2()
+        stream.synchronize()
+    os.environ["FNNUE_SEARCH2_TRACE"] = "0"
+    ev.set_search_draws(False)
 
 
 def actor_lines(a):
