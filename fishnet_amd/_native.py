@@ -218,6 +218,15 @@ SIGNATURES = {
     "fnnue_get_search_draws": ([_vp, _P(_i32)], _i32),
     "fnnue_backend_set_draw_rules": ([_vp, _i32], _i32),
     "fnnue_backend_draw_rules": ([_vp, _P(_i32)], _i32),
+    # capture quiescence below the search's leaves (ABI 3.13)
+    "fnnue_game_captures": ([C.c_char_p, C.c_char_p, _vp, _sz, _vp, _P(_sz)], _i32),
+    "fnnue_quiesce_device": ([_vp, _vp, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_quiesce": ([_vp, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_set_search_quiesce": ([_vp, _i32], _i32),
+    "fnnue_get_search_quiesce": ([_vp, _P(_i32)], _i32),
+    "fnnue_quiesce_slices": ([_vp, _P(_u64)], _i32),
+    "fnnue_backend_set_quiesce": ([_vp, _i32], _i32),
+    "fnnue_backend_quiesce": ([_vp, _P(_i32)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

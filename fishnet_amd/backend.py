@@ -356,6 +356,16 @@ class GpuEvalStub:
         N.check(N.lib.fnnue_backend_draw_rules(self._actor._h, C.byref(on)))
         return bool(on.value)
 
+    def set_quiesce(self, depth: int) -> None:
+        """fnnue_backend_set_quiesce: chess analysis batches at 1 or 2 plies resolve captures below their leaves,
+        `depth` captures deep at most (0: off; fnnue.h has the rule)."""
+        N.check(N.lib.fnnue_backend_set_quiesce(self._actor._h, int(depth)))
+
+    def quiesce(self) -> int:
+        d = C.c_int()
+        N.check(N.lib.fnnue_backend_quiesce(self._actor._h, C.byref(d)))
+        return d.value
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -386,7 +396,7 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
             analysis_depth: int = 0, variant_analysis_depth: int = 0,
             analysis_plies: int | None = None,
             variant_analysis_plies: int | None = None,
-            draw_rules: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
+            draw_rules: bool = False, quiesce: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -397,7 +407,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     (GpuEvalStub.set_analysis_plies; it takes the place of `analysis_depth`); `variant_analysis_plies`: 0, 1
     or 2 for the variant nets' batches (GpuEvalStub.set_variant_analysis_plies; it takes the place of
     `variant_analysis_depth`); `draw_rules`: repetition and fifty-move draws in the chess searches
-    (GpuEvalStub.set_draw_rules; off by default)."""
+    (GpuEvalStub.set_draw_rules; off by default); `quiesce`: the capture quiescence depth below the chess
+    searches' leaves (GpuEvalStub.set_quiesce; 0 by default)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -422,6 +433,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_variant_analysis_plies(variant_analysis_plies)
     if draw_rules:
         stub.set_draw_rules(True)
+    if quiesce:
+        stub.set_quiesce(quiesce)
     return stub, actor
 
 

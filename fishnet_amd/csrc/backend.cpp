@@ -472,6 +472,7 @@ struct fnnue_backend {
   int analysis_depth = 0;
   int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
   bool draw_rules = false;  // fnnue_backend_set_draw_rules: repetition and fifty-move draws in the chess searches
+  int quiesce = 0;  // fnnue_backend_set_quiesce: capture quiescence depth below the chess searches' leaves
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
   int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
@@ -1017,6 +1018,13 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                          : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(gp), goff, nkid, gtotal,
                                                      FNNUE_GROUP_STAR, gps, gpo, s))
         return rc;
+      if (chess && quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
+        QuiesceStats qs;
+        if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(ks), (uint32_t)nkid, goff,
+                                           (uint32_t)gtotal, ge, gps, gpo, quiesce, s, &qs))
+          return rc;
+        syncs += (uint32_t)qs.syncs;
+      }
       HIP_TRY(launch_best_children_own(gps, gpo, ge, gm, goff, (uint32_t)nkid, (uint32_t)gtotal, kb, s),
               "best_children launch");
       if (draws)  // a drawn child's pv ends at it: its own terms into its record
@@ -1028,6 +1036,13 @@ int fnnue_backend::stage_search(int k, size_t pi) {
                                                                  reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
             "best_replies launch");
   } else {
+    if (chess && quiesce > 0) {  // the children's terms become those of their capture lines' ends
+      QuiesceStats qs;
+      if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(states), n, coff, (uint32_t)total, ke,
+                                         kps, kpo, quiesce, s, &qs))
+        return rc;
+      syncs += (uint32_t)qs.syncs;
+    }
     HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
                                  reinterpret_cast<fnnue_best*>(dimg + P.o_best), s),
             "best_children launch");
@@ -2017,6 +2032,22 @@ int fnnue_backend_set_draw_rules(fnnue_backend* b, int on) {
   if (!b) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
   b->draw_rules = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_quiesce(fnnue_backend* b, int depth) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (depth < 0 || depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->quiesce = depth;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_quiesce(fnnue_backend* b, int* depth) {
+  if (!b || !depth) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);
+  *depth = b->quiesce;
   return FNNUE_OK;
 }
 

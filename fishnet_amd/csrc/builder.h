@@ -79,7 +79,14 @@ struct BuilderScratch {
     kGrandPositional,
     // the draw rules (draws.hip): per game its root clock, per ply its key, window start and history, the list
     kDrawClock0, kDrawKeys, kDrawLo, kDrawHist, kDrawList,
-    kSlots
+    // capture quiescence (quiesce.hip): the roots (boards, their records in the leaves' arrays, which of them are
+    // searched, their results), one level's temporaries, then per level (FNNUE_QUIESCE_MAX slots each) the nodes'
+    // record offsets and group numbers, the records' moves, the children's results and boards
+    kQRoots, kQMap, kQActive, kQRes0, kQCnt, kQHas, kQGoff, kQPos, kQPsqt, kQPositional,
+    kQRoff, kQGidx = kQRoff + FNNUE_QUIESCE_MAX, kQMoves = kQGidx + FNNUE_QUIESCE_MAX,
+    kQRes = kQMoves + FNNUE_QUIESCE_MAX, kQBoards = kQRes + FNNUE_QUIESCE_MAX,
+    kQEnd = kQBoards + FNNUE_QUIESCE_MAX,
+    kSlots = kQEnd
   };
   void* p[kSlots] = {};
   size_t bytes[kSlots] = {};
@@ -185,6 +192,27 @@ hipError_t mark_draws_level2(const DrawHistory& h, const DBoard* d_states, uint3
 hipError_t draw_own_terms(const DrawHistory& h, uint32_t p0, uint32_t p1, const uint32_t* d_off, const uint8_t* d_end,
                           const uint32_t* d_kid_off, uint32_t rec0, const int32_t* d_gps, const int32_t* d_gpo,
                           fnnue_best* d_kid_best, hipStream_t s);
+
+// ---- quiesce.hip: capture quiescence below the leaves (include/fnnue.h, ABI 3.13) ----
+// What a call did, for FNNUE_SEARCH2_TRACE and the tests: the records of every
+// level summed over the slices, and the slices of the root frontier.
+struct QuiesceStats {
+  uint64_t level_records[FNNUE_QUIESCE_MAX] = {};
+  uint64_t slices = 0;
+  uint64_t redone = 0;  // slices cut down and started again after a level passed the bound
+  uint64_t syncs = 0;   // blocking waits for a level's size
+  // with `timed` (FNNUE_SEARCH2_TRACE): device time between HIP events, summed over levels and slices, redone
+  // work included: the roots' boards and the scatter, generation (count, scans, write), the STAR evaluation,
+  // the results' kernels (quiet_leaves, quiet_reduce)
+  bool timed = false;
+  double roots_ms = 0, gen_ms = 0, eval_ms = 0, reduce_ms = 0;
+};
+// The most records one level of one slice may hold: FNNUE_QUIESCE_RECORDS in
+// the environment, read per call, 16M without and at most (a level's records
+// and its children's then stay far below 2^32), at least kQuiesceMinRecords.
+// A slice of one root is never cut, whatever its tree holds.
+constexpr size_t kQuiesceMinRecords = 256;
+size_t quiesce_budget();
 
 // The chess replay with both outputs: the packed plies and their boards.
 hipError_t replay_chess_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,

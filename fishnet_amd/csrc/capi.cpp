@@ -409,7 +409,10 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 //       reductions and their variant forms), fnnue_ply_history / fnnue_game_history[_device],
 //       fnnue_ctx_game_history, fnnue_set_search_draws / fnnue_get_search_draws,
 //       fnnue_backend_set_draw_rules / fnnue_backend_draw_rules
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 12u; }
+// 3.13: capture quiescence below the device search's leaves: fnnue_quiet / fnnue_quiesce[_device],
+//       fnnue_game_captures, fnnue_set_search_quiesce / fnnue_get_search_quiesce, fnnue_quiesce_slices,
+//       fnnue_backend_set_quiesce / fnnue_backend_quiesce
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 13u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1679,6 +1682,14 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
             "game history launch");
     HIP_TRY(mark_draws_level1(hist, plies, (uint32_t)nply, kids.off, kids.moves, kids.end, s), "draw marks launch");
   }
+  if (variant == kVariantChess && ctx->search_quiesce > 0) {
+    // capture quiescence: the children's terms become those of their capture lines' ends, before any reduction
+    if (nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+    const DBoard* plies = static_cast<const DBoard*>(ctx->bscratch.p[BuilderScratch::kStates]);
+    if ((rc = quiesce_leaves_device(ctx, ctx->bscratch, plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kids.end, ps,
+                                    po, ctx->search_quiesce, s, nullptr)))
+      return rc;
+  }
   HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
           "best_children launch");
   if (k)
@@ -1968,7 +1979,9 @@ size_t search2_budget() {
 // prints the phases' device times to stderr, one JSON line — diagnostics only
 // (tools/search2_bench.py).
 struct Search2Trace {
-  enum { kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kHistory, kMark, kPhases };
+  enum {
+    kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kHistory, kMark, kQuiesce, kPhases
+  };
   bool on = false;
   hipStream_t s = nullptr;
   std::vector<std::pair<int, hipEvent_t>> marks;
@@ -1983,9 +1996,11 @@ struct Search2Trace {
     if (ev) marks.emplace_back(phase, ev);
   }
   long listed = -1;  // the plies on the draw rules' list (read back for the report only)
+  int quiesce = 0;   // the quiescence depth, with what the levels held and the slices of leaves
+  QuiesceStats qstats;
   void report(size_t plies, size_t kids, size_t records, size_t chunks) {
     static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1",
-                                               "reduce2", "topk", "history", "mark"};
+                                               "reduce2", "topk", "history", "mark", "quiesce"};
     if (on && !marks.empty() && hipEventSynchronize(marks.back().second) == hipSuccess) {
       double ms[kPhases] = {};
       for (size_t i = 0; i + 1 < marks.size(); ++i) {
@@ -1996,6 +2011,15 @@ struct Search2Trace {
                          std::to_string(kids) + ",\"grandchild_records\":" + std::to_string(records) +
                          ",\"chunks\":" + std::to_string(chunks);
       if (listed >= 0) line += ",\"draw_list\":" + std::to_string(listed);
+      if (quiesce > 0) {
+        line += ",\"quiesce\":" + std::to_string(quiesce) + ",\"quiesce_slices\":" + std::to_string(qstats.slices) +
+                ",\"quiesce_records\":[";
+        for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_records[l]);
+        line += "],\"quiesce_redone\":" + std::to_string(qstats.redone) + ",\"quiesce_roots_ms\":" +
+                std::to_string(qstats.roots_ms) + ",\"quiesce_gen_ms\":" + std::to_string(qstats.gen_ms) +
+                ",\"quiesce_eval_ms\":" + std::to_string(qstats.eval_ms) + ",\"quiesce_reduce_ms\":" +
+                std::to_string(qstats.reduce_ms);
+      }
       for (int k = 0; k < kPhases; ++k) line += std::string(",\"") + kName[k] + "_ms\":" + std::to_string(ms[k]);
       std::fprintf(stderr, "%s}\n", line.c_str());
     }
@@ -2193,6 +2217,14 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
                : fnnue_eval_vgroups_device(ctx, static_cast<fnnue_vpos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
                                            gpo, s);
     if (rc) return rc;
+    if (chess && ctx->search_quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
+      trace.mark(Search2Trace::kQuiesce);
+      trace.quiesce = ctx->search_quiesce;
+      trace.qstats.timed = trace.on;
+      if ((rc = quiesce_leaves_device(ctx, ws, reinterpret_cast<const DBoard*>(chunk_states), nk, ch_off, nr, gend, gps,
+                                      gpo, ctx->search_quiesce, s, &trace.qstats)))
+        return rc;
+    }
     trace.mark(Search2Trace::kReduce1);
     HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
     if (draws) {  // a drawn child's pv ends at it: its own terms, while the chunk still holds them
@@ -2548,6 +2580,134 @@ int fnnue_random_game(uint64_t seed, const char* fen, uint32_t plies, char* move
   std::memcpy(moves, out.c_str(), out.size() + 1);
   return FNNUE_OK;
 }
+}  // extern "C"
+
+// ---- capture quiescence (ABI 3.13; the kernels: quiesce.hip) ----
+extern "C" {
+
+int fnnue_set_search_quiesce(fnnue_ctx* ctx, int depth) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (depth < 0 || depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  ctx->search_quiesce = depth;
+  return FNNUE_OK;
+}
+
+int fnnue_get_search_quiesce(const fnnue_ctx* ctx, int* depth) {
+  if (!ctx || !depth) return fail(FNNUE_E_ARG, "null argument");
+  *depth = ctx->search_quiesce;
+  return FNNUE_OK;
+}
+
+int fnnue_quiesce_slices(const fnnue_ctx* ctx, uint64_t* slices) {
+  if (!ctx || !slices) return fail(FNNUE_E_ARG, "null argument");
+  *slices = ctx->quiesce_slices;
+  return FNNUE_OK;
+}
+
+int fnnue_game_captures(const char* fen, const char* moves, fnnue_pos* out, size_t cap, fnnue_move* mv,
+                        size_t* n_out) {
+  if (!fen || !n_out) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = 0;
+  Board b;
+  std::string err;
+  if (!board_from_fen(fen, b, &err)) return fail(FNNUE_E_FEN, err);
+  std::vector<std::string> ms;
+  split_moves(moves, ms);
+  for (size_t i = 0; i < ms.size(); ++i) {
+    Move m;
+    if (!parse_uci(b, ms[i].c_str(), m))
+      return fail(FNNUE_E_MOVE, "illegal move " + ms[i] + " at ply " + std::to_string(i + 1));
+    b.do_move(m);
+  }
+  std::vector<fnnue_pos> res{b.pack()};
+  std::vector<fnnue_move> codes{0};
+  std::vector<Move> legal;
+  b.legal_moves(legal);
+  const int them = b.stm ^ 1;
+  const int before = __builtin_popcountll(b.byColor[them]);
+  for (const Move& m : legal) {
+    if (m.castle) continue;  // king takes own rook: no capture
+    Board c = b;
+    c.do_move(m);
+    if (__builtin_popcountll(c.byColor[them]) >= before) continue;
+    res.push_back(c.pack());
+    codes.push_back((fnnue_move)((uint32_t)m.from | (uint32_t)m.to << 6 | (uint32_t)m.promo << 12));
+  }
+  *n_out = res.size();
+  if (!out || !mv || cap < res.size()) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  std::memcpy(out, res.data(), res.size() * sizeof(fnnue_pos));
+  std::memcpy(mv, codes.data(), codes.size() * sizeof(fnnue_move));
+  return FNNUE_OK;
+}
+
+int fnnue_quiesce_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+                         size_t ngames, uint32_t depth, fnnue_quiet* d_out, size_t cap, uint32_t* d_off,
+                         size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "quiescence needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
+  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  int rc = order_workspace(ctx, s);  // the scratch is the context's: ordered like its workspace
+  if (rc) return rc;
+  WorkspaceUse use{ctx, s};
+  const DBoard* states = nullptr;
+  const uint32_t* ply_off = nullptr;
+  const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  const BuildResult R = replay_states_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s, ctx->bscratch,
+                                             &states, &ply_off);
+  if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
+  *n_out = R.n_out;
+  *n_groups = R.n_groups;
+  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(R.err_game));
+  if (R.err_code)
+    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
+                                  std::to_string(R.err_game));
+  if (R.n_out > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+  if ((rc = quiesce_nodes_device(ctx, ctx->bscratch, states, (uint32_t)R.n_out, (int)depth, d_out, s, nullptr)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
+  return FNNUE_OK;
+}
+
+int fnnue_quiesce(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
+                  const uint32_t* moves_off, size_t ngames, uint32_t depth, fnnue_quiet* out, size_t cap,
+                  uint32_t* off, size_t off_cap, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "quiescence needs a chess net");
+  if (ngames == 0) return FNNUE_OK;
+  DeviceGuard g(ctx->device);
+  char* d_text = nullptr;
+  uint32_t *d_fo = nullptr, *d_mo = nullptr;
+  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
+  if (rc) return rc;
+  const bool room = out && off && off_cap >= ngames + 1;
+  TempDev buf;  // [results | off]
+  const size_t o_off = (cap * sizeof(fnnue_quiet) + 15) / 16 * 16;
+  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
+  char* d = static_cast<char*>(buf.p);
+  hipStream_t s = ctx->stream;
+  rc = fnnue_quiesce_device(ctx, d_text, d_fo, d_mo, ngames, depth, room ? reinterpret_cast<fnnue_quiet*>(d) : nullptr,
+                            room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
+                            room ? off_cap : 0, n_out, n_groups, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_quiet), hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return latched(ctx);
+}
+
 }  // extern "C"
 
 // ---- repetition and fifty-move draws (ABI 3.12; the kernels: draws.hip) ----

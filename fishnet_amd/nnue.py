@@ -265,6 +265,10 @@ class Line(C.Structure):
 LINE_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"), ("move", "<u2"),
                        ("kind", "u1"), ("reserved", "u1")])
 MAX_CHILDREN = N.MAX_CHILDREN
+# fnnue_quiet (ABI 3.13): Q_d of a position, the terms of its capture line's end, the line's first move
+QUIET_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("move", "<u2"),
+                        ("len", "u1"), ("reserved", "u1")])
+QUIESCE_MAX = 4
 # fnnue_line2: one of a ply's k best lines at two plies (move, reply); kind BEST_NONE = an unused slot
 LINE2_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"),
                         ("reply_index", "<u4"), ("move", "<u2"), ("reply", "<u2"), ("kind", "u1"), ("pv_len", "u1"),
@@ -531,6 +535,43 @@ class Evaluator:
                                                 C.c_void_p(d_moves_off), ngames, C.c_void_p(d_out), cap,
                                                 C.c_void_p(d_off), off_cap, C.byref(n), C.byref(g),
                                                 C.c_void_p(stream)))
+        return n.value, g.value
+
+    # capture quiescence below the search's leaves (ABI 3.13)
+    def set_search_quiesce(self, depth: int) -> None:
+        """fnnue_set_search_quiesce: the leaves of search1 / search1_lines / search2 / search2_children /
+        search2_lines take the terms of their capture line's end, `depth` captures deep at most (0: off)."""
+        N.check(N.lib.fnnue_set_search_quiesce(self._h, depth))
+
+    def search_quiesce(self) -> int:
+        d = C.c_int()
+        N.check(N.lib.fnnue_get_search_quiesce(self._h, C.byref(d)))
+        return d.value
+
+    def quiesce_slices(self) -> int:
+        """fnnue_quiesce_slices: the slices of leaves the context's quiescence has worked through so far."""
+        n = C.c_uint64()
+        N.check(N.lib.fnnue_quiesce_slices(self._h, C.byref(n)))
+        return n.value
+
+    def quiesce(self, games, depth: int) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_quiesce: Q_depth of every ply -> (QUIET_DTYPE records, CHAIN offsets per game)."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=QUIET_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_quiesce(self._h, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games), depth,
+                                    N.ptr(out), cap, N.ptr(off), len(off), C.byref(n), C.byref(g)))
+        return out[: n.value], off[: g.value + 1]
+
+    def quiesce_device(self, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, depth: int, d_out: int,
+                       cap: int, d_off: int, off_cap: int, stream: int | None) -> tuple[int, int]:
+        """fnnue_quiesce_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_quiesce_device(self._h, C.c_void_p(d_text), C.c_void_p(d_fen_off), C.c_void_p(d_moves_off),
+                                           ngames, depth, C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap,
+                                           C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
     # the two-ply search (ABI 3.7)
@@ -1077,6 +1118,20 @@ def game_children(fen: str, moves: str | list[str]) -> tuple[np.ndarray, np.ndar
     N.check(N.lib.fnnue_game_children(fen.encode(), moves.encode(), N.ptr(out), cap, N.ptr(off), len(off),
                                       C.byref(n), C.byref(g)))
     return out[: n.value], off[: g.value + 1]
+
+
+def game_captures(fen: str, moves: str | list[str] = "") -> tuple[np.ndarray, np.ndarray]:
+    """fnnue_game_captures: the game's last position followed by its capture children (legal moves after
+    which the opponent has one piece fewer, in the order of game_children) -> (positions, uint16 move codes;
+    codes[0] = 0)."""
+    if not isinstance(moves, str):
+        moves = " ".join(moves)
+    cap = 128
+    out = N.positions_array(cap)
+    mv = np.zeros(cap, dtype=np.uint16)
+    n = C.c_size_t()
+    N.check(N.lib.fnnue_game_captures(fen.encode(), moves.encode(), N.ptr(out), cap, N.ptr(mv), C.byref(n)))
+    return out[: n.value], mv[: n.value]
 
 
 def random_playouts(seed: int, count: int, min_plies: int = 0, max_plies: int = 160,

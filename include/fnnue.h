@@ -873,6 +873,91 @@ int fnnue_ctx_game_history(fnnue_ctx *ctx, const char *text, size_t text_len, co
 int fnnue_set_search_draws(fnnue_ctx *ctx, int on);
 int fnnue_get_search_draws(const fnnue_ctx *ctx, int *on);
 
+/* ---- capture quiescence below the search's leaves (ABI 3.13) ----
+ * A bare static evaluation values the child after QxP as "a pawn up" also when
+ * the pawn is defended.  Every engine the reference drives resolves captures
+ * before it trusts an evaluation; this is the plain form of that, without
+ * pruning.  The rule, for a chess position X and a depth d in 0..FNNUE_QUIESCE_MAX:
+ *  - s(X) = trunc(((int64)psqt(X) + positional(X)) / 16), C truncation, from X's
+ *    side to move, as fnnue_best_children takes it.
+ *  - caps(X) is the set of X's legal moves after which the opponent has one
+ *    piece fewer: en passant included, capturing promotions included (one move
+ *    per promotion piece); a Chess960 castling move spelled king-takes-own-rook
+ *    is no capture, nor is a quiet promotion.  Their order is the order of X's
+ *    children in fnnue_build_children, restricted to captures.
+ *  - Q_0(X) = s(X), line(X) = [];
+ *    Q_d(X) = max(s(X), max over c in caps(X) of -Q_{d-1}(X.c)) for d >= 1.
+ *    Candidate 0 is standing pat, the captures follow in order, and a later
+ *    candidate replaces the current one only when it is strictly greater (the
+ *    first maximum wins).  line(X) is empty for stand pat, else [c] +
+ *    line_{d-1}(X.c); the line's end is the position after its last capture.
+ *  - Checks, mates and stalemates are not recognised inside the tree: a side in
+ *    check may stand pat, and a position without a legal move has no captures
+ *    and is worth s.  This limit is deliberate; check evasions are out of scope.
+ *  - The reported terms are the psqt / positional of the line's end, negated
+ *    with int32 wrap-around (as fnnue_best negates) exactly when the line has an
+ *    odd number of captures.  For terms that do not wrap, value ==
+ *    trunc((psqt + positional) / 16) therefore holds for the reported triple.
+ *  - nodes(X) is the number of capture records in the whole tree below X (every
+ *    capture of every node above the last level), 0 at depth 0.
+ *
+ * In the searches, with quiescence depth d > 0 (fnnue_set_search_quiesce): a
+ * leaf is a record j >= 1 of a ply's STAR group in a one-ply search, or of a
+ * child's STAR group in a two-ply search.  Every leaf whose end byte has
+ * neither FNNUE_END_NO_MOVES nor FNNUE_END_DRAW gets its (psqt, positional)
+ * replaced by the reported terms of Q_d(leaf) before any reduction runs.
+ * Nothing else changes: the reductions, ranks, tie rules, kinds, `nodes`,
+ * `pv_len` and the pv are as before (the pv does not show the capture line),
+ * records j = 0, leaves with NO_MOVES or DRAW and the terms a drawn or
+ * stalemated child reports of its own are untouched.  A position below a
+ * capture cannot repeat an earlier one and its clock is 0, so quiescence nodes
+ * are never tested for draws and the two settings compose.  With depth 0 every
+ * byte of every result is that of ABI 3.12.
+ *
+ * On the device the tree is level-synchronous (quiesce.hip): per level the
+ * captures are counted, scanned, written as STAR groups [node, its captures]
+ * and evaluated; a node without a capture forms no group.  Each level's size
+ * is read back once (the calls synchronise their stream), and no level holds
+ * more than FNNUE_QUIESCE_RECORDS records (environment, read per call; default
+ * and most 16M, least 256): a slice of the leaves whose tree would is cut
+ * down and redone; a single leaf's tree is never cut.  Results do not depend on the
+ * slicing.  Out of scope: variants, move work, check evasions, quiet
+ * promotions, any pruning, extending the pv with the capture line. */
+#define FNNUE_QUIESCE_MAX 4
+typedef struct {            /* 20 bytes */
+  int32_t psqt, positional; /* of the line's end, oriented to the position's side to move */
+  int32_t value;            /* Q_d */
+  uint32_t nodes;           /* capture records below the position */
+  fnnue_move move;          /* the line's first capture, 0 when standing pat */
+  uint8_t len;              /* captures in the line, 0..d */
+  uint8_t reserved;         /* 0 */
+} fnnue_quiet;
+/* Host only: the game's last position followed by its capture children
+ * (caps() above, in order) with their move codes, mv[0] = 0; cap entries in out
+ * and mv.  *n_out is set also with FNNUE_E_CAPACITY; FNNUE_E_FEN / FNNUE_E_MOVE
+ * as fnnue_game_children. */
+int fnnue_game_captures(const char *fen, const char *moves, fnnue_pos *out, size_t cap, fnnue_move *mv,
+                        size_t *n_out);
+/* One fnnue_quiet per ply of every game, CHAIN offsets per game: signature
+ * shape, capacity protocol and errors are fnnue_search1[_device]'s.  depth >
+ * FNNUE_QUIESCE_MAX: FNNUE_E_ARG; a variant net's context: FNNUE_E_ARCH.  Depth
+ * 0 gives the ply's own terms, nodes 0 and len 0. */
+int fnnue_quiesce_device(fnnue_ctx *ctx, const char *d_text, const uint32_t *d_fen_off, const uint32_t *d_moves_off,
+                         size_t ngames, uint32_t depth, fnnue_quiet *d_out, size_t cap, uint32_t *d_off,
+                         size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_quiesce(fnnue_ctx *ctx, const char *text, size_t text_len, const uint32_t *fen_off,
+                  const uint32_t *moves_off, size_t ngames, uint32_t depth, fnnue_quiet *out, size_t cap,
+                  uint32_t *off, size_t off_cap, size_t *n_out, size_t *n_groups);
+/* The quiescence depth (default 0, at most FNNUE_QUIESCE_MAX: FNNUE_E_ARG) of
+ * fnnue_search1, fnnue_search1_lines, fnnue_search2, fnnue_search2_children,
+ * fnnue_search2_lines and their _device forms.  A variant net's context accepts
+ * the setting and ignores it. */
+int fnnue_set_search_quiesce(fnnue_ctx *ctx, int depth);
+int fnnue_get_search_quiesce(const fnnue_ctx *ctx, int *depth);
+/* Diagnostics: the slices of leaves (whole frontiers count as one) the
+ * context's quiescence has worked through since it was created. */
+int fnnue_quiesce_slices(const fnnue_ctx *ctx, uint64_t *slices);
+
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware
  * layout matches the kernels' assumption. */

@@ -420,6 +420,21 @@ int fnnue_backend_set_variant_analysis_plies(fnnue_backend *b, int plies);
 int fnnue_backend_set_draw_rules(fnnue_backend *b, int on);
 int fnnue_backend_draw_rules(fnnue_backend *b, int *on);
 
+/* ---- capture quiescence below the searches' leaves (ABI 3.13) ----
+ * fnnue_backend_set_quiesce(b, depth) (default 0, at most FNNUE_QUIESCE_MAX:
+ * FNNUE_E_ARG): every chess analysis batch searched at 1 or 2 plies (go,
+ * go_timeout, go_pv, go_lines, go_lines_pv, go_compact) replaces its leaves'
+ * terms by those of their capture line's end (fnnue.h: the rule and what
+ * stays), before the piece's reductions: the same device function at both
+ * reduction sites.  Depth-0 analysis, move work, variant batches, `nodes` /
+ * `positions` and the JSON shapes are unchanged, and the setting composes with
+ * the draw rules.  With quiescence on, a piece reads each level's size back
+ * (one more blocking wait per level and slice, counted in stream_syncs, and not
+ * bounded by the call's deadline as the sizing waits are): what is said above
+ * about a piece's one or two sizing waits holds with quiescence off only. */
+int fnnue_backend_set_quiesce(fnnue_backend *b, int depth);
+int fnnue_backend_quiesce(fnnue_backend *b, int *depth);
+
 /* ---- MultiPV at two plies (ABI 3.11) ----
  * One line of a response with its whole pv, as the reference keeps one
  * Vec<Uci> per MultiPV line at the searched depth ([ref] src/ipc.rs:68-93). */

@@ -1,7 +1,7 @@
 """Times of the two-ply search (fnnue_search2_device) and of the engine actor
 at two plies.  GPU box only.  One JSON line per measurement.
 
-    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218] [--draws N]
+    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218] [--draws N] [--quiesce D]
                                   [--variant crazyhouse|atomic|kingofthehill|racingkings|threecheck]
 
 The shape: N random legal games of L plies each from the start position
@@ -33,6 +33,11 @@ actor's go_pv() at 1 and 2 variant plies on batches of that variant;
 (fnnue_set_search_draws) off and on, in this process on the same games (phases
 search2_draws_off / _on: median, min, max), and traced calls with the rules on,
 whose line carries history_ms, mark_ms and draw_list (the plies on the list).
+`--quiesce D` (chess) adds interleaved rounds (`--runs` of them, at least 3) of search1 and search2 with the
+capture quiescence depth (fnnue_set_search_quiesce) at 0, 1, .. D, in this process on the same games (phases
+search1_quiesce_d / search2_quiesce_d: median, min, max of the device time between two events, and the host's
+wall time, which holds the level read-backs), and one traced search2 call per depth, whose line carries
+quiesce_ms, the per-level record counts and the slice count.
 `--piece-plies A,B,...` repeats the 2-plies actor lines with those values of
 FNNUE_BACKEND_PIECE_PLIES (a two-plies piece is a 1024th of it).
 """
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--piece-plies", default="")
     ap.add_argument("--lines", default="")
     ap.add_argument("--draws", type=int, default=0)
+    ap.add_argument("--quiesce", type=int, default=0)
     a = ap.parse_args()
     import torch
     import fishnet_amd as F
@@ -168,6 +174,8 @@ def main():
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     if a.draws and not a.variant:
         draws_rounds(a, ev, stream, search2, base)
+    if a.quiesce and not a.variant:
+        quiesce_rounds(a, ev, stream, search1, search2, base)
     ev.close()
     if a.actor and a.variant:
         vactor_lines(a, vid)
@@ -208,6 +216,46 @@ def draws_rounds(a, ev, stream, search2, base):
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     ev.set_search_draws(False)
+
+
+def quiesce_rounds(a, ev, stream, search1, search2, base):
+    """search1 and search2 at quiescence depth 0..D, interleaved in this process on the same games; then one traced
+    search2 call per depth (quiesce_ms, quiesce_records per level and quiesce_slices in the library's line)."""
+    import torch
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+        stream.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        ev.check()
+        return e0.elapsed_time(e1), wall
+
+    depths = list(range(a.quiesce + 1))
+    rounds = max(a.runs, 3)
+    ms = {(n, d): [] for n in ("search1", "search2") for d in depths}
+    for _ in range(rounds):
+        for d in depths:
+            ev.set_search_quiesce(d)
+            ms[("search1", d)].append(timed(search1))
+            ms[("search2", d)].append(timed(search2))
+    for (name, d), v in ms.items():
+        dev_ms, wall = sorted(x[0] for x in v), sorted(x[1] for x in v)
+        print(json.dumps(dict(base, phase=f"{name}_quiesce_{d}", rounds=rounds, ms=[round(x, 4) for x in dev_ms],
+                              median_ms=round(dev_ms[len(dev_ms) // 2], 4), min_ms=round(dev_ms[0], 4),
+                              max_ms=round(dev_ms[-1], 4), wall_median_ms=round(wall[len(wall) // 2], 4))), flush=True)
+    os.environ["FNNUE_SEARCH2_TRACE"] = "1"
+    for d in depths[1:]:
+        ev.set_search_quiesce(d)
+        with torch.cuda.stream(stream):
+            search2()
+        stream.synchronize()
+    os.environ["FNNUE_SEARCH2_TRACE"] = "0"
+    ev.set_search_quiesce(0)
 
 
 def actor_lines(a):
