@@ -227,6 +227,12 @@ SIGNATURES = {
     "fnnue_quiesce_slices": ([_vp, _P(_u64)], _i32),
     "fnnue_backend_set_quiesce": ([_vp, _i32], _i32),
     "fnnue_backend_quiesce": ([_vp, _P(_i32)], _i32),
+    # check evasions and mates inside the quiescence (ABI 3.14)
+    "fnnue_set_search_quiesce_checks": ([_vp, _i32], _i32),
+    "fnnue_get_search_quiesce_checks": ([_vp, _P(_i32)], _i32),
+    "fnnue_game_quiet_moves": ([C.c_char_p, C.c_char_p, _vp, _sz, _vp, _P(_i32), _P(_sz)], _i32),
+    "fnnue_backend_set_quiesce_checks": ([_vp, _i32], _i32),
+    "fnnue_backend_quiesce_checks": ([_vp, _P(_i32)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

@@ -366,6 +366,16 @@ class GpuEvalStub:
         N.check(N.lib.fnnue_backend_quiesce(self._actor._h, C.byref(d)))
         return d.value
 
+    def set_quiesce_checks(self, on: bool) -> None:
+        """fnnue_backend_set_quiesce_checks: the quiescence of chess analysis batches recognises check evasions
+        and mates (fnnue.h: Q'), and coded mate values are answered as Score::Mate."""
+        N.check(N.lib.fnnue_backend_set_quiesce_checks(self._actor._h, 1 if on else 0))
+
+    def quiesce_checks(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_backend_quiesce_checks(self._actor._h, C.byref(on)))
+        return bool(on.value)
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -396,7 +406,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
             analysis_depth: int = 0, variant_analysis_depth: int = 0,
             analysis_plies: int | None = None,
             variant_analysis_plies: int | None = None,
-            draw_rules: bool = False, quiesce: int = 0) -> tuple[GpuEvalStub, GpuEvalActor]:
+            draw_rules: bool = False, quiesce: int = 0,
+            quiesce_checks: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -408,7 +419,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     or 2 for the variant nets' batches (GpuEvalStub.set_variant_analysis_plies; it takes the place of
     `variant_analysis_depth`); `draw_rules`: repetition and fifty-move draws in the chess searches
     (GpuEvalStub.set_draw_rules; off by default); `quiesce`: the capture quiescence depth below the chess
-    searches' leaves (GpuEvalStub.set_quiesce; 0 by default)."""
+    searches' leaves (GpuEvalStub.set_quiesce; 0 by default); `quiesce_checks`: check evasions and mates inside
+    that quiescence (GpuEvalStub.set_quiesce_checks; off by default)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -435,6 +447,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_draw_rules(True)
     if quiesce:
         stub.set_quiesce(quiesce)
+    if quiesce_checks:
+        stub.set_quiesce_checks(True)
     return stub, actor
 
 

@@ -473,6 +473,7 @@ struct fnnue_backend {
   int variant_analysis_depth = 0;  // fnnue_backend_set_variant_analysis_depth: the same for the variant nets' plies
   bool draw_rules = false;  // fnnue_backend_set_draw_rules: repetition and fifty-move draws in the chess searches
   int quiesce = 0;  // fnnue_backend_set_quiesce: capture quiescence depth below the chess searches' leaves
+  bool quiesce_checks = false;  // fnnue_backend_set_quiesce_checks: evasions and mates inside it, coded mates answered
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
   int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
@@ -1021,7 +1022,7 @@ int fnnue_backend::stage_search(int k, size_t pi) {
       if (chess && quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
         QuiesceStats qs;
         if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(ks), (uint32_t)nkid, goff,
-                                           (uint32_t)gtotal, ge, gps, gpo, quiesce, s, &qs))
+                                           (uint32_t)gtotal, ge, gps, gpo, quiesce, quiesce_checks, 2, s, &qs))
           return rc;
         syncs += (uint32_t)qs.syncs;
       }
@@ -1039,7 +1040,7 @@ int fnnue_backend::stage_search(int k, size_t pi) {
     if (chess && quiesce > 0) {  // the children's terms become those of their capture lines' ends
       QuiesceStats qs;
       if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(states), n, coff, (uint32_t)total, ke,
-                                         kps, kpo, quiesce, s, &qs))
+                                         kps, kpo, quiesce, quiesce_checks, 1, s, &qs))
         return rc;
       syncs += (uint32_t)qs.syncs;
     }
@@ -1204,6 +1205,16 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const uint32_t nps = el > 0 ? (uint32_t)std::min(4.0e9, (double)filled / (el * 1e-3)) : 0;
   const int32_t nrm = norm;
   const ResponseTail tail(ms, nps);
+  // quiescence checks: a FNNUE_BEST_CP value beyond the static domain is a coded mate -> its Score::Mate moves
+  // (0: not one).  Chess searches with quiescence only; otherwise no value is ever remapped.
+  const bool coded_on = k == kVariantChess && quiesce_checks && quiesce > 0;
+  auto coded = [coded_on](uint8_t kind, int32_t v) -> int64_t {
+    if (!coded_on || kind != FNNUE_BEST_CP) return 0;
+    const int32_t a = v < 0 ? -v : v;
+    if (a <= FNNUE_VALUE_MATE - 64) return 0;
+    const int32_t plies = FNNUE_VALUE_MATE - a;
+    return v > 0 ? (plies + 1) / 2 : -(plies / 2);
+  };
   pool.run(P.ng, fill_grain, [&](size_t lo, size_t hi) {
     for (size_t g = lo; g < hi; ++g) {
       const size_t i = P.games[g];
@@ -1227,8 +1238,9 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           const bool none = B.kind == FNNUE_BEST_NONE;
           // mated: every move allows a mate in one, or (variants) loses at once
           const bool mate = B.kind == FNNUE_BEST_MATE, mated = B.kind == FNNUE_BEST_MATED || B.kind == FNNUE_BEST_LOST;
-          const uint8_t kind = none ? end_kind : mate || mated ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-          const int64_t score = none ? 0 : mate ? 1 : mated ? -1 : (int64_t)B.value * 100 / nrm;
+          const int64_t cm = coded(B.kind, B.value);
+          const uint8_t kind = none ? end_kind : mate || mated || cm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+          const int64_t score = none ? 0 : mate ? 1 : mated ? -1 : cm ? cm : (int64_t)B.value * 100 / nrm;
           const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
           const uint8_t depth = none ? 0 : B.pv_len;
           if (j.cout) {
@@ -1260,11 +1272,12 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
             (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
             if (L.pv_len == 2) (void)(k == kVariantChess ? fnnue_move_uci(L.reply, rp) : fnnue_vmove_uci(L.reply, rp));
             fnnue_pv_line2 out{};
-            out.score = lm ? 1 : ld ? -1 : (int64_t)L.value * 100 / nrm;
+            const int64_t lc = coded(L.kind, L.value);
+            out.score = lm ? 1 : ld ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
             out.psqt = L.psqt;
             out.positional = L.positional;
             std::snprintf(out.pv, sizeof(out.pv), "%s%s%s", mv, rp[0] ? " " : "", rp);
-            out.score_kind = lm || ld ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+            out.score_kind = lm || ld || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
             out.pv_len = rp[0] ? 2 : 1;
             dst[nl] = out;
           }
@@ -1291,8 +1304,9 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           const bool none = B.kind == FNNUE_BEST_NONE;
           // a mate in one, or (variants) every move loses at once: Mate(1) / Mate(-1), as move work
           const bool mate = B.kind == FNNUE_BEST_MATE, lost = B.kind == FNNUE_BEST_LOST;
-          const uint8_t kind = none ? end_kind : mate || lost ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-          const int64_t score = none ? 0 : mate ? 1 : lost ? -1 : (int64_t)B.value * 100 / nrm;
+          const int64_t cm = coded(B.kind, B.value);
+          const uint8_t kind = none ? end_kind : mate || lost || cm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+          const int64_t score = none ? 0 : mate ? 1 : lost ? -1 : cm ? cm : (int64_t)B.value * 100 / nrm;
           const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
           if (j.cout) {
             if (skipped)
@@ -1319,25 +1333,26 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
           for (uint32_t l = 0; l < nl; ++l) {
             const fnnue_line& L = src[l];
             const bool lm = L.kind == FNNUE_BEST_MATE, ll = L.kind == FNNUE_BEST_LOST;
+            const int64_t lc = coded(L.kind, L.value);
             char mv[8];
             (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
             if (!dst) {  // go_lines_pv at one ply: the same line in the two-ply record
               fnnue_pv_line2 out2{};
-              out2.score = lm ? 1 : ll ? -1 : (int64_t)L.value * 100 / nrm;
+              out2.score = lm ? 1 : ll ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
               out2.psqt = L.psqt;
               out2.positional = L.positional;
               std::memcpy(out2.pv, mv, 6);
-              out2.score_kind = lm || ll ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+              out2.score_kind = lm || ll || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
               out2.pv_len = 1;
               j.lines2[at + l] = out2;
               continue;
             }
             fnnue_pv_line out{};
-            out.score = lm ? 1 : ll ? -1 : (int64_t)L.value * 100 / nrm;
+            out.score = lm ? 1 : ll ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
             out.psqt = L.psqt;
             out.positional = L.positional;
             std::memcpy(out.move, mv, 6);  // at most "e7e8q" and its NUL
-            out.score_kind = lm || ll ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
+            out.score_kind = lm || ll || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
             dst[l] = out;
           }
           j.line_off[b + q + 1] = nl;  // a count for now
@@ -2048,6 +2063,20 @@ int fnnue_backend_quiesce(fnnue_backend* b, int* depth) {
   if (!b || !depth) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->run_mu);
   *depth = b->quiesce;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_quiesce_checks(fnnue_backend* b, int on) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->quiesce_checks = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_quiesce_checks(fnnue_backend* b, int* on) {
+  if (!b || !on) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);
+  *on = b->quiesce_checks ? 1 : 0;
   return FNNUE_OK;
 }
 

@@ -86,7 +86,9 @@ struct BuilderScratch {
     kQRoff, kQGidx = kQRoff + FNNUE_QUIESCE_MAX, kQMoves = kQGidx + FNNUE_QUIESCE_MAX,
     kQRes = kQMoves + FNNUE_QUIESCE_MAX, kQBoards = kQRes + FNNUE_QUIESCE_MAX,
     kQEnd = kQBoards + FNNUE_QUIESCE_MAX,
-    kSlots = kQEnd
+    // quiescence checks (ABI 3.14): per level the nodes' flag bytes (in check / mated), the trace's counters
+    kQFlag = kQEnd, kQEvasions = kQFlag + FNNUE_QUIESCE_MAX,
+    kSlots
   };
   void* p[kSlots] = {};
   size_t bytes[kSlots] = {};
@@ -198,6 +200,9 @@ hipError_t draw_own_terms(const DrawHistory& h, uint32_t p0, uint32_t p1, const 
 // level summed over the slices, and the slices of the root frontier.
 struct QuiesceStats {
   uint64_t level_records[FNNUE_QUIESCE_MAX] = {};
+  // quiescence checks, with `timed` only: of those records the evasions, and the nodes in check that had one
+  uint64_t level_evasions[FNNUE_QUIESCE_MAX] = {};
+  uint64_t level_in_check[FNNUE_QUIESCE_MAX] = {};
   uint64_t slices = 0;
   uint64_t redone = 0;  // slices cut down and started again after a level passed the bound
   uint64_t syncs = 0;   // blocking waits for a level's size

@@ -412,7 +412,10 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.13: capture quiescence below the device search's leaves: fnnue_quiet / fnnue_quiesce[_device],
 //       fnnue_game_captures, fnnue_set_search_quiesce / fnnue_get_search_quiesce, fnnue_quiesce_slices,
 //       fnnue_backend_set_quiesce / fnnue_backend_quiesce
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 13u; }
+// 3.14: check evasions and mates inside the quiescence: FNNUE_VALUE_MATE, FNNUE_QUIET_DECIDED,
+//       fnnue_set_search_quiesce_checks / fnnue_get_search_quiesce_checks, fnnue_game_quiet_moves,
+//       fnnue_backend_set_quiesce_checks / fnnue_backend_quiesce_checks
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 14u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");
@@ -1687,7 +1690,7 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
     if (nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
     const DBoard* plies = static_cast<const DBoard*>(ctx->bscratch.p[BuilderScratch::kStates]);
     if ((rc = quiesce_leaves_device(ctx, ctx->bscratch, plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kids.end, ps,
-                                    po, ctx->search_quiesce, s, nullptr)))
+                                    po, ctx->search_quiesce, ctx->search_quiesce_checks, 1, s, nullptr)))
       return rc;
   }
   HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
@@ -1997,6 +2000,7 @@ struct Search2Trace {
   }
   long listed = -1;  // the plies on the draw rules' list (read back for the report only)
   int quiesce = 0;   // the quiescence depth, with what the levels held and the slices of leaves
+  bool quiesce_checks = false;  // with the evasion records and the nodes in check per level
   QuiesceStats qstats;
   void report(size_t plies, size_t kids, size_t records, size_t chunks) {
     static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1",
@@ -2015,6 +2019,12 @@ struct Search2Trace {
         line += ",\"quiesce\":" + std::to_string(quiesce) + ",\"quiesce_slices\":" + std::to_string(qstats.slices) +
                 ",\"quiesce_records\":[";
         for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_records[l]);
+        if (quiesce_checks) {
+          line += "],\"quiesce_evasions\":[";
+          for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_evasions[l]);
+          line += "],\"quiesce_in_check\":[";
+          for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_in_check[l]);
+        }
         line += "],\"quiesce_redone\":" + std::to_string(qstats.redone) + ",\"quiesce_roots_ms\":" +
                 std::to_string(qstats.roots_ms) + ",\"quiesce_gen_ms\":" + std::to_string(qstats.gen_ms) +
                 ",\"quiesce_eval_ms\":" + std::to_string(qstats.eval_ms) + ",\"quiesce_reduce_ms\":" +
@@ -2222,8 +2232,9 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
       trace.quiesce = ctx->search_quiesce;
       trace.qstats.timed = trace.on;
       if ((rc = quiesce_leaves_device(ctx, ws, reinterpret_cast<const DBoard*>(chunk_states), nk, ch_off, nr, gend, gps,
-                                      gpo, ctx->search_quiesce, s, &trace.qstats)))
+                                      gpo, ctx->search_quiesce, ctx->search_quiesce_checks, 2, s, &trace.qstats)))
         return rc;
+      trace.quiesce_checks = ctx->search_quiesce_checks;
     }
     trace.mark(Search2Trace::kReduce1);
     HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
@@ -2599,16 +2610,29 @@ int fnnue_get_search_quiesce(const fnnue_ctx* ctx, int* depth) {
   return FNNUE_OK;
 }
 
+int fnnue_set_search_quiesce_checks(fnnue_ctx* ctx, int on) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  ctx->search_quiesce_checks = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_get_search_quiesce_checks(const fnnue_ctx* ctx, int* on) {
+  if (!ctx || !on) return fail(FNNUE_E_ARG, "null argument");
+  *on = ctx->search_quiesce_checks ? 1 : 0;
+  return FNNUE_OK;
+}
+
 int fnnue_quiesce_slices(const fnnue_ctx* ctx, uint64_t* slices) {
   if (!ctx || !slices) return fail(FNNUE_E_ARG, "null argument");
   *slices = ctx->quiesce_slices;
   return FNNUE_OK;
 }
 
-int fnnue_game_captures(const char* fen, const char* moves, fnnue_pos* out, size_t cap, fnnue_move* mv,
-                        size_t* n_out) {
-  if (!fen || !n_out) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = 0;
+namespace {
+// fnnue_game_captures / fnnue_game_quiet_moves: the game's last position, then
+// its captures, or (evasions, and the position in check) all its legal moves.
+int game_candidates(const char* fen, const char* moves, fnnue_pos* out, size_t cap, fnnue_move* mv, bool evasions,
+                    int* in_check, size_t* n_out) {
   Board b;
   std::string err;
   if (!board_from_fen(fen, b, &err)) return fail(FNNUE_E_FEN, err);
@@ -2626,11 +2650,13 @@ int fnnue_game_captures(const char* fen, const char* moves, fnnue_pos* out, size
   b.legal_moves(legal);
   const int them = b.stm ^ 1;
   const int before = __builtin_popcountll(b.byColor[them]);
+  const bool all = evasions && b.in_check();
+  if (in_check) *in_check = b.in_check() ? 1 : 0;
   for (const Move& m : legal) {
-    if (m.castle) continue;  // king takes own rook: no capture
+    if (m.castle && !all) continue;  // king takes own rook: no capture
     Board c = b;
     c.do_move(m);
-    if (__builtin_popcountll(c.byColor[them]) >= before) continue;
+    if (!all && __builtin_popcountll(c.byColor[them]) >= before) continue;
     res.push_back(c.pack());
     codes.push_back((fnnue_move)((uint32_t)m.from | (uint32_t)m.to << 6 | (uint32_t)m.promo << 12));
   }
@@ -2639,6 +2665,22 @@ int fnnue_game_captures(const char* fen, const char* moves, fnnue_pos* out, size
   std::memcpy(out, res.data(), res.size() * sizeof(fnnue_pos));
   std::memcpy(mv, codes.data(), codes.size() * sizeof(fnnue_move));
   return FNNUE_OK;
+}
+}  // namespace
+
+int fnnue_game_captures(const char* fen, const char* moves, fnnue_pos* out, size_t cap, fnnue_move* mv,
+                        size_t* n_out) {
+  if (!fen || !n_out) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = 0;
+  return game_candidates(fen, moves, out, cap, mv, false, nullptr, n_out);
+}
+
+int fnnue_game_quiet_moves(const char* fen, const char* moves, fnnue_pos* out, size_t cap, fnnue_move* mv,
+                           int* in_check, size_t* n_out) {
+  if (!fen || !n_out || !in_check) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = 0;
+  *in_check = 0;
+  return game_candidates(fen, moves, out, cap, mv, true, in_check, n_out);
 }
 
 int fnnue_quiesce_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
@@ -2671,7 +2713,8 @@ int fnnue_quiesce_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_f
     return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
                                   std::to_string(R.err_game));
   if (R.n_out > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  if ((rc = quiesce_nodes_device(ctx, ctx->bscratch, states, (uint32_t)R.n_out, (int)depth, d_out, s, nullptr)))
+  if ((rc = quiesce_nodes_device(ctx, ctx->bscratch, states, (uint32_t)R.n_out, (int)depth, ctx->search_quiesce_checks,
+                                 d_out, s, nullptr)))
     return rc;
   HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
   return FNNUE_OK;

@@ -43,6 +43,7 @@ struct fnnue_ctx {
   int ft_impl = FNNUE_FT_AUTO;
   bool search_draws = false;   // fnnue_set_search_draws: repetition and fifty-move draws in fnnue_search1 / 2
   int search_quiesce = 0;      // fnnue_set_search_quiesce: capture quiescence depth below the searches' leaves
+  bool search_quiesce_checks = false;  // fnnue_set_search_quiesce_checks: evasions and mates inside that tree
   uint64_t quiesce_slices = 0; // slices of root frontiers quiesce.hip has worked through (fnnue_quiesce_slices)
   int32_t acc_bound = 0;       // accumulator_bound of the net (the largest slice bound)
   uint64_t swar_eligible = 0;  // bit s: slice s's bound < 2^15, SWAR rows allowed (plan.swar: the enabled ones)
@@ -133,12 +134,14 @@ namespace fnnue {
 // nor kFinalDraw gets its two terms replaced in place by the reported terms of
 // Q_depth.  Runs behind the groups' evaluation on `s`, reads each level's size
 // back (synchronises `s`), evaluates through ctx, temporaries from ws.
+// checks: the rule Q'_depth (ABI 3.14); a decided leaf then gets (0, 16 * v) with
+// v `ply` further from the mate value (the leaves' depth in the search, 1 or 2).
 int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_parents, uint32_t n,
                           const uint32_t* d_off, uint32_t total, const uint8_t* d_end, int32_t* d_psqt,
-                          int32_t* d_positional, int depth, hipStream_t s, QuiesceStats* st);
+                          int32_t* d_positional, int depth, bool checks, int ply, hipStream_t s, QuiesceStats* st);
 // fnnue_quiesce_device's form: the n boards themselves are the roots, one
 // fnnue_quiet each (their own evaluation included).
 int quiesce_nodes_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_states, uint32_t n, int depth,
-                         fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st);
+                         bool checks, fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st);
 
 }  // namespace fnnue

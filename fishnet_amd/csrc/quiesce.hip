@@ -17,7 +17,13 @@
 //   quiet_reduce_kernel   one thread per node (a group is a handful of records):
 //                         stand pat against the negated results of its captures,
 //                         the first maximum wins.
-// No end flags, no checks, no mates inside the tree.  Each level's size is read
+// No end flags, no checks, no mates inside the tree: the plain rule.  With
+// "quiescence checks" (ABI 3.14) the generators and the results'
+// kernels run in their checks form (the template argument CHK): a node in check
+// lists all its legal moves and may not stand pat, a node in check without one
+// is mated, mate values lose one ply per level on the way up, and the children
+// of the last level, whose boards the plain form does not keep, are written and
+// probed for mates by mate_probe_kernel.  Each level's size is read
 // back once; a level above FNNUE_QUIESCE_RECORDS makes the host cut down the slice
 // of the root frontier it works on and redo it (one root's own tree is never cut).
 #include <hip/hip_runtime.h>
@@ -99,34 +105,100 @@ __device__ __forceinline__ fnnue_quiet stand_pat(int32_t ps, int32_t po) {
   return q;
 }
 
+// A decided (mate) result in the checks form: psqt 0, positional 16 * value.
+__device__ __forceinline__ fnnue_quiet decided(int32_t v, uint32_t nodes, uint16_t move, uint8_t len) {
+  fnnue_quiet q;
+  q.psqt = 0;
+  q.positional = 16 * v;
+  q.value = v;
+  q.nodes = nodes;
+  q.move = move;
+  q.len = len;
+  q.reserved = FNNUE_QUIET_DECIDED;
+  return q;
+}
+
+// Has b's side to move a legal move?
+__device__ __forceinline__ bool any_legal(const DBoard& b) {
+  bool any = false;
+  for_each_legal(b, [&](const DMove&) -> bool {
+    any = true;
+    return false;
+  });
+  return any;
+}
+
+// The node flags of the checks form.
+constexpr uint8_t kNodeInCheck = 1, kNodeMated = 2;
+
 // cnt[i]: the records of node i's group (1 + its captures, 0 without a capture),
 // has[i]: whether it forms one.  active (optional): nodes with 0 stay as they are.
+template <bool CHK>
 __global__ __launch_bounds__(kGenBlock) void capture_count_kernel(const DBoard* __restrict__ states,
                                                                   const uint8_t* __restrict__ active, uint32_t n,
                                                                   uint32_t* __restrict__ cnt,
-                                                                  uint32_t* __restrict__ has) {
+                                                                  uint32_t* __restrict__ has,
+                                                                  uint8_t* __restrict__ flag,
+                                                                  fnnue_quiet* __restrict__ above,
+                                                                  unsigned long long* __restrict__ evasions) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t c = 0;
+  uint8_t fl = 0;
   if (!active || active[i]) {
     const DBoard b = states[i];
-    for_each_capture(b, [&](const DMove&) -> bool {
+    auto count = [&](const DMove&) -> bool {
       ++c;
       return true;
-    });
+    };
+    if constexpr (CHK) {
+      // checks form: a node in check counts all its legal moves; without one it
+      // is mated, and its result in the level above (written before this kernel
+      // on the same stream) becomes the mate value
+      if (in_check(b)) {
+        fl = kNodeInCheck;
+        for_each_legal(b, count);
+        if (!c) {
+          fl |= kNodeMated;
+          above[i] = decided(-FNNUE_VALUE_MATE, 0, 0, 0);
+        } else if (evasions) {
+          atomicAdd(evasions, (unsigned long long)c);
+          atomicAdd(evasions + 1, 1ull);
+        }
+      } else {
+        for_each_capture(b, count);
+      }
+    } else {
+      for_each_capture(b, count);
+    }
   }
+  if constexpr (CHK) flag[i] = fl;
   cnt[i] = c ? c + 1 : 0;
   has[i] = c ? 1 : 0;
+}
+
+// The checks form's horizon: the boards that are not expanded (the children of
+// the last level, the roots at depth 0).  A side in check without a legal move
+// is mated at every depth; one that has a move stands pat here.
+__global__ __launch_bounds__(kGenBlock) void mate_probe_kernel(const DBoard* __restrict__ states, uint32_t n,
+                                                               fnnue_quiet* __restrict__ res) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DBoard b = states[i];
+  if (in_check(b) && !any_legal(b)) res[i] = decided(-FNNUE_VALUE_MATE, 0, 0, 0);
 }
 
 // One thread per record: record r belongs to the last node i with roff[i] <= r
 // (nodes without a group repeat their successor's offset); r - roff[i] = 0 is
 // the node itself, k > 0 its k-th capture.  Child k of node i is entry
 // roff[i] - gidx[i] + k - 1 of the next frontier.
+// Checks form: a node in check (flag) regenerates its legal moves instead.
+template <bool CHK>
 __global__ __launch_bounds__(kGenBlock) void capture_write_kernel(
     const DBoard* __restrict__ states, uint32_t n, const uint32_t* __restrict__ roff,
     const uint32_t* __restrict__ gidx, uint32_t total, uint32_t ngroups, fnnue_pos* __restrict__ out,
-    uint16_t* __restrict__ moves, uint32_t* __restrict__ goff, DBoard* __restrict__ next) {
+    uint16_t* __restrict__ moves, uint32_t* __restrict__ goff, DBoard* __restrict__ next,
+    const uint8_t* __restrict__ flag) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= total) return;
   uint32_t lo = 0, hi = n;  // roff[lo] <= r < roff[hi]
@@ -141,12 +213,18 @@ __global__ __launch_bounds__(kGenBlock) void capture_write_kernel(
   uint16_t mv = 0;
   if (k) {
     uint32_t j = 0;
-    for_each_capture(b, [&](const DMove& m) -> bool {
+    auto take = [&](const DMove& m) -> bool {
       if (++j < k) return true;
       do_move(c, m);
       mv = (uint16_t)((uint32_t)m.from | (uint32_t)m.to << 6 | (uint32_t)m.promo << 12);
       return false;
-    });
+    };
+    if constexpr (CHK) {
+      if (flag[lo] & kNodeInCheck) for_each_legal(b, take);  // no castling out of check: the code needs no flag
+      else for_each_capture(b, take);
+    } else {
+      for_each_capture(b, take);
+    }
     if (next) next[r - g - 1] = c;
   } else {
     goff[g] = r;
@@ -174,11 +252,15 @@ __global__ __launch_bounds__(kBlock) void quiet_leaves_kernel(const uint32_t* __
 // Node i's result by the rule: candidate 0 is standing pat (what node[i] holds),
 // the captures follow in order, a later one replaces the current only when it
 // is strictly greater.  Terms negated with int32 wrap-around, as fnnue_best's.
+// Checks form: a node in check has no candidate 0 (its first evasion is), and a
+// decided child result moves one ply toward zero when it is negated.
+template <bool CHK>
 __global__ __launch_bounds__(kBlock) void quiet_reduce_kernel(const uint32_t* __restrict__ roff,
                                                               const uint32_t* __restrict__ gidx, uint32_t n,
                                                               const uint16_t* __restrict__ moves,
                                                               const fnnue_quiet* __restrict__ child,
-                                                              fnnue_quiet* __restrict__ node) {
+                                                              fnnue_quiet* __restrict__ node,
+                                                              const uint8_t* __restrict__ flag) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t o = roff[i], e = roff[i + 1];
@@ -186,17 +268,29 @@ __global__ __launch_bounds__(kBlock) void quiet_reduce_kernel(const uint32_t* __
   const uint32_t base = o - gidx[i] - 1;
   fnnue_quiet best = node[i];
   uint32_t nodes = 0;
+  bool have = true;
+  if constexpr (CHK) have = !(flag[i] & kNodeInCheck);
   for (uint32_t k = 1; k < e - o; ++k) {
     const fnnue_quiet ch = child[base + k];
     nodes += 1u + ch.nodes;
+    if constexpr (CHK) {
+      if (ch.reserved & FNNUE_QUIET_DECIDED) {
+        const int32_t v = ch.value > 0 ? -(ch.value - 1) : -(ch.value + 1);
+        if (!have || v > best.value) best = decided(v, 0, moves[o + k], (uint8_t)(ch.len + 1));
+        have = true;
+        continue;
+      }
+    }
     const int32_t v = -ch.value;
-    if (v > best.value) {
+    if (!have || v > best.value) {
       best.psqt = (int32_t)(0u - (uint32_t)ch.psqt);
       best.positional = (int32_t)(0u - (uint32_t)ch.positional);
       best.value = v;
       best.move = moves[o + k];
       best.len = (uint8_t)(ch.len + 1);
+      if constexpr (CHK) best.reserved = 0;
     }
+    have = true;
   }
   best.nodes = nodes;
   node[i] = best;
@@ -219,15 +313,27 @@ __global__ __launch_bounds__(kBlock) void leaf_init_kernel(const uint2* __restri
   active[d] = (end[r] & (kFinalNoMoves | kFinalDraw)) ? 0 : 1;
 }
 
+// Checks form: a decided leaf at search depth p counts its plies from the
+// searched ply, p further from the mate value.
+template <bool CHK>
 __global__ __launch_bounds__(kBlock) void leaf_scatter_kernel(const uint2* __restrict__ map,
                                                               const uint32_t* __restrict__ off,
                                                               const uint8_t* __restrict__ active,
                                                               const fnnue_quiet* __restrict__ res, uint32_t nleaf,
-                                                              int32_t* __restrict__ ps, int32_t* __restrict__ po) {
+                                                              int32_t* __restrict__ ps, int32_t* __restrict__ po,
+                                                              int32_t p) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= nleaf || !active[d]) return;
   const uint2 m = map[d];
   const uint32_t r = off[m.x] + m.y;
+  if constexpr (CHK) {
+    if (res[d].reserved & FNNUE_QUIET_DECIDED) {
+      const int32_t v = res[d].value;
+      ps[r] = 0;
+      po[r] = 16 * (v > 0 ? v - p : v + p);
+      return;
+    }
+  }
   ps[r] = res[d].psqt;
   po[r] = res[d].positional;
 }
@@ -281,6 +387,8 @@ struct Marks {
 
 // One slice [a, b) of the root frontier through every level and back.
 // *overflow: a level passed the budget (nothing of the slice is reduced then).
+// CHK: the checks form (the mated roots and nodes are written on the way down).
+template <bool CHK>
 int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* active, size_t a, size_t b,
                   fnnue_quiet* res0, int depth, size_t budget, hipStream_t s, QuiesceStats* st, Marks& tm,
                   size_t* overflow) {
@@ -293,6 +401,13 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
   uint16_t* moves[FNNUE_QUIESCE_MAX + 1] = {};
   fnnue_quiet* res[FNNUE_QUIESCE_MAX + 1] = {};
   uint64_t recs[FNNUE_QUIESCE_MAX + 1] = {};
+  uint8_t* flag[FNNUE_QUIESCE_MAX + 1] = {};
+  // the trace's evasion counters, per level [evasion records, nodes in check with one]
+  unsigned long long* evas = nullptr;
+  if (CHK && st && st->timed) {
+    HIP_TRY(ws.get(W::kQEvasions, FNNUE_QUIESCE_MAX * 16, (void**)&evas), "device allocation (quiescence scratch)");
+    HIP_TRY(hipMemsetAsync(evas, 0, FNNUE_QUIESCE_MAX * 16, s), "hipMemsetAsync");
+  }
   res[0] = res0 + a;
   int deepest = 0;
   for (int L = 1; L <= depth && cur_n; ++L) {
@@ -305,8 +420,9 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
     HIP_TRY(ws.get(W::kQGidx + x, ((size_t)cur_n + 1) * 4, (void**)&gidx[L]), "device allocation (quiescence scratch)");
     HIP_TRY(hipMemsetAsync(cnt + cur_n, 0, 4, s), "hipMemsetAsync");
     HIP_TRY(hipMemsetAsync(has + cur_n, 0, 4, s), "hipMemsetAsync");
-    hipLaunchKernelGGL(capture_count_kernel, grid_for(cur_n, kGenBlock), dim3(kGenBlock), 0, s, cur, cur_active, cur_n,
-                       cnt, has);
+    if (CHK) HIP_TRY(ws.get(W::kQFlag + x, cur_n, (void**)&flag[L]), "device allocation (quiescence scratch)");
+    hipLaunchKernelGGL(capture_count_kernel<CHK>, grid_for(cur_n, kGenBlock), dim3(kGenBlock), 0, s, cur, cur_active,
+                       cur_n, cnt, has, flag[L], res[L - 1], evas ? evas + 2 * x : nullptr);
     HIP_TRY(hipGetLastError(), "capture_count launch");
     HIP_TRY(builder_exclusive_scan(cnt, roff[L], cur_n, s, ws), "capture scan");
     HIP_TRY(builder_exclusive_scan(has, gidx[L], cur_n, s, ws), "capture scan");
@@ -334,11 +450,11 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
     HIP_TRY(ws.get(W::kQMoves + x, (size_t)total * 2, (void**)&moves[L]), "device allocation (quiescence scratch)");
     HIP_TRY(ws.get(W::kQRes + x, (size_t)nkid * sizeof(fnnue_quiet), (void**)&res[L]),
             "device allocation (quiescence scratch)");
-    if (L < depth)
+    if (L < depth || CHK)  // the checks form keeps the last level's boards too: its mates are probed below
       HIP_TRY(ws.get(W::kQBoards + x, (size_t)nkid * sizeof(DBoard), (void**)&next),
               "device allocation (quiescence scratch)");
-    hipLaunchKernelGGL(capture_write_kernel, grid_for(total, kGenBlock), dim3(kGenBlock), 0, s, cur, cur_n, roff[L],
-                       gidx[L], total, ngroups, pos, moves[L], goff, next);
+    hipLaunchKernelGGL(capture_write_kernel<CHK>, grid_for(total, kGenBlock), dim3(kGenBlock), 0, s, cur, cur_n,
+                       roff[L], gidx[L], total, ngroups, pos, moves[L], goff, next, flag[L]);
     HIP_TRY(hipGetLastError(), "capture_write launch");
     tm.mark(Marks::kEval);
     if (int rc = fnnue_eval_groups_device(ctx, pos, goff, ngroups, total, FNNUE_GROUP_STAR, ps, po, s)) return rc;
@@ -346,6 +462,10 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
     hipLaunchKernelGGL(quiet_leaves_kernel, grid_for(cur_n, kBlock), dim3(kBlock), 0, s, roff[L], gidx[L], cur_n, ps,
                        po, res[L]);
     HIP_TRY(hipGetLastError(), "quiet_leaves launch");
+    if (CHK && L == depth) {  // the horizon: a mated child is mated at depth 0 as well
+      hipLaunchKernelGGL(mate_probe_kernel, grid_for(nkid, kGenBlock), dim3(kGenBlock), 0, s, next, nkid, res[L]);
+      HIP_TRY(hipGetLastError(), "mate_probe launch");
+    }
     level_n[L] = cur_n;
     recs[L] = total;
     deepest = L;
@@ -355,13 +475,22 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
   }
   tm.mark(Marks::kReduce);
   for (int L = deepest; L >= 1; --L) {
-    hipLaunchKernelGGL(quiet_reduce_kernel, grid_for(level_n[L], kBlock), dim3(kBlock), 0, s, roff[L], gidx[L],
-                       level_n[L], moves[L], res[L], res[L - 1]);
+    hipLaunchKernelGGL(quiet_reduce_kernel<CHK>, grid_for(level_n[L], kBlock), dim3(kBlock), 0, s, roff[L], gidx[L],
+                       level_n[L], moves[L], res[L], res[L - 1], flag[L]);
     HIP_TRY(hipGetLastError(), "quiet_reduce launch");
   }
   tm.mark(Marks::kEnd);
   if (st)
     for (int L = 1; L <= deepest; ++L) st->level_records[L - 1] += recs[L];
+  if (evas) {  // the trace only: one more wait
+    unsigned long long h[2 * FNNUE_QUIESCE_MAX] = {};
+    HIP_TRY(hipMemcpyAsync(h, evas, sizeof(h), hipMemcpyDeviceToHost, s), "D2H(evasion counters)");
+    HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+    for (int l = 0; l < FNNUE_QUIESCE_MAX; ++l) {
+      st->level_evasions[l] += h[2 * l];
+      st->level_in_check[l] += h[2 * l + 1];
+    }
+  }
   return FNNUE_OK;
 }
 
@@ -369,14 +498,16 @@ int quiesce_slice(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* act
 // some level is cut down (to what the level's size says fits, at most to half)
 // and redone; the next slice starts with the size that fit.
 int quiesce_frontier(fnnue_ctx* ctx, W& ws, const DBoard* roots, const uint8_t* active, size_t n, fnnue_quiet* res0,
-                     int depth, hipStream_t s, QuiesceStats* st, Marks& tm) {
+                     int depth, bool checks, hipStream_t s, QuiesceStats* st, Marks& tm) {
   const size_t budget = quiesce_budget();
   size_t step = std::min(n, budget);
   for (size_t a = 0; a < n;) {
     size_t b = std::min(n, a + step);
     for (;;) {
       size_t overflow = 0;  // the records of the level that passed the bound
-      if (int rc = quiesce_slice(ctx, ws, roots, active, a, b, res0, depth, budget, s, st, tm, &overflow)) return rc;
+      if (int rc = checks ? quiesce_slice<true>(ctx, ws, roots, active, a, b, res0, depth, budget, s, st, tm, &overflow)
+                          : quiesce_slice<false>(ctx, ws, roots, active, a, b, res0, depth, budget, s, st, tm, &overflow))
+        return rc;
       if (!overflow) break;
       const size_t fits = (size_t)((double)(b - a) * (double)budget / (double)overflow * 0.875);
       step = std::max<size_t>(1, std::min(fits, (b - a) / 2));
@@ -400,7 +531,7 @@ size_t quiesce_budget() {
 
 int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_parents, uint32_t n,
                           const uint32_t* d_off, uint32_t total, const uint8_t* d_end, int32_t* d_psqt,
-                          int32_t* d_positional, int depth, hipStream_t s, QuiesceStats* st) {
+                          int32_t* d_positional, int depth, bool checks, int ply, hipStream_t s, QuiesceStats* st) {
   if (depth <= 0 || n == 0 || total <= n) return FNNUE_OK;
   if (depth > FNNUE_QUIESCE_MAX) return fail(FNNUE_E_ARG, "quiescence depth above FNNUE_QUIESCE_MAX");
   const uint32_t nleaf = total - n;
@@ -421,10 +552,14 @@ int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_pa
   hipLaunchKernelGGL(leaf_init_kernel, grid_for(nleaf, kBlock), dim3(kBlock), 0, s, map, d_off, d_end, d_psqt,
                      d_positional, nleaf, res0, active);
   HIP_TRY(hipGetLastError(), "leaf_init launch");
-  if (int rc = quiesce_frontier(ctx, ws, roots, active, nleaf, res0, depth, s, st, tm)) return rc;
+  if (int rc = quiesce_frontier(ctx, ws, roots, active, nleaf, res0, depth, checks, s, st, tm)) return rc;
   tm.mark(Marks::kRoots);
-  hipLaunchKernelGGL(leaf_scatter_kernel, grid_for(nleaf, kBlock), dim3(kBlock), 0, s, map, d_off, active, res0, nleaf,
-                     d_psqt, d_positional);
+  if (checks)
+    hipLaunchKernelGGL(leaf_scatter_kernel<true>, grid_for(nleaf, kBlock), dim3(kBlock), 0, s, map, d_off, active, res0,
+                       nleaf, d_psqt, d_positional, (int32_t)ply);
+  else
+    hipLaunchKernelGGL(leaf_scatter_kernel<false>, grid_for(nleaf, kBlock), dim3(kBlock), 0, s, map, d_off, active, res0,
+                       nleaf, d_psqt, d_positional, 0);
   HIP_TRY(hipGetLastError(), "leaf_scatter launch");
   tm.mark(Marks::kEnd);
   tm.report(st);
@@ -432,7 +567,7 @@ int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_pa
 }
 
 int quiesce_nodes_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_states, uint32_t n, int depth,
-                         fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st) {
+                         bool checks, fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st) {
   if (n == 0) return FNNUE_OK;
   if (depth < 0 || depth > FNNUE_QUIESCE_MAX) return fail(FNNUE_E_ARG, "quiescence depth above FNNUE_QUIESCE_MAX");
   fnnue_pos* pos = nullptr;
@@ -445,9 +580,15 @@ int quiesce_nodes_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_sta
   if (int rc = fnnue_eval_positions_device(ctx, pos, n, ps, po, s)) return rc;
   hipLaunchKernelGGL(node_init_kernel, grid_for(n, kBlock), dim3(kBlock), 0, s, ps, po, n, d_out);
   HIP_TRY(hipGetLastError(), "node_init launch");
-  if (depth == 0) return FNNUE_OK;
+  if (depth == 0) {
+    if (checks) {  // a mated ply is mated at depth 0 as well
+      hipLaunchKernelGGL(mate_probe_kernel, grid_for(n, kGenBlock), dim3(kGenBlock), 0, s, d_states, n, d_out);
+      HIP_TRY(hipGetLastError(), "mate_probe launch");
+    }
+    return FNNUE_OK;
+  }
   Marks tm;  // untimed
-  return quiesce_frontier(ctx, ws, d_states, nullptr, n, d_out, depth, s, st, tm);
+  return quiesce_frontier(ctx, ws, d_states, nullptr, n, d_out, depth, checks, s, st, tm);
 }
 
 }  // namespace fnnue

@@ -269,6 +269,8 @@ MAX_CHILDREN = N.MAX_CHILDREN
 QUIET_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("nodes", "<u4"), ("move", "<u2"),
                         ("len", "u1"), ("reserved", "u1")])
 QUIESCE_MAX = 4
+VALUE_MATE = 32000     # FNNUE_VALUE_MATE (ABI 3.14): the value of a mated position under quiescence checks
+QUIET_DECIDED = 1      # FNNUE_QUIET_DECIDED in QUIET_DTYPE's "reserved" byte
 # fnnue_line2: one of a ply's k best lines at two plies (move, reply); kind BEST_NONE = an unused slot
 LINE2_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("value", "<i4"), ("child", "<u4"),
                         ("reply_index", "<u4"), ("move", "<u2"), ("reply", "<u2"), ("kind", "u1"), ("pv_len", "u1"),
@@ -547,6 +549,16 @@ class Evaluator:
         d = C.c_int()
         N.check(N.lib.fnnue_get_search_quiesce(self._h, C.byref(d)))
         return d.value
+
+    def set_search_quiesce_checks(self, on: bool) -> None:
+        """fnnue_set_search_quiesce_checks: the quiescence of the searches and of quiesce() follows Q' (ABI
+        3.14): a node in check lists its evasions and may not stand pat, mates are values near VALUE_MATE."""
+        N.check(N.lib.fnnue_set_search_quiesce_checks(self._h, 1 if on else 0))
+
+    def search_quiesce_checks(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_get_search_quiesce_checks(self._h, C.byref(on)))
+        return bool(on.value)
 
     def quiesce_slices(self) -> int:
         """fnnue_quiesce_slices: the slices of leaves the context's quiescence has worked through so far."""
@@ -1132,6 +1144,21 @@ def game_captures(fen: str, moves: str | list[str] = "") -> tuple[np.ndarray, np
     n = C.c_size_t()
     N.check(N.lib.fnnue_game_captures(fen.encode(), moves.encode(), N.ptr(out), cap, N.ptr(mv), C.byref(n)))
     return out[: n.value], mv[: n.value]
+
+
+def game_quiet_moves(fen: str, moves: str | list[str] = "") -> tuple[np.ndarray, np.ndarray, bool]:
+    """fnnue_game_quiet_moves: the game's last position followed by the candidates of the quiescence with
+    checks (every legal move when the position is in check, its captures otherwise, in the order of
+    game_children) -> (positions, uint16 move codes with codes[0] = 0, in check)."""
+    if not isinstance(moves, str):
+        moves = " ".join(moves)
+    cap = 256
+    out = N.positions_array(cap)
+    mv = np.zeros(cap, dtype=np.uint16)
+    n, chk = C.c_size_t(), C.c_int()
+    N.check(N.lib.fnnue_game_quiet_moves(fen.encode(), moves.encode(), N.ptr(out), cap, N.ptr(mv), C.byref(chk),
+                                         C.byref(n)))
+    return out[: n.value], mv[: n.value], bool(chk.value)
 
 
 def random_playouts(seed: int, count: int, min_plies: int = 0, max_plies: int = 160,

@@ -893,7 +893,8 @@ int fnnue_get_search_draws(const fnnue_ctx *ctx, int *on);
  *    line_{d-1}(X.c); the line's end is the position after its last capture.
  *  - Checks, mates and stalemates are not recognised inside the tree: a side in
  *    check may stand pat, and a position without a legal move has no captures
- *    and is worth s.  This limit is deliberate; check evasions are out of scope.
+ *    and is worth s.  This is the plain rule; "quiescence checks" (ABI 3.14,
+ *    below) is the opt-in rule Q' that recognises evasions and mates.
  *  - The reported terms are the psqt / positional of the line's end, negated
  *    with int32 wrap-around (as fnnue_best negates) exactly when the line has an
  *    odd number of captures.  For terms that do not wrap, value ==
@@ -930,7 +931,7 @@ typedef struct {            /* 20 bytes */
   uint32_t nodes;           /* capture records below the position */
   fnnue_move move;          /* the line's first capture, 0 when standing pat */
   uint8_t len;              /* captures in the line, 0..d */
-  uint8_t reserved;         /* 0 */
+  uint8_t reserved;         /* FNNUE_QUIET_DECIDED with quiescence checks and a decided result, else 0 */
 } fnnue_quiet;
 /* Host only: the game's last position followed by its capture children
  * (caps() above, in order) with their move codes, mv[0] = 0; cap entries in out
@@ -957,6 +958,66 @@ int fnnue_get_search_quiesce(const fnnue_ctx *ctx, int *depth);
 /* Diagnostics: the slices of leaves (whole frontiers count as one) the
  * context's quiescence has worked through since it was created. */
 int fnnue_quiesce_slices(const fnnue_ctx *ctx, uint64_t *slices);
+
+/* ---- check evasions and mates inside the capture quiescence (ABI 3.14) ----
+ * The plain rule lets a side in check stand pat and scores a capture that
+ * mates as the material it takes.  "Quiescence checks", an opt-in setting
+ * (fnnue_set_search_quiesce_checks, off by default), replaces Q_d by Q'_d.
+ * For a chess position X and a remaining depth d in 0..FNNUE_QUIESCE_MAX:
+ *  - chk(X): X's side to move is in check.
+ *  - cand(X): all of X's legal moves when chk(X), in the order of X's children
+ *    in fnnue_build_children; caps(X) otherwise, unchanged.
+ *  - Mated: if chk(X) and X has no legal move, X is mated at every d, 0
+ *    included: value -FNNUE_VALUE_MATE, line empty, nodes 0.
+ *  - Horizon: otherwise Q'_0(X) = s(X).  A side in check that still has a move
+ *    stands pat at the horizon; this is a stated limit.
+ *  - In check, d >= 1: Q'_d(X) = max over cand(X) of the negated child result.
+ *    No standing pat: candidate 0 is the first evasion, and a later candidate
+ *    replaces the current one only when it is strictly greater.
+ *  - Not in check, d >= 1: as Q_d, stand pat is candidate 0, then the captures.
+ *    A position that is not in check and has no capture stands pat: stalemate
+ *    is not recognised, as before.
+ *  - Negating a decided (mate) child result moves it one ply toward zero:
+ *    child -32000 gives the parent 31999, child 31999 gives -31998, and so on.
+ *    Undecided results negate as before.
+ *  - Reported terms.  A decided result reports psqt = 0 and positional = 16 *
+ *    value, so value == trunc((psqt + positional) / 16) still holds, and its
+ *    `reserved` byte carries FNNUE_QUIET_DECIDED.  An undecided result reports
+ *    the terms of its line's end exactly as Q_d does, with `reserved` 0; with
+ *    the setting off `reserved` is always 0.
+ *  - nodes counts every record of the tree, evasions included; move / len
+ *    describe the line, which may start with and contain quiet evasions.
+ *  - Domain: static values must satisfy |s| < FNNUE_VALUE_MATE - 64 (real nets
+ *    are far below).  Beyond that, results are unspecified with the setting on.
+ *  - Draws: a quiet evasion can repeat an earlier position, so "a node below a
+ *    capture cannot repeat" no longer covers every node of the tree.  Nodes
+ *    inside the tree are still not tested for draws; leaves with DRAW or
+ *    NO_MOVES stay untouched, as before.
+ *
+ * In the searches a leaf at search depth p (1 in the one-ply searches, 2 in
+ * the two-ply ones) whose Q' is decided gets the terms (0, 16 * v) with |v| =
+ * FNNUE_VALUE_MATE - (p + n), n the mate's distance inside the tree: the leaf
+ * counts plies from the searched ply.  The reductions, ranks and kinds are
+ * untouched: a coded mate is an ordinary FNNUE_BEST_CP value, which ranks
+ * below a flagged mate in 1 and above a flagged FNNUE_BEST_MATED.
+ * fnnue_quiesce[_device] reports distances from the ply itself (p = 0).  With
+ * the setting off, or with quiescence depth 0 in the searches, every byte of
+ * every result is that of ABI 3.13.  The setting governs fnnue_search1[_lines],
+ * fnnue_search2[_children|_lines], their _device forms and
+ * fnnue_quiesce[_device]; a variant net's context accepts and ignores it.
+ * Evasion records count toward FNNUE_QUIESCE_RECORDS like capture records.
+ * Out of scope: variants, quiet checks or quiet promotions as candidates,
+ * stalemate and draw tests inside the tree, pruning. */
+#define FNNUE_VALUE_MATE 32000
+#define FNNUE_QUIET_DECIDED 1
+int fnnue_set_search_quiesce_checks(fnnue_ctx *ctx, int on);
+int fnnue_get_search_quiesce_checks(const fnnue_ctx *ctx, int *on);
+/* Host only: the game's last position followed by cand() of it in order, with
+ * the move codes (mv[0] = 0) and *in_check = chk(); capacity and error protocol
+ * as fnnue_game_captures.  A position in check lists every legal move, any
+ * other its captures. */
+int fnnue_game_quiet_moves(const char *fen, const char *moves, fnnue_pos *out, size_t cap, fnnue_move *mv,
+                           int *in_check, size_t *n_out);
 
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware

@@ -435,6 +435,19 @@ int fnnue_backend_draw_rules(fnnue_backend *b, int *on);
 int fnnue_backend_set_quiesce(fnnue_backend *b, int depth);
 int fnnue_backend_quiesce(fnnue_backend *b, int *depth);
 
+/* ---- check evasions and mates inside the quiescence (ABI 3.14) ----
+ * fnnue_backend_set_quiesce_checks(b, on) (off by default): the quiescence of
+ * the chess analysis batches follows Q' (fnnue.h), and a FNNUE_BEST_CP result
+ * or line whose |value| > FNNUE_VALUE_MATE - 64 is answered as
+ * FNNUE_SCORE_MATE: plies = FNNUE_VALUE_MATE - |value|, a win is +(plies + 1)
+ * / 2, a loss -plies / 2, at every fill site (best, best2, lines, lines2, the
+ * compact form; the JSON prints "mate").  Reported psqt / positional are the
+ * coded terms.  With the setting off no value is ever remapped.  Move work,
+ * variant batches, depth-0 analysis and batches with quiescence depth 0 are
+ * unchanged. */
+int fnnue_backend_set_quiesce_checks(fnnue_backend *b, int on);
+int fnnue_backend_quiesce_checks(fnnue_backend *b, int *on);
+
 /* ---- MultiPV at two plies (ABI 3.11) ----
  * One line of a response with its whole pv, as the reference keeps one
  * Vec<Uci> per MultiPV line at the searched depth ([ref] src/ipc.rs:68-93). */

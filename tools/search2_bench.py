@@ -1,7 +1,7 @@
 """Times of the two-ply search (fnnue_search2_device) and of the engine actor
 at two plies.  GPU box only.  One JSON line per measurement.
 
-    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218] [--draws N] [--quiesce D]
+    python tools/search2_bench.py [--games 200] [--plies 60] [--hd 1024] [--runs 3] [--actor] [--lines 3,218] [--draws N] [--quiesce D] [--quiesce-checks]
                                   [--variant crazyhouse|atomic|kingofthehill|racingkings|threecheck]
 
 The shape: N random legal games of L plies each from the start position
@@ -37,7 +37,10 @@ whose line carries history_ms, mark_ms and draw_list (the plies on the list).
 capture quiescence depth (fnnue_set_search_quiesce) at 0, 1, .. D, in this process on the same games (phases
 search1_quiesce_d / search2_quiesce_d: median, min, max of the device time between two events, and the host's
 wall time, which holds the level read-backs), and one traced search2 call per depth, whose line carries
-quiesce_ms, the per-level record counts and the slice count.
+quiesce_ms, the per-level record counts and the slice count.  With `--quiesce-checks` every depth above 0 is
+measured twice in the same rounds, quiescence checks (fnnue_set_search_quiesce_checks) off and on (phases
+search1_quiesce_d / search2_quiesce_d and ..._d_checks), and the traced calls with the setting on carry
+quiesce_evasions and quiesce_in_check per level (the evasion records, the nodes in check that had one).
 `--piece-plies A,B,...` repeats the 2-plies actor lines with those values of
 FNNUE_BACKEND_PIECE_PLIES (a two-plies piece is a 1024th of it).
 """
@@ -74,6 +77,7 @@ def main():
     ap.add_argument("--lines", default="")
     ap.add_argument("--draws", type=int, default=0)
     ap.add_argument("--quiesce", type=int, default=0)
+    ap.add_argument("--quiesce-checks", action="store_true")
     a = ap.parse_args()
     import torch
     import fishnet_amd as F
@@ -235,27 +239,33 @@ def quiesce_rounds(a, ev, stream, search1, search2, base):
         ev.check()
         return e0.elapsed_time(e1), wall
 
-    depths = list(range(a.quiesce + 1))
+    depths = [(d, False) for d in range(a.quiesce + 1)]
+    if a.quiesce_checks:  # every depth above 0 with the setting off and on, interleaved
+        depths = sorted(depths + [(d, True) for d in range(1, a.quiesce + 1)])
     rounds = max(a.runs, 3)
     ms = {(n, d): [] for n in ("search1", "search2") for d in depths}
     for _ in range(rounds):
-        for d in depths:
+        for d, checks in depths:
             ev.set_search_quiesce(d)
-            ms[("search1", d)].append(timed(search1))
-            ms[("search2", d)].append(timed(search2))
-    for (name, d), v in ms.items():
+            ev.set_search_quiesce_checks(checks)
+            ms[("search1", (d, checks))].append(timed(search1))
+            ms[("search2", (d, checks))].append(timed(search2))
+    for (name, (d, checks)), v in ms.items():
         dev_ms, wall = sorted(x[0] for x in v), sorted(x[1] for x in v)
-        print(json.dumps(dict(base, phase=f"{name}_quiesce_{d}", rounds=rounds, ms=[round(x, 4) for x in dev_ms],
+        print(json.dumps(dict(base, phase=f"{name}_quiesce_{d}" + ("_checks" if checks else ""), rounds=rounds,
+                              ms=[round(x, 4) for x in dev_ms],
                               median_ms=round(dev_ms[len(dev_ms) // 2], 4), min_ms=round(dev_ms[0], 4),
                               max_ms=round(dev_ms[-1], 4), wall_median_ms=round(wall[len(wall) // 2], 4))), flush=True)
     os.environ["FNNUE_SEARCH2_TRACE"] = "1"
-    for d in depths[1:]:
+    for d, checks in depths[1:]:
         ev.set_search_quiesce(d)
+        ev.set_search_quiesce_checks(checks)
         with torch.cuda.stream(stream):
             search2()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     ev.set_search_quiesce(0)
+    ev.set_search_quiesce_checks(False)
 
 
 def actor_lines(a):
