@@ -81,6 +81,7 @@
 #include "board.h"
 #include "builder.h"
 #include "internal.h"
+#include "search_steps.h"
 #include "text_scan.h"
 #include "vboard.h"
 #include "workers.h"
@@ -147,6 +148,13 @@ struct DevBuf {
     return reinterpret_cast<T*>(static_cast<char*>(p) + off);
   }
 };
+// b with at least `bytes`, *out its start.
+template <class T>
+int reserve(DevBuf& b, size_t bytes, T** out) {
+  const int rc = b.reserve(bytes);
+  *out = static_cast<T*>(b.p);
+  return rc;
+}
 
 // Grow-only pinned host buffer (the DMA engines read / write it directly, so
 // the copies are asynchronous and need no staging through pageable memory).
@@ -182,11 +190,6 @@ size_t count_moves(const char* s) {
 // A position without a legal move with one of these is lost (`mate 0`), else drawn (`cp 0`).
 constexpr uint8_t kFinalDecided = kFinalCheck | kFinalExtinct | kFinalVariant;
 
-int64_t to_cp(int32_t psqt, int32_t positional, int32_t norm) {
-  const int64_t v = ((int64_t)psqt + positional) / 16;  // OutputScale, C truncation
-  return v * 100 / norm;
-}
-
 // A root with no legal move: the engine prints `info depth 0 score mate 0`
 // (checkmated; atomic: its king exploded; kingofthehill / racingkings: lost
 // by the variant's rule) or `score cp 0` (stalemate, a racingkings draw) and
@@ -201,6 +204,51 @@ void terminal_response(fnnue_position_response& r, uint8_t fin) {
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// A search record's (kind, value) as an answer's (FNNUE_SCORE_*, score), for a
+// piece answered in units of `norm`: a mate in one and its mirror images
+// (mated: every move allows a mate in one; lost: every move loses at once) are
+// Score::Mate(1) / Mate(-1).  coded: with quiescence checks a FNNUE_BEST_CP
+// value beyond the static domain is a coded mate, answered as Score::Mate of
+// its moves.  Everything else is centipawns.  One rule for every record: only
+// the replies' kernels emit FNNUE_BEST_MATED, so no one-ply answer changes by it;
+// fill() answers a depth-0 ply as a FNNUE_BEST_CP record of its own value, no move.
+struct Answer { uint8_t kind; int64_t score; };
+struct ScoreRule {
+  int32_t norm;
+  bool coded;
+  Answer operator()(uint8_t kind, int64_t value) const {
+    if (kind == FNNUE_BEST_MATE) return {FNNUE_SCORE_MATE, 1};
+    if (kind == FNNUE_BEST_MATED || kind == FNNUE_BEST_LOST) return {FNNUE_SCORE_MATE, -1};
+    const int64_t a = value < 0 ? -value : value;
+    if (coded && kind == FNNUE_BEST_CP && a > FNNUE_VALUE_MATE - 64) {
+      const int64_t plies = FNNUE_VALUE_MATE - a;
+      if (const int64_t moves = value > 0 ? (plies + 1) / 2 : -(plies / 2)) return {FNNUE_SCORE_MATE, moves};
+    }
+    return {FNNUE_SCORE_CP, value * 100 / norm};
+  }
+};
+
+// A move code of net k's rules as UCI text (a variant's may be a drop).
+void move_uci(int k, fnnue_move m, char* out) {
+  (void)(k == kVariantChess ? fnnue_move_uci(m, out) : fnnue_vmove_uci(m, out));
+}
+
+// A fnnue_line2, or a fnnue_line with reply "", as the answer's line with its whole pv.
+template <class Line>
+fnnue_pv_line2 pv_line2(int k, const ScoreRule& rule, const Line& L, const char* reply) {
+  char mv[8] = {0};
+  move_uci(k, L.move, mv);
+  const Answer a = rule(L.kind, L.value);
+  fnnue_pv_line2 out{};
+  out.score = a.score;
+  out.psqt = L.psqt;
+  out.positional = L.positional;
+  std::snprintf(out.pv, sizeof(out.pv), "%s%s%s", mv, reply[0] ? " " : "", reply);
+  out.score_kind = a.kind;
+  out.pv_len = reply[0] ? 2 : 1;
+  return out;
+}
 
 // MultiPV slots per ply of an analysis batch: Some(k) asks for k lines, and a
 // ply has at most FNNUE_MAX_CHILDREN legal moves.
@@ -874,11 +922,7 @@ int fnnue_backend::stage_eval(int k, size_t pi) {
   } else if (P.ng) {
     const uint32_t* d_off = reinterpret_cast<const uint32_t*>(dimg + P.o_ply);
     const void* d_pos = W.pos.at<char>(P.pos0);
-    const int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(d_pos), d_off, P.ng, P.n,
-                                                    FNNUE_GROUP_CHAIN, d_ps, d_po, s)
-                         : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(d_pos), d_off, P.ng, P.n,
-                                                     FNNUE_GROUP_CHAIN, d_ps, d_po, s);
-    if (rc) return rc;
+    if (int rc = eval_groups(SearchRules{k}, c, d_pos, d_off, P.ng, P.n, FNNUE_GROUP_CHAIN, d_ps, d_po, s)) return rc;
   }
   if (P.nk) {
     const void* d_kids = dimg + P.o_kids;
@@ -911,154 +955,104 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   hipStream_t s = c->stream;
   char* dimg = W.dev.at<char>(P.dev0);
   const uint32_t n = P.n;
-  const bool chess = k == kVariantChess;
-  const void* states = W.states.at<char>(P.st0);
-  if (int rc = W.kid_cnt.reserve((size_t)(n + 1) * 4)) return rc;
-  if (int rc = W.kid_off.reserve((size_t)(n + 1) * 4)) return rc;
+  const SearchRules rules{k};
+  // this backend's bounded wait for a size the device wrote to hs[1]
   if (int rc = W.sizing.reserve(8)) return rc;
-  uint32_t* coff = W.kid_off.at<uint32_t>(0);
-  HIP_TRY(chess ? children_count_device(static_cast<const DBoard*>(states), n, W.kid_cnt.at<uint32_t>(0), coff, s,
-                                        W.bscratch)
-                : vchildren_count_device(k, states, n, W.kid_cnt.at<uint32_t>(0), coff, s, W.bscratch),
-          "children count launch");
   uint32_t* hs = W.sizing.at<uint32_t>(0);
+  auto read_size = [&](const uint32_t* d_size, const char* what) {
+    HIP_TRY(hipMemcpyAsync(hs + 1, d_size, 4, hipMemcpyDeviceToHost, s), "D2H(size)");
+    HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(size)");
+    const auto tw = Clock::now();
+    const int rc = wait_event(W.ev_done[pi], what);
+    wait_ms += ms_since(tw);
+    ++syncs;
+    return rc;
+  };
+  StarGroups g;  // the plies' groups: their children
+  g.states = W.states.at<char>(P.st0);
+  g.n = n;
+  uint32_t *cnt = nullptr, *coff = nullptr;
+  if (int rc = reserve(W.kid_cnt, (size_t)(n + 1) * 4, &cnt)) return rc;
+  if (int rc = reserve(W.kid_off, (size_t)(n + 1) * 4, &coff)) return rc;
+  g.off = coff;
+  HIP_TRY(count_children(rules, g.states, n, cnt, coff, s, W.bscratch), "children count launch");
   HIP_TRY(hipMemcpyAsync(hs, dimg + P.o_res, 4, hipMemcpyDeviceToHost, s), "D2H(builder error)");
-  HIP_TRY(hipMemcpyAsync(hs + 1, coff + n, 4, hipMemcpyDeviceToHost, s), "D2H(children count)");
-  HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(children count)");
-  const auto tw = Clock::now();
-  const int rcw = wait_event(W.ev_done[pi], "sizing a piece's children");
-  wait_ms += ms_since(tw);
-  ++syncs;
-  if (rcw) return rcw;
+  if (int rc = read_size(coff + n, "sizing a piece's children")) return rc;
   if (hs[0]) return FNNUE_OK;  // a rejected game: its boards are not those of a game
   const size_t total = hs[1];
-  if (int rc = W.kid_pos.reserve(total * W.rec)) return rc;
-  if (int rc = W.kid_moves.reserve(total * 2)) return rc;
-  if (int rc = W.kid_end.reserve(total)) return rc;
-  if (int rc = W.kid_ps.reserve(total * 4)) return rc;
-  if (int rc = W.kid_po.reserve(total * 4)) return rc;
-  void* kp = W.kid_pos.at<char>(0);
-  uint16_t* km = W.kid_moves.at<uint16_t>(0);
-  uint8_t* ke = W.kid_end.at<uint8_t>(0);
-  int32_t* kps = W.kid_ps.at<int32_t>(0);
-  int32_t* kpo = W.kid_po.at<int32_t>(0);
-  HIP_TRY(chess ? children_write_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total,
-                                        static_cast<fnnue_pos*>(kp), km, ke, s)
-                : vchildren_write_device(k, states, n, coff, (uint32_t)total, static_cast<fnnue_vpos*>(kp), km, ke, s),
-          "children launch");
+  g.total = (uint32_t)total;
+  void* kp = nullptr;
+  uint16_t* km = nullptr;
+  if (int rc = reserve(W.kid_pos, total * W.rec, &kp)) return rc;
+  if (int rc = reserve(W.kid_moves, total * 2, &km)) return rc;
+  if (int rc = reserve(W.kid_end, total, &g.end)) return rc;
+  if (int rc = reserve(W.kid_ps, total * 4, &g.psqt)) return rc;
+  if (int rc = reserve(W.kid_po, total * 4, &g.positional)) return rc;
+  g.moves = km;
+  HIP_TRY(write_children(rules, g.states, n, coff, g.total, kp, km, g.end, s), "children launch");
   // The draw rules (fnnue_backend_set_draw_rules, chess batches): a piece holds
   // whole games (plan() never cuts one), so the history of its plies is
   // complete; the marks go on the listed plies' children here and on their
   // grandchildren behind the second expansion, before the reductions.
-  const bool draws = chess && draw_rules;
+  SearchSettings set{nullptr, rules.chess() ? quiesce : 0, quiesce_checks};
   DrawHistory hist;
-  if (draws) {
-    HIP_TRY(game_history_device(dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
-                                reinterpret_cast<const uint32_t*>(dimg + P.o_mv),
-                                reinterpret_cast<const uint32_t*>(dimg + P.o_ply), P.ng,
-                                static_cast<const DBoard*>(states), n, draw_key_bits(), s, W.bscratch, &hist),
-            "game history launch");
-    HIP_TRY(mark_draws_level1(hist, static_cast<const DBoard*>(states), n, coff, km, ke, s), "draw marks launch");
+  if (rules.chess() && draw_rules) {
+    if (int rc = draw_history_level1(dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
+                                     reinterpret_cast<const uint32_t*>(dimg + P.o_mv),
+                                     reinterpret_cast<const uint32_t*>(dimg + P.o_ply), P.ng, g.states, n, coff, km,
+                                     g.end, s, W.bscratch, &hist, nullptr))
+      return rc;
+    set.draws = &hist;
   }
-  if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(kp), coff, n, total, FNNUE_GROUP_STAR,
-                                                kps, kpo, s)
-                     : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(kp), coff, n, total,
-                                                 FNNUE_GROUP_STAR, kps, kpo, s))
-    return rc;
+  if (int rc = eval_groups(rules, c, kp, coff, n, total, FNNUE_GROUP_STAR, g.psqt, g.positional, s)) return rc;
   P.searched = total - n;
+  QuiesceStats qs;
   if (P.depth2) {
     // Two plies: the children's boards, their own children counted and the
-    // count read back (the second sizing wait), expanded and evaluated, one
-    // fnnue_best per child, then the second reduction into the results image.
+    // count read back (the second sizing wait), then the piece as one chunk:
+    // one fnnue_best per child; the second reduction into the results image,
+    // and for a go_lines_pv() call the lines with their replies.
     const size_t nkid = total - n;
-    if (int rc = W.kid_best.reserve((nkid + 1) * sizeof(fnnue_best))) return rc;
-    fnnue_best* kb = W.kid_best.at<fnnue_best>(0);
+    fnnue_best* kb = nullptr;
+    if (int rc = reserve(W.kid_best, (nkid + 1) * sizeof(fnnue_best), &kb)) return rc;
     if (nkid) {
-      if (int rc = W.kid_states.reserve(nkid * (chess ? sizeof(DBoard) : vstate_bytes(k)))) return rc;
-      if (int rc = W.kid2_cnt.reserve((nkid + 1) * 4)) return rc;
-      if (int rc = W.kid2_off.reserve((nkid + 1) * 4)) return rc;
-      void* ks = W.kid_states.at<char>(0);
-      uint32_t* goff = W.kid2_off.at<uint32_t>(0);
-      HIP_TRY(chess ? child_states_device(static_cast<const DBoard*>(states), n, coff, (uint32_t)total,
-                                          static_cast<DBoard*>(ks), nullptr, s)
-                    : vchild_states_device(k, states, n, coff, (uint32_t)total, ks, nullptr, s),
-              "child_states launch");
-      HIP_TRY(chess ? children_count_device(static_cast<const DBoard*>(ks), (uint32_t)nkid,
-                                            W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch)
-                    : vchildren_count_device(k, ks, (uint32_t)nkid, W.kid2_cnt.at<uint32_t>(0), goff, s, W.bscratch),
-              "grandchildren count launch");
-      HIP_TRY(hipMemcpyAsync(hs + 1, goff + nkid, 4, hipMemcpyDeviceToHost, s), "D2H(grandchildren count)");
-      HIP_TRY(hipEventRecord(W.ev_done[pi], s), "hipEventRecord(grandchildren count)");
-      const auto tg = Clock::now();
-      const int rcg = wait_event(W.ev_done[pi], "sizing a piece's grandchildren");
-      wait_ms += ms_since(tg);
-      ++syncs;
-      if (rcg) return rcg;
+      void* ks = nullptr;
+      uint32_t *gcnt = nullptr, *goff = nullptr;
+      if (int rc = reserve(W.kid_states, nkid * rules.state_bytes(), &ks)) return rc;
+      if (int rc = reserve(W.kid2_cnt, (nkid + 1) * 4, &gcnt)) return rc;
+      if (int rc = reserve(W.kid2_off, (nkid + 1) * 4, &goff)) return rc;
+      HIP_TRY(child_states(rules, g.states, n, coff, g.total, ks, nullptr, s), "child_states launch");
+      HIP_TRY(count_children(rules, ks, (uint32_t)nkid, gcnt, goff, s, W.bscratch), "grandchildren count launch");
+      if (int rc = read_size(goff + nkid, "sizing a piece's grandchildren")) return rc;
       const size_t gtotal = hs[1];
-      if (int rc = W.g_pos.reserve(gtotal * W.rec)) return rc;
-      if (int rc = W.g_moves.reserve(gtotal * 2)) return rc;
-      if (int rc = W.g_end.reserve(gtotal)) return rc;
-      if (int rc = W.g_ps.reserve(gtotal * 4)) return rc;
-      if (int rc = W.g_po.reserve(gtotal * 4)) return rc;
-      void* gp = W.g_pos.at<char>(0);
-      uint16_t* gm = W.g_moves.at<uint16_t>(0);
-      uint8_t* ge = W.g_end.at<uint8_t>(0);
-      int32_t* gps = W.g_ps.at<int32_t>(0);
-      int32_t* gpo = W.g_po.at<int32_t>(0);
-      HIP_TRY(chess ? children_write_device(static_cast<const DBoard*>(ks), (uint32_t)nkid, goff, (uint32_t)gtotal,
-                                            static_cast<fnnue_pos*>(gp), gm, ge, s)
-                    : vchildren_write_device(k, ks, (uint32_t)nkid, goff, (uint32_t)gtotal,
-                                             static_cast<fnnue_vpos*>(gp), gm, ge, s),
-              "grandchildren launch");
-      if (draws)
-        HIP_TRY(mark_draws_level2(hist, static_cast<const DBoard*>(states), 0, n, coff, static_cast<const DBoard*>(ks),
-                                  goff, 0, gm, ge, s),
-                "draw marks launch");
-      if (int rc = chess ? fnnue_eval_groups_device(c, static_cast<const fnnue_pos*>(gp), goff, nkid, gtotal,
-                                                    FNNUE_GROUP_STAR, gps, gpo, s)
-                         : fnnue_eval_vgroups_device(c, static_cast<const fnnue_vpos*>(gp), goff, nkid, gtotal,
-                                                     FNNUE_GROUP_STAR, gps, gpo, s))
-        return rc;
-      if (chess && quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
-        QuiesceStats qs;
-        if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(ks), (uint32_t)nkid, goff,
-                                           (uint32_t)gtotal, ge, gps, gpo, quiesce, quiesce_checks, 2, s, &qs))
-          return rc;
-        syncs += (uint32_t)qs.syncs;
-      }
-      HIP_TRY(launch_best_children_own(gps, gpo, ge, gm, goff, (uint32_t)nkid, (uint32_t)gtotal, kb, s),
-              "best_children launch");
-      if (draws)  // a drawn child's pv ends at it: its own terms into its record
-        HIP_TRY(draw_own_terms(hist, 0, n, coff, ke, goff, 0, gps, gpo, kb, s), "draw terms launch");
+      Level2Chunk ch;
+      ch.p1 = n, ch.nk = (uint32_t)nkid, ch.nr = (uint32_t)gtotal;
+      ch.ch_off = goff;
+      if (int rc = reserve(W.g_pos, gtotal * W.rec, &ch.pos)) return rc;
+      if (int rc = reserve(W.g_moves, gtotal * 2, &ch.moves)) return rc;
+      if (int rc = reserve(W.g_end, gtotal, &ch.end)) return rc;
+      if (int rc = reserve(W.g_ps, gtotal * 4, &ch.psqt)) return rc;
+      if (int rc = reserve(W.g_po, gtotal * 4, &ch.positional)) return rc;
+      if (int rc = search_level2_chunk(c, W.bscratch, rules, set, g, ks, goff, ch, kb, s, &qs, nullptr)) return rc;
       P.searched += gtotal - nkid;
     }
-    // the variant nets: the variant ranks (FNNUE_END_WON children, every reply loses at once)
-    HIP_TRY((chess ? launch_best_replies : launch_vbest_replies)(ke, km, coff, n, (uint32_t)total, kb, nullptr,
-                                                                 reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
+    HIP_TRY(best_replies(rules.vranks(), g.end, km, coff, n, g.total, kb, nullptr,
+                         reinterpret_cast<fnnue_best2*>(dimg + P.o_best), s),
             "best_replies launch");
+    if (P.nslots)
+      HIP_TRY(topk_replies(rules.vranks(), g.end, km, coff, n, g.total, kb, nullptr,
+                           reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
+                           reinterpret_cast<fnnue_line2*>(dimg + P.o_lines), P.nslots, s),
+              "topk_replies launch");
   } else {
-    if (chess && quiesce > 0) {  // the children's terms become those of their capture lines' ends
-      QuiesceStats qs;
-      if (int rc = quiesce_leaves_device(c, W.bscratch, static_cast<const DBoard*>(states), n, coff, (uint32_t)total, ke,
-                                         kps, kpo, quiesce, quiesce_checks, 1, s, &qs))
-        return rc;
-      syncs += (uint32_t)qs.syncs;
-    }
-    HIP_TRY(launch_best_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
-                                 reinterpret_cast<fnnue_best*>(dimg + P.o_best), s),
-            "best_children launch");
+    // One ply: the reduction into the results image, and the lines of a go_lines() call that asked for MultiPV
+    if (int rc = reduce_level1(c, W.bscratch, set, g, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
+                               reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
+                               P.nslots ? reinterpret_cast<fnnue_line*>(dimg + P.o_lines) : nullptr, P.nslots, s, &qs))
+      return rc;
   }
-  if (P.nslots && P.depth2)  // a go_lines_pv() call at two plies: the lines with their replies
-    HIP_TRY(launch_topk_replies(!chess, ke, km, coff, n, (uint32_t)total, W.kid_best.at<fnnue_best>(0), nullptr,
-                                reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
-                                reinterpret_cast<fnnue_line2*>(dimg + P.o_lines), P.nslots, s),
-            "topk_replies launch");
-  else if (P.nslots)  // a go_lines() call whose piece has a batch that asked for MultiPV
-    HIP_TRY(launch_topk_children(kps, kpo, ke, km, coff, n, (uint32_t)total,
-                                 reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
-                                 reinterpret_cast<fnnue_line*>(dimg + P.o_lines), P.nslots, s),
-            "topk_children launch");
-  HIP_TRY(launch_gather_parents(kps, kpo, coff, n, (uint32_t)total, reinterpret_cast<int32_t*>(dimg + P.o_ps),
+  syncs += (uint32_t)qs.syncs;
+  HIP_TRY(launch_gather_parents(g.psqt, g.positional, coff, n, g.total, reinterpret_cast<int32_t*>(dimg + P.o_ps),
                                 reinterpret_cast<int32_t*>(dimg + P.o_po), s),
           "gather_parents launch");
   return FNNUE_OK;
@@ -1205,16 +1199,8 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const uint32_t nps = el > 0 ? (uint32_t)std::min(4.0e9, (double)filled / (el * 1e-3)) : 0;
   const int32_t nrm = norm;
   const ResponseTail tail(ms, nps);
-  // quiescence checks: a FNNUE_BEST_CP value beyond the static domain is a coded mate -> its Score::Mate moves
-  // (0: not one).  Chess searches with quiescence only; otherwise no value is ever remapped.
-  const bool coded_on = k == kVariantChess && quiesce_checks && quiesce > 0;
-  auto coded = [coded_on](uint8_t kind, int32_t v) -> int64_t {
-    if (!coded_on || kind != FNNUE_BEST_CP) return 0;
-    const int32_t a = v < 0 ? -v : v;
-    if (a <= FNNUE_VALUE_MATE - 64) return 0;
-    const int32_t plies = FNNUE_VALUE_MATE - a;
-    return v > 0 ? (plies + 1) / 2 : -(plies / 2);
-  };
+  // coded mates: chess searches with quiescence checks only; otherwise no value is ever remapped
+  const ScoreRule rule{nrm, k == kVariantChess && quiesce_checks && quiesce > 0};
   pool.run(P.ng, fill_grain, [&](size_t lo, size_t hi) {
     for (size_t g = lo; g < hi; ++g) {
       const size_t i = P.games[g];
@@ -1227,172 +1213,97 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
       // be played from it): mate 0 / cp 0 instead of an evaluation.
       const bool ends = fin[g] & kFinalNoMoves;
       const uint8_t end_kind = (fin[g] & kFinalDecided) ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-      if (best2) {
-        // Two plies: every ply from its fnnue_best2; a ply without a child as at depth 0.
-        const fnnue_best2* gb = best2 + ply[g];
-        const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
-        const uint32_t kk = dlines2 ? line_slots(j.batches[i]) : 0;
-        for (uint32_t q = 0; q < len; ++q) {
-          const fnnue_best2& B = gb[q];
-          const bool skipped = sk && skip[b + q];
-          const bool none = B.kind == FNNUE_BEST_NONE;
-          // mated: every move allows a mate in one, or (variants) loses at once
-          const bool mate = B.kind == FNNUE_BEST_MATE, mated = B.kind == FNNUE_BEST_MATED || B.kind == FNNUE_BEST_LOST;
-          const int64_t cm = coded(B.kind, B.value);
-          const uint8_t kind = none ? end_kind : mate || mated || cm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-          const int64_t score = none ? 0 : mate ? 1 : mated ? -1 : cm ? cm : (int64_t)B.value * 100 / nrm;
-          const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
-          const uint8_t depth = none ? 0 : B.pv_len;
-          if (j.cout) {
-            if (skipped)
-              put_compact(j.cout + b + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
-            else
-              put_compact(j.cout + b + q, rps, rpo, (int32_t)score, kind, depth, none ? fl | FNNUE_COMPACT_NO_MOVES : fl);
-            continue;
-          }
-          fnnue_position_response* r = j.out + b + q;
-          if (skipped) {
-            put_response(r, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
-            continue;
-          }
-          put_response(r, response_head(q, 0, kind, depth, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
-          if (!none) (void)(k == kVariantChess ? fnnue_move_uci(B.move, r->best_move) : fnnue_vmove_uci(B.move, r->best_move));
-          if (j.reply && !none) j.reply[b + q] = B.reply;
-          if (none || !kk) continue;
-          // MultiPV at two plies: the ply's lines until the first unused slot
-          // (the slots beyond its legal moves are all-zero), at the batch's
-          // provisional place (close_lines() packs them afterwards)
-          const fnnue_line2* src = dlines2 + loff[ply[g] + q];
-          fnnue_pv_line2* dst = j.lines2 + lbase[i] + (size_t)q * kk;
-          uint32_t nl = 0;
-          for (; nl < kk && src[nl].kind != FNNUE_BEST_NONE; ++nl) {
-            const fnnue_line2& L = src[nl];
-            const bool lm = L.kind == FNNUE_BEST_MATE, ld = L.kind == FNNUE_BEST_MATED || L.kind == FNNUE_BEST_LOST;
-            char mv[8], rp[8] = {0};
-            (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
-            if (L.pv_len == 2) (void)(k == kVariantChess ? fnnue_move_uci(L.reply, rp) : fnnue_vmove_uci(L.reply, rp));
-            fnnue_pv_line2 out{};
-            const int64_t lc = coded(L.kind, L.value);
-            out.score = lm ? 1 : ld ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
-            out.psqt = L.psqt;
-            out.positional = L.positional;
-            std::snprintf(out.pv, sizeof(out.pv), "%s%s%s", mv, rp[0] ? " " : "", rp);
-            out.score_kind = lm || ld || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-            out.pv_len = rp[0] ? 2 : 1;
-            dst[nl] = out;
-          }
-          j.line_off[b + q + 1] = nl;  // a count for now
-        }
-        if (j.cout) {
-          fnnue_batch_compact& B = j.bout[i];
-          B.time_ms = ms;
-          B.nps = nps;
-          B.nodes = 0;
-          std::memset(B.best_move, 0, sizeof(B.best_move));
-        }
-        continue;
-      }
-      if (best) {
-        // Depth 1: every ply from its fnnue_best.  A ply without a child is the
-        // game's last one without a legal move, answered as at depth 0.
-        const fnnue_best* gb = best + ply[g];
-        const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
-        const uint32_t kk = dlines ? line_slots(j.batches[i]) : 0;
-        for (uint32_t q = 0; q < len; ++q) {
-          const fnnue_best& B = gb[q];
-          const bool skipped = sk && skip[b + q];
-          const bool none = B.kind == FNNUE_BEST_NONE;
-          // a mate in one, or (variants) every move loses at once: Mate(1) / Mate(-1), as move work
-          const bool mate = B.kind == FNNUE_BEST_MATE, lost = B.kind == FNNUE_BEST_LOST;
-          const int64_t cm = coded(B.kind, B.value);
-          const uint8_t kind = none ? end_kind : mate || lost || cm ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-          const int64_t score = none ? 0 : mate ? 1 : lost ? -1 : cm ? cm : (int64_t)B.value * 100 / nrm;
-          const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
-          if (j.cout) {
-            if (skipped)
-              put_compact(j.cout + b + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
-            else
-              put_compact(j.cout + b + q, rps, rpo, (int32_t)score, kind, none ? 0 : 1,
-                          none ? fl | FNNUE_COMPACT_NO_MOVES : fl);
-            continue;
-          }
-          fnnue_position_response* r = j.out + b + q;
-          if (skipped) {
-            put_response(r, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
-            continue;
-          }
-          put_response(r, response_head(q, 0, kind, none ? 0 : 1, matrix), score, rps, rpo, none ? 0 : B.nodes, tail);
-          if (!none) (void)(k == kVariantChess ? fnnue_move_uci(B.move, r->best_move) : fnnue_vmove_uci(B.move, r->best_move));
-          if (none || !kk) continue;
-          // MultiPV: the first min(slots, nodes) lines of the ply, at the
-          // batch's provisional place (close_lines() packs them afterwards)
-          const uint32_t nl = std::min(kk, B.nodes);
-          const fnnue_line* src = dlines + loff[ply[g] + q];
-          const size_t at = lbase[i] + (size_t)q * kk;
-          fnnue_pv_line* dst = j.lines ? j.lines + at : nullptr;
-          for (uint32_t l = 0; l < nl; ++l) {
-            const fnnue_line& L = src[l];
-            const bool lm = L.kind == FNNUE_BEST_MATE, ll = L.kind == FNNUE_BEST_LOST;
-            const int64_t lc = coded(L.kind, L.value);
-            char mv[8];
-            (void)(k == kVariantChess ? fnnue_move_uci(L.move, mv) : fnnue_vmove_uci(L.move, mv));
-            if (!dst) {  // go_lines_pv at one ply: the same line in the two-ply record
-              fnnue_pv_line2 out2{};
-              out2.score = lm ? 1 : ll ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
-              out2.psqt = L.psqt;
-              out2.positional = L.positional;
-              std::memcpy(out2.pv, mv, 6);
-              out2.score_kind = lm || ll || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-              out2.pv_len = 1;
-              j.lines2[at + l] = out2;
-              continue;
-            }
-            fnnue_pv_line out{};
-            out.score = lm ? 1 : ll ? -1 : lc ? lc : (int64_t)L.value * 100 / nrm;
-            out.psqt = L.psqt;
-            out.positional = L.positional;
-            std::memcpy(out.move, mv, 6);  // at most "e7e8q" and its NUL
-            out.score_kind = lm || ll || lc ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-            dst[l] = out;
-          }
-          j.line_off[b + q + 1] = nl;  // a count for now
-        }
-        if (j.cout) {
-          fnnue_batch_compact& B = j.bout[i];
-          B.time_ms = ms;
-          B.nps = nps;
-          B.nodes = 0;
-          std::memset(B.best_move, 0, sizeof(B.best_move));
-        }
-        continue;
-      }
-      if (j.cout) {
-        fnnue_position_compact* r = j.cout + b;
-        const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
-        for (uint32_t q = 0; q < len; ++q) {
-          if (sk && skip[b + q])
-            put_compact(r + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
-          else if (q + 1 == len && ends)
-            put_compact(r + q, gps[q], gpo[q], 0, end_kind, 0, fl | FNNUE_COMPACT_NO_MOVES);
-          else
-            put_compact(r + q, gps[q], gpo[q], (int32_t)to_cp(gps[q], gpo[q], nrm), FNNUE_SCORE_CP, 0, fl);
-        }
+      if (j.cout) {  // the compact form's batch record, whatever the plies' answers come from
         fnnue_batch_compact& B = j.bout[i];
         B.time_ms = ms;
         B.nps = nps;
         B.nodes = 0;
         std::memset(B.best_move, 0, sizeof(B.best_move));
+      }
+      // Ply q's answer from its record B, full or compact: a fnnue_best2 (two plies), a fnnue_best, or at
+      // depth 0 the ply's own value as one.  A ply without a child is the game's last one without a legal move:
+      // mate 0 / cp 0 with its own terms.  true: a full record was written for a ply with a move.
+      const uint8_t fl = matrix ? FNNUE_COMPACT_MATRIX : 0;
+      auto answer = [&](uint32_t q, const auto& B, uint8_t pv_len, const ScoreRule& rule) {
+        const bool none = B.kind == FNNUE_BEST_NONE;
+        const Answer a = none ? Answer{end_kind, 0} : rule(B.kind, B.value);
+        const int32_t rps = none ? gps[q] : B.psqt, rpo = none ? gpo[q] : B.positional;
+        const uint8_t depth = none ? 0 : pv_len;
+        const bool skipped = sk && skip[b + q];
+        if (j.cout) {
+          if (skipped)
+            put_compact(j.cout + b + q, 0, 0, 0, 0, 0, FNNUE_COMPACT_SKIPPED);
+          else
+            put_compact(j.cout + b + q, rps, rpo, (int32_t)a.score, a.kind, depth, none ? fl | FNNUE_COMPACT_NO_MOVES : fl);
+          return false;
+        }
+        fnnue_position_response* r = j.out + b + q;
+        if (skipped) {
+          put_response(r, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
+          return false;
+        }
+        put_response(r, response_head(q, 0, a.kind, depth, matrix), a.score, rps, rpo, none ? 0 : B.nodes, tail);
+        if (!none && B.move) move_uci(k, B.move, r->best_move);
+        return !none;
+      };
+      if (best2 || best) {
+        const uint32_t kk = dlines2 || dlines ? line_slots(j.batches[i]) : 0;
+        // the lines go to the batch's provisional place, lbase[i] + q * kk (close_lines() packs them afterwards)
+        for (uint32_t q = 0; q < len; ++q) {
+          uint32_t nl = 0;
+          if (best2) {
+            const fnnue_best2& B = best2[ply[g] + q];
+            if (!answer(q, B, B.pv_len, rule)) continue;
+            if (j.reply) j.reply[b + q] = B.reply;
+            if (!kk) continue;
+            // MultiPV at two plies: the ply's lines until the first unused slot
+            // (the slots beyond its legal moves are all-zero)
+            const fnnue_line2* src = dlines2 + loff[ply[g] + q];
+            const size_t at = lbase[i] + (size_t)q * kk;
+            for (; nl < kk && src[nl].kind != FNNUE_BEST_NONE; ++nl) {
+              const fnnue_line2& L = src[nl];
+              char rp[8] = {0};
+              if (L.pv_len == 2) move_uci(k, L.reply, rp);
+              j.lines2[at + nl] = pv_line2(k, rule, L, rp);
+            }
+          } else {
+            const fnnue_best& B = best[ply[g] + q];
+            if (!answer(q, B, 1, rule) || !kk) continue;
+            // MultiPV: the first min(slots, nodes) lines of the ply
+            const fnnue_line* src = dlines + loff[ply[g] + q];
+            const size_t at = lbase[i] + (size_t)q * kk;
+            nl = std::min(kk, B.nodes);
+            for (uint32_t l = 0; l < nl; ++l) {
+              const fnnue_line& L = src[l];
+              if (!j.lines) {  // go_lines_pv at one ply: the same line in the two-ply record
+                j.lines2[at + l] = pv_line2(k, rule, L, "");
+                continue;
+              }
+              const Answer a = rule(L.kind, L.value);
+              char mv[8] = {0};
+              move_uci(k, L.move, mv);
+              fnnue_pv_line out{};
+              out.score = a.score;
+              out.psqt = L.psqt;
+              out.positional = L.positional;
+              std::memcpy(out.move, mv, 6);  // at most "e7e8q" and its NUL
+              out.score_kind = a.kind;
+              j.lines[at + l] = out;
+            }
+          }
+          j.line_off[b + q + 1] = nl;  // a count for now
+        }
         continue;
       }
-      fnnue_position_response* r = j.out + b;
+      // Depth 0: every ply's own value in centipawns (never a coded mate), but the last without a legal move
       for (uint32_t q = 0; q < len; ++q) {
-        if (sk && skip[b + q])
-          put_response(r + q, response_head(q, 1, 0, 0, 0), 0, 0, 0, 0, tail);
-        else if (q + 1 == len && ends)
-          put_response(r + q, response_head(q, 0, end_kind, 0, matrix), 0, gps[q], gpo[q], 0, tail);
-        else
-          put_response(r + q, response_head(q, 0, FNNUE_SCORE_CP, 0, matrix), to_cp(gps[q], gpo[q], nrm), gps[q],
-                       gpo[q], 1, tail);
+        fnnue_best B{};
+        B.kind = q + 1 == len && ends ? FNNUE_BEST_NONE : FNNUE_BEST_CP;
+        B.value = (int32_t)(((int64_t)gps[q] + gpo[q]) / 16);  // OutputScale, C truncation
+        B.psqt = gps[q];
+        B.positional = gpo[q];
+        B.nodes = 1;
+        answer(q, B, 0, ScoreRule{nrm, false});
       }
     }
   });
@@ -1437,10 +1348,11 @@ void fnnue_backend::fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint3
       }
     }
     const size_t x = W.kid_first[t] + best;
-    const uint8_t kind = best_rank != 1 ? FNNUE_SCORE_MATE : FNNUE_SCORE_CP;
-    const int64_t score = best_rank == 2 ? 1 : best_rank == 0 ? -1 : bv * 100 / norm;
+    // the ranks as the searches' records name them: no coded mates at this depth
+    const Answer a = ScoreRule{norm, false}(
+        best_rank == 2 ? FNNUE_BEST_MATE : best_rank == 0 ? FNNUE_BEST_LOST : FNNUE_BEST_CP, bv);
     if (j.cout) {
-      put_compact(j.cout + j.off[i], -kps[x], -kpo[x], (int32_t)score, kind, 1, 0);
+      put_compact(j.cout + j.off[i], -kps[x], -kpo[x], (int32_t)a.score, a.kind, 1, 0);
       fnnue_batch_compact& B = j.bout[i];
       B.time_ms = ms;
       B.nps = nps;
@@ -1457,8 +1369,8 @@ void fnnue_backend::fill_roots(Job& j, int k, const Piece& P, uint64_t ms, uint3
     r.positional = -kpo[x];
     r.depth = 1;
     r.nodes = R.uci.size();
-    r.score_kind = kind;
-    r.score = score;
+    r.score_kind = a.kind;
+    r.score = a.score;
     std::strncpy(r.best_move, R.uci[best].c_str(), sizeof(r.best_move) - 1);
   }
 }

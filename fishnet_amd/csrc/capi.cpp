@@ -1,12 +1,11 @@
 // capi.cpp — the C ABI (include/fnnue.h).  Host runtime: net ownership, device
 // contexts (one per GPU, weights resident in HBM), chunked launches, error
-// mapping to fishnet's PositionFailed semantics, batch building.
+// mapping to fishnet's PositionFailed semantics, the host game functions.  The
+// device builder and the searches: search_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -271,6 +270,17 @@ int finish_upload(fnnue_ctx* c) {
   return FNNUE_OK;
 }
 
+int order_workspace(fnnue_ctx* c, hipStream_t s) {
+  if (c->ws_own_pending) {
+    if (s == c->stream) return FNNUE_OK;
+    HIP_TRY(hipEventRecord(c->ws_event, c->stream), "hipEventRecord");
+    c->ws_recorded = true;
+    c->ws_own_pending = false;
+  }
+  if (c->ws_recorded) HIP_TRY(hipStreamWaitEvent(s, c->ws_event, 0), "hipStreamWaitEvent");
+  return FNNUE_OK;
+}
+
 }  // namespace fnnue::detail
 
 namespace {
@@ -336,47 +346,6 @@ int run_chunk_tail(fnnue_ctx* c, uint32_t n, int32_t* d_positional, hipStream_t 
   HIP_TRY(launch_stack(c->hd, c->x, c->bucket, n, c->ptrs, d_positional, perm, psqt_part, d_psqt, s),
           "stack kernel launch");
   return record_event(c, ev, 3, s);
-}
-
-// Workspace ordering across streams (the workspace is shared by every call on
-// a ctx): a call on a caller's stream records ws_event on it when its work is
-// enqueued (also after an error: part of it may be), and each call first
-// waits for that event.  No caller stream handle of an earlier call is ever
-// used again, so a caller may destroy a stream right after a call on it.  A
-// call on the context's own stream records nothing (an event record between
-// two kernels idles the stream for microseconds): the next call on the same
-// stream is ordered by the stream, and a call on another stream records
-// ws_event on the own stream, which lives as long as the context, first.
-struct WorkspaceUse {
-  fnnue_ctx* c;
-  hipStream_t s;
-  ~WorkspaceUse() {
-    if (s == c->stream) {
-      c->ws_own_pending = true;
-    } else if (hipEventRecord(c->ws_event, s) == hipSuccess) {
-      c->ws_recorded = true;
-      c->ws_own_pending = false;
-    } else {
-      // No event for this call's work: the stale one (an earlier call's) would
-      // let the next call on another stream overwrite the workspace while this
-      // one still reads it.  Wait for the work instead (a destructor cannot
-      // return the error; the ordering is what must hold).
-      (void)hipStreamSynchronize(s);
-      c->ws_recorded = false;
-      c->ws_own_pending = false;
-    }
-  }
-};
-
-int order_workspace(fnnue_ctx* c, hipStream_t s) {
-  if (c->ws_own_pending) {
-    if (s == c->stream) return FNNUE_OK;
-    HIP_TRY(hipEventRecord(c->ws_event, c->stream), "hipEventRecord");
-    c->ws_recorded = true;
-    c->ws_own_pending = false;
-  }
-  if (c->ws_recorded) HIP_TRY(hipStreamWaitEvent(s, c->ws_event, 0), "hipStreamWaitEvent");
-  return FNNUE_OK;
 }
 
 hipEvent_t mid_event(std::array<hipEvent_t, 4>* ev) { return ev ? (*ev)[1] : nullptr; }
@@ -1353,102 +1322,7 @@ int fnnue_selftest_mfma(int device) {
 
 }  // extern "C"
 
-namespace {
-
-// fnnue_build_batch_device, and with moves / end fnnue_build_children_device.
-int build_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                 size_t ngames, int mode, fnnue_pos* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
-                 uint16_t* d_moves, uint8_t* d_end, size_t* n_out, size_t* n_groups, void* stream,
-                 ChildrenBufs* own = nullptr) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  if (mode != FNNUE_PLAYOUT_PLIES && mode != FNNUE_PLAYOUT_CHILDREN) return fail(FNNUE_E_ARG, "bad build mode");
-  *n_out = *n_groups = 0;
-  if (ngames == 0) return FNNUE_OK;
-  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  const BuildResult R = build_batch_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames,
-                                           mode == FNNUE_PLAYOUT_CHILDREN, d_out, cap, d_off, off_cap, s,
-                                           ctx->bscratch, nullptr, d_moves, d_end, own);
-  if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
-  *n_out = R.n_out;
-  *n_groups = R.n_groups;
-  if (R.err_code == kBuildErrFen)
-    return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(R.err_game));
-  if (R.err_code == kBuildErrMove)
-    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
-                                  std::to_string(R.err_game));
-  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  return FNNUE_OK;
-}
-
-// Stages a host game text (and its offsets) in the context's builder input.
-int stage_games(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
-                size_t ngames, char** d_text, uint32_t** d_fo, uint32_t** d_mo) {
-  if (fen_off[ngames] > text_len) return fail(FNNUE_E_ARG, "offsets exceed the text");
-  for (size_t i = 0; i < ngames; ++i)
-    if (fen_off[i] > moves_off[i] || moves_off[i] > fen_off[i + 1]) return fail(FNNUE_E_ARG, "offsets out of order");
-  const size_t text_bytes = (text_len + 255) / 256 * 256;
-  const size_t fo_bytes = (ngames + 1) * 4, mo_bytes = ngames * 4;
-  if (int rc = ensure_builder_input(ctx, text_bytes + fo_bytes + mo_bytes)) return rc;
-  *d_text = ctx->d_btext;
-  *d_fo = reinterpret_cast<uint32_t*>(ctx->d_btext + text_bytes);
-  *d_mo = *d_fo + (ngames + 1);
-  hipStream_t s = ctx->stream;
-  HIP_TRY(hipMemcpyAsync(*d_text, text, text_len, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(*d_fo, fen_off, fo_bytes, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(*d_mo, moves_off, mo_bytes, hipMemcpyHostToDevice, s), "H2D");
-  return FNNUE_OK;
-}
-
-// fnnue_build_vchildren_device, and with `own` the variant search's children
-// in the context's scratch.
-int build_vdevice(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                  const uint32_t* d_moves_off, size_t ngames, fnnue_vpos* d_out, size_t cap, uint32_t* d_off,
-                  size_t off_cap, uint16_t* d_moves, uint8_t* d_end, size_t* n_out, size_t* n_groups, void* stream,
-                  VChildrenBufs* own = nullptr) {
-  *n_out = *n_groups = 0;
-  if (!variant_known(variant) || variant == kVariantChess)
-    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
-  if (ngames == 0) return FNNUE_OK;
-  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  const BuildResult R = build_vbatch_device(variant, d_text, d_fen_off, d_moves_off, (uint32_t)ngames, true,
-                                            d_out, cap, d_off, off_cap, s, ctx->bscratch, nullptr, d_moves, d_end,
-                                            own);
-  if (R.hip != hipSuccess) return hip_fail(R.hip, "device variant batch builder");
-  *n_out = R.n_out;
-  *n_groups = R.n_groups;
-  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable variant FEN in game " + std::to_string(R.err_game));
-  if (R.err_code == kBuildErrMove)
-    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
-                                  std::to_string(R.err_game));
-  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  return FNNUE_OK;
-}
-
-// A device buffer for the length of one host-buffer call.
-struct TempDev {
-  void* p = nullptr;
-  ~TempDev() {
-    if (p) (void)hipFree(p);
-  }
-  int get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? FNNUE_OK : fail(FNNUE_E_OOM, "device allocation"); }
-};
-
-}  // namespace
-
 extern "C" {
-
-int fnnue_build_batch_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                             const uint32_t* d_moves_off, size_t ngames, int mode, fnnue_pos* d_out, size_t cap,
-                             uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  return build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, mode, d_out, cap, d_off, off_cap, nullptr, nullptr,
-                      n_out, n_groups, stream);
-}
 
 int fnnue_move_uci(fnnue_move m, char out[8]) {
   if (!out) return fail(FNNUE_E_ARG, "null argument");
@@ -1463,949 +1337,6 @@ int fnnue_move_uci(fnnue_move m, char out[8]) {
   out[4] = promo ? " pnbrq"[promo] : 0;
   out[5] = 0;
   return FNNUE_OK;
-}
-
-int fnnue_build_children_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                                const uint32_t* d_moves_off, size_t ngames, fnnue_pos* d_out, size_t cap,
-                                uint32_t* d_off, size_t off_cap, fnnue_move* d_moves, uint8_t* d_end, size_t* n_out,
-                                size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  if (d_out && (!d_moves || !d_end)) return fail(FNNUE_E_ARG, "null moves / end buffer");
-  return build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, d_out, cap, d_off, off_cap,
-                      d_moves, d_end, n_out, n_groups, stream);
-}
-
-int fnnue_build_children(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                         const uint32_t* moves_off, size_t ngames, fnnue_pos* out, size_t cap, uint32_t* off,
-                         size_t off_cap, fnnue_move* moves, uint8_t* end, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  rc = fnnue_build_children_device(ctx, d_text, d_fo, d_mo, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr, n_out,
-                                   n_groups, s);
-  if (rc != FNNUE_E_CAPACITY) return rc;  // sizing pass: always "too small" with no outputs
-  if (!out || !off || !moves || !end || cap < *n_out || off_cap < *n_groups + 1)
-    return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  if ((rc = ensure_stage(ctx, *n_out, *n_groups + 1))) return rc;
-  TempDev extra;  // moves (2 B) then end (1 B) per record
-  const size_t nrec = *n_out;
-  if ((rc = extra.get(nrec * 3))) return rc;
-  fnnue_move* d_moves = static_cast<fnnue_move*>(extra.p);
-  uint8_t* d_end = static_cast<uint8_t*>(extra.p) + nrec * 2;
-  rc = fnnue_build_children_device(ctx, d_text, d_fo, d_mo, ngames, ctx->d_pos, nrec, ctx->d_off, *n_groups + 1,
-                                   d_moves, d_end, n_out, n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, ctx->d_pos, *n_out * sizeof(fnnue_pos), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, ctx->d_off, (*n_groups + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(moves, d_moves, *n_out * 2, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(end, d_end, *n_out, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-int fnnue_best_children_device(fnnue_ctx* ctx, const int32_t* d_psqt, const int32_t* d_positional,
-                               const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off, size_t ngroups,
-                               size_t npos, fnnue_best* d_out, void* stream) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!d_psqt || !d_positional || !d_end || !d_off || !d_out) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  HIP_TRY(launch_best_children(d_psqt, d_positional, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_out,
-                               s),
-          "best_children launch");
-  return FNNUE_OK;
-}
-
-int fnnue_best_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* positional, const uint8_t* end,
-                        const fnnue_move* moves, const uint32_t* off, size_t ngroups, size_t npos, fnnue_best* out) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!off || !out || (npos && (!psqt || !positional || !end))) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  DeviceGuard g(ctx->device);
-  // [psqt | positional | off | out | moves | end]: 4-byte parts first
-  const size_t n4 = npos * 4, o_off = 2 * n4, o_out = o_off + (ngroups + 1) * 4;
-  const size_t o_mv = o_out + ngroups * sizeof(fnnue_best), o_end = o_mv + npos * 2;
-  TempDev buf;
-  if (int rc = buf.get(o_end + npos)) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  if (npos) {
-    HIP_TRY(hipMemcpyAsync(d, psqt, n4, hipMemcpyHostToDevice, s), "H2D");
-    HIP_TRY(hipMemcpyAsync(d + n4, positional, n4, hipMemcpyHostToDevice, s), "H2D");
-    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
-    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  const int rc = fnnue_best_children_device(
-      ctx, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + n4), reinterpret_cast<uint8_t*>(d + o_end),
-      moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr, reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
-      reinterpret_cast<fnnue_best*>(d + o_out), s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, ngroups * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-int fnnue_topk_children_device(fnnue_ctx* ctx, const int32_t* d_psqt, const int32_t* d_positional,
-                               const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off, size_t ngroups,
-                               size_t npos, const uint32_t* d_line_off, fnnue_line* d_lines, size_t lines_cap,
-                               void* stream) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!d_psqt || !d_positional || !d_end || !d_off || !d_line_off || (lines_cap && !d_lines))
-    return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  if (lines_cap == 0) return FNNUE_OK;  // no slot may be written
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  HIP_TRY(launch_topk_children(d_psqt, d_positional, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos,
-                               d_line_off, 0, d_lines, lines_cap, s),
-          "topk_children launch");
-  return FNNUE_OK;
-}
-
-int fnnue_topk_children(fnnue_ctx* ctx, const int32_t* psqt, const int32_t* positional, const uint8_t* end,
-                        const fnnue_move* moves, const uint32_t* off, size_t ngroups, size_t npos,
-                        const uint32_t* line_off, fnnue_line* lines, size_t lines_cap) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!off || !line_off || (npos && (!psqt || !positional || !end))) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  for (size_t g = 0; g < ngroups; ++g)
-    if (line_off[g] > line_off[g + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
-  const size_t nl = line_off[ngroups];
-  if (nl > lines_cap) return fail(FNNUE_E_CAPACITY, "line buffer too small");
-  if (nl && !lines) return fail(FNNUE_E_ARG, "null buffer");
-  if (nl == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  // [psqt | positional | off | line_off | lines | moves | end]: 4-byte parts first
-  const size_t n4 = npos * 4, o_off = 2 * n4, o_loff = o_off + (ngroups + 1) * 4, o_lines = o_loff + (ngroups + 1) * 4;
-  const size_t o_mv = o_lines + nl * sizeof(fnnue_line), o_end = o_mv + npos * 2;
-  TempDev buf;
-  if (int rc = buf.get(o_end + npos)) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  if (npos) {
-    HIP_TRY(hipMemcpyAsync(d, psqt, n4, hipMemcpyHostToDevice, s), "H2D");
-    HIP_TRY(hipMemcpyAsync(d + n4, positional, n4, hipMemcpyHostToDevice, s), "H2D");
-    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
-    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(d + o_loff, line_off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  // the caller's lines go up first, so that slots no group writes (empty groups) come back as they were
-  HIP_TRY(hipMemcpyAsync(d + o_lines, lines, nl * sizeof(fnnue_line), hipMemcpyHostToDevice, s), "H2D");
-  const int rc = fnnue_topk_children_device(
-      ctx, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + n4), reinterpret_cast<uint8_t*>(d + o_end),
-      moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr, reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
-      reinterpret_cast<uint32_t*>(d + o_loff), reinterpret_cast<fnnue_line*>(d + o_lines), nl, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(lines, d + o_lines, nl * sizeof(fnnue_line), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The net a one-ply search of `variant` needs: fnnue_search1* a chess net,
-// fnnue_vsearch1* one whose feature set and game-over records are the
-// variant's (its own net; the atomic net also for kingofthehill, racingkings, threecheck).
-int search1_arch(const fnnue_ctx* ctx, int variant) {
-  if (variant == kVariantChess)
-    return ctx->variant == kVariantChess ? (int)FNNUE_OK : fail(FNNUE_E_ARCH, "the one-ply search needs a chess net");
-  if (!variant_known(variant)) return fail(FNNUE_E_ARCH, "unknown variant " + std::to_string(variant));
-  if (ctx->variant == variant || (ctx->variant == kVariantAtomic && variant_board_only(variant))) return FNNUE_OK;
-  return fail(FNNUE_E_ARCH, std::string("the context's net (") + variant_name(ctx->variant) + ") does not evaluate " +
-                                variant_name(variant));
-}
-
-// fnnue_search1_device, and with k >= 1 fnnue_search1_lines_device: ply p's k
-// best children at d_lines[p * k ..] from the same scratch, behind the reduction.
-int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                   const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
-                   uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
-                   size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (int rc = search1_arch(ctx, variant)) return rc;
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  // the children and their terms live in the context's scratch: ordered like its workspace
-  int rc = order_workspace(ctx, s);
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  ChildrenBufs kids;
-  VChildrenBufs vkids;
-  kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  if (k) kids.max_groups = d_lines ? std::min(kids.max_groups, lines_cap / k) : 0;
-  vkids.max_groups = kids.max_groups;
-  size_t nrec = 0, nply = 0;
-  if (variant == kVariantChess)
-    rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
-                      nullptr, nullptr, &nrec, &nply, s, &kids);
-  else
-    rc = build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
-                       &nrec, &nply, s, &vkids);
-  *n_out = nply;
-  *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
-  if (rc) return rc;
-  int32_t *ps = nullptr, *po = nullptr;
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPsqt, nrec * 4, (void**)&ps), "device allocation (search scratch)");
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidPositional, nrec * 4, (void**)&po),
-          "device allocation (search scratch)");
-  if (variant == kVariantChess) {
-    rc = fnnue_eval_groups_device(ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s);
-  } else {
-    rc = fnnue_eval_vgroups_device(ctx, vkids.pos, vkids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s);
-    kids.off = vkids.off;
-    kids.moves = vkids.moves;
-    kids.end = vkids.end;
-    kids.ply_off = vkids.ply_off;
-  }
-  if (rc) return rc;
-  if (variant == kVariantChess && ctx->search_draws) {
-    // the draw rules: the plies' history from the boards the replay left, then the marks on the listed plies' children
-    DrawHistory hist;
-    const DBoard* plies = static_cast<const DBoard*>(ctx->bscratch.p[BuilderScratch::kStates]);
-    HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, plies, (uint32_t)nply,
-                                draw_key_bits(), s, ctx->bscratch, &hist),
-            "game history launch");
-    HIP_TRY(mark_draws_level1(hist, plies, (uint32_t)nply, kids.off, kids.moves, kids.end, s), "draw marks launch");
-  }
-  if (variant == kVariantChess && ctx->search_quiesce > 0) {
-    // capture quiescence: the children's terms become those of their capture lines' ends, before any reduction
-    if (nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-    const DBoard* plies = static_cast<const DBoard*>(ctx->bscratch.p[BuilderScratch::kStates]);
-    if ((rc = quiesce_leaves_device(ctx, ctx->bscratch, plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kids.end, ps,
-                                    po, ctx->search_quiesce, ctx->search_quiesce_checks, 1, s, nullptr)))
-      return rc;
-  }
-  HIP_TRY(launch_best_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, d_out, s),
-          "best_children launch");
-  if (k)
-    HIP_TRY(launch_topk_children(ps, po, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, nullptr, k,
-                                 d_lines, lines_cap, s),
-            "topk_children launch");
-  HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
-  return FNNUE_OK;
-}
-
-// The host-buffer forms: staged through the ctx's stream.
-int search1_host(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                 const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap, uint32_t* off,
-                 size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (int rc = search1_arch(ctx, variant)) return rc;
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1 && (!k || lines);
-  // [best | lines | off]: the lines' room is cut to whole plies the records have room for
-  const size_t nl = k ? std::min(lines_cap / k, cap) * k : 0;
-  TempDev buf;
-  const size_t o_lines = cap * sizeof(fnnue_best), o_off = o_lines + nl * sizeof(fnnue_line);
-  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  rc = search1_device(ctx, variant, d_text, d_fo, d_mo, ngames, k, room ? reinterpret_cast<fnnue_best*>(d) : nullptr,
-                      room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
-                      room && k ? reinterpret_cast<fnnue_line*>(d + o_lines) : nullptr, room ? nl : 0, n_out,
-                      n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
-  if (k) HIP_TRY(hipMemcpyAsync(lines, d + o_lines, *n_out * k * sizeof(fnnue_line), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return latched(ctx);
-}
-
-}  // namespace
-
-extern "C" {
-
-int fnnue_search1_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                         size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
-                         size_t* n_groups, void* stream) {
-  return search1_device(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr, 0, n_out,
-                        n_groups, stream);
-}
-
-int fnnue_search1_lines_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                               const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
-                               uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
-                               size_t* n_groups, void* stream) {
-  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_device(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines, lines_cap,
-                        n_out, n_groups, stream);
-}
-
-int fnnue_search1_lines(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                        const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap,
-                        uint32_t* off, size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out,
-                        size_t* n_groups) {
-  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_host(ctx, kVariantChess, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines, lines_cap,
-                      n_out, n_groups);
-}
-
-int fnnue_search1(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                  const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off, size_t off_cap,
-                  size_t* n_out, size_t* n_groups) {
-  return search1_host(ctx, kVariantChess, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0, n_out,
-                      n_groups);
-}
-
-}  // extern "C"
-
-namespace {
-
-// fnnue_best_replies[_device] (vranks = false) and fnnue_vbest_replies[_device].
-int best_replies_device(fnnue_ctx* ctx, bool vranks, const uint8_t* d_end, const fnnue_move* d_moves,
-                        const uint32_t* d_off, size_t ngroups, size_t npos, const fnnue_best* d_child_best,
-                        fnnue_best2* d_out, void* stream) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!d_end || !d_off || !d_child_best || !d_out) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  // the groups' first entries in d_child_best (a caller's groups may be empty) live in the context's scratch
-  int rc = order_workspace(ctx, s);
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  uint32_t *cnt = nullptr, *base = nullptr;
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidCnt, (ngroups + 1) * 4, (void**)&cnt), "device allocation (scratch)");
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidOff, (ngroups + 1) * 4, (void**)&base), "device allocation (scratch)");
-  HIP_TRY(launch_child_counts(d_off, (uint32_t)ngroups, (uint32_t)npos, cnt, s), "child_counts launch");
-  HIP_TRY(builder_exclusive_scan(cnt, base, (uint32_t)ngroups, s, ctx->bscratch), "scan");
-  HIP_TRY((vranks ? launch_vbest_replies : launch_best_replies)(d_end, d_moves, d_off, (uint32_t)ngroups,
-                                                                (uint32_t)npos, d_child_best, base, d_out, s),
-          "best_replies launch");
-  return FNNUE_OK;
-}
-
-int best_replies_host(fnnue_ctx* ctx, bool vranks, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                      size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!off || !out || (npos && !end)) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  size_t nchild = 0;  // as the kernel clamps the offsets
-  for (size_t i = 0; i < ngroups; ++i) {
-    const size_t e = std::min<size_t>(off[i + 1], npos), o = std::min<size_t>(off[i], e);
-    if (e > o) nchild += e - o - 1;
-  }
-  if (nchild && !child_best) return fail(FNNUE_E_ARG, "null buffer");
-  DeviceGuard g(ctx->device);
-  // [child_best | off | out | moves | end]: 4-byte parts first
-  const size_t o_off = (nchild + 1) * sizeof(fnnue_best), o_out = o_off + (ngroups + 1) * 4;
-  const size_t o_mv = o_out + ngroups * sizeof(fnnue_best2), o_end = o_mv + npos * 2;
-  TempDev buf;
-  if (int rc = buf.get(o_end + npos)) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  if (nchild) HIP_TRY(hipMemcpyAsync(d, child_best, nchild * sizeof(fnnue_best), hipMemcpyHostToDevice, s), "H2D");
-  if (npos) {
-    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
-    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  const int rc = best_replies_device(ctx, vranks, reinterpret_cast<uint8_t*>(d + o_end),
-                                     moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
-                                     reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
-                                     reinterpret_cast<fnnue_best*>(d), reinterpret_cast<fnnue_best2*>(d + o_out), s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, ngroups * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-// fnnue_topk_replies_device (vranks = false) and fnnue_vtopk_replies_device:
-// best_replies_device's base offsets, then the ranking kernel.
-int topk_replies_device(fnnue_ctx* ctx, bool vranks, const uint8_t* d_end, const fnnue_move* d_moves,
-                        const uint32_t* d_off, size_t ngroups, size_t npos, const fnnue_best* d_child_best,
-                        const uint32_t* d_line_off, fnnue_line2* d_lines, size_t lines_cap, void* stream) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!d_end || !d_off || !d_child_best || !d_line_off || (lines_cap && !d_lines))
-    return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  if (lines_cap == 0) return FNNUE_OK;  // no slot may be written
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  int rc = order_workspace(ctx, s);
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  uint32_t *cnt = nullptr, *base = nullptr;
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidCnt, (ngroups + 1) * 4, (void**)&cnt), "device allocation (scratch)");
-  HIP_TRY(ctx->bscratch.get(BuilderScratch::kKidOff, (ngroups + 1) * 4, (void**)&base), "device allocation (scratch)");
-  HIP_TRY(launch_child_counts(d_off, (uint32_t)ngroups, (uint32_t)npos, cnt, s), "child_counts launch");
-  HIP_TRY(builder_exclusive_scan(cnt, base, (uint32_t)ngroups, s, ctx->bscratch), "scan");
-  HIP_TRY(launch_topk_replies(vranks, d_end, d_moves, d_off, (uint32_t)ngroups, (uint32_t)npos, d_child_best, base,
-                              d_line_off, 0, d_lines, lines_cap, s),
-          "topk_replies launch");
-  return FNNUE_OK;
-}
-
-int topk_replies_host(fnnue_ctx* ctx, bool vranks, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                      size_t ngroups, size_t npos, const fnnue_best* child_best, const uint32_t* line_off,
-                      fnnue_line2* lines, size_t lines_cap) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (ngroups == 0) return FNNUE_OK;
-  if (!off || !line_off || (npos && !end)) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngroups > 0xFFFFFFFEu || npos > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  for (size_t g = 0; g < ngroups; ++g)
-    if (line_off[g] > line_off[g + 1]) return fail(FNNUE_E_ARG, "line offsets decrease");
-  const size_t nl = line_off[ngroups];
-  if (nl > lines_cap) return fail(FNNUE_E_CAPACITY, "line buffer too small");
-  if (nl && !lines) return fail(FNNUE_E_ARG, "null buffer");
-  size_t nchild = 0;  // as the kernel clamps the offsets
-  for (size_t i = 0; i < ngroups; ++i) {
-    const size_t e = std::min<size_t>(off[i + 1], npos), o = std::min<size_t>(off[i], e);
-    if (e > o) nchild += e - o - 1;
-  }
-  if (nchild && !child_best) return fail(FNNUE_E_ARG, "null buffer");
-  if (nl == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  // [child_best | off | line_off | lines | moves | end]: 4-byte parts first
-  const size_t o_off = (nchild + 1) * sizeof(fnnue_best), o_loff = o_off + (ngroups + 1) * 4;
-  const size_t o_lines = o_loff + (ngroups + 1) * 4, o_mv = o_lines + nl * sizeof(fnnue_line2), o_end = o_mv + npos * 2;
-  TempDev buf;
-  if (int rc = buf.get(o_end + npos)) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  if (nchild) HIP_TRY(hipMemcpyAsync(d, child_best, nchild * sizeof(fnnue_best), hipMemcpyHostToDevice, s), "H2D");
-  if (npos) {
-    HIP_TRY(hipMemcpyAsync(d + o_end, end, npos, hipMemcpyHostToDevice, s), "H2D");
-    if (moves) HIP_TRY(hipMemcpyAsync(d + o_mv, moves, npos * 2, hipMemcpyHostToDevice, s), "H2D");
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_off, off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(d + o_loff, line_off, (ngroups + 1) * 4, hipMemcpyHostToDevice, s), "H2D");
-  // the caller's lines go up first, so that slots no group writes (empty groups) come back as they were
-  HIP_TRY(hipMemcpyAsync(d + o_lines, lines, nl * sizeof(fnnue_line2), hipMemcpyHostToDevice, s), "H2D");
-  const int rc = topk_replies_device(ctx, vranks, reinterpret_cast<uint8_t*>(d + o_end),
-                                     moves ? reinterpret_cast<fnnue_move*>(d + o_mv) : nullptr,
-                                     reinterpret_cast<uint32_t*>(d + o_off), ngroups, npos,
-                                     reinterpret_cast<fnnue_best*>(d), reinterpret_cast<uint32_t*>(d + o_loff),
-                                     reinterpret_cast<fnnue_line2*>(d + o_lines), nl, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(lines, d + o_lines, nl * sizeof(fnnue_line2), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int fnnue_topk_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
-                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, const uint32_t* d_line_off,
-                              fnnue_line2* d_lines, size_t lines_cap, void* stream) {
-  return topk_replies_device(ctx, false, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_line_off, d_lines,
-                             lines_cap, stream);
-}
-
-int fnnue_topk_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off, size_t ngroups,
-                       size_t npos, const fnnue_best* child_best, const uint32_t* line_off, fnnue_line2* lines,
-                       size_t lines_cap) {
-  return topk_replies_host(ctx, false, end, moves, off, ngroups, npos, child_best, line_off, lines, lines_cap);
-}
-
-int fnnue_vtopk_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
-                               size_t ngroups, size_t npos, const fnnue_best* d_child_best, const uint32_t* d_line_off,
-                               fnnue_line2* d_lines, size_t lines_cap, void* stream) {
-  return topk_replies_device(ctx, true, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_line_off, d_lines,
-                             lines_cap, stream);
-}
-
-int fnnue_vtopk_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                        size_t ngroups, size_t npos, const fnnue_best* child_best, const uint32_t* line_off,
-                        fnnue_line2* lines, size_t lines_cap) {
-  return topk_replies_host(ctx, true, end, moves, off, ngroups, npos, child_best, line_off, lines, lines_cap);
-}
-
-int fnnue_best_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
-                              size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
-                              void* stream) {
-  return best_replies_device(ctx, false, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_out, stream);
-}
-
-int fnnue_best_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                       size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
-  return best_replies_host(ctx, false, end, moves, off, ngroups, npos, child_best, out);
-}
-
-int fnnue_vbest_replies_device(fnnue_ctx* ctx, const uint8_t* d_end, const fnnue_move* d_moves, const uint32_t* d_off,
-                               size_t ngroups, size_t npos, const fnnue_best* d_child_best, fnnue_best2* d_out,
-                               void* stream) {
-  return best_replies_device(ctx, true, d_end, d_moves, d_off, ngroups, npos, d_child_best, d_out, stream);
-}
-
-int fnnue_vbest_replies(fnnue_ctx* ctx, const uint8_t* end, const fnnue_move* moves, const uint32_t* off,
-                        size_t ngroups, size_t npos, const fnnue_best* child_best, fnnue_best2* out) {
-  return best_replies_host(ctx, true, end, moves, off, ngroups, npos, child_best, out);
-}
-
-}  // extern "C"
-
-namespace {
-
-// One ply's most records two plies down: 218 children of 1 + 218 records each.
-constexpr size_t kSearch2MinRecords = (size_t)(FNNUE_MAX_CHILDREN + 1) * (FNNUE_MAX_CHILDREN + 1);
-
-size_t search2_budget() {
-  size_t n = (size_t)16 << 20;
-  if (const char* e = std::getenv("FNNUE_SEARCH2_RECORDS")) n = (size_t)std::max(0LL, std::atoll(e));
-  return std::min<size_t>(std::max(n, kSearch2MinRecords), 0xFFFFFFFFu);
-}
-
-// FNNUE_SEARCH2_TRACE=1 in the environment (read per call): HIP events between
-// the phases of a fnnue_search2 call; the call then waits for its work and
-// prints the phases' device times to stderr, one JSON line — diagnostics only
-// (tools/search2_bench.py).
-struct Search2Trace {
-  enum {
-    kLevel1, kChildStates, kCount, kExpand, kEval, kReduce1, kReduce2, kTopk, kHistory, kMark, kQuiesce, kPhases
-  };
-  bool on = false;
-  hipStream_t s = nullptr;
-  std::vector<std::pair<int, hipEvent_t>> marks;
-  Search2Trace(hipStream_t stream) : s(stream) {
-    const char* e = std::getenv("FNNUE_SEARCH2_TRACE");
-    on = e && *e && *e != '0';
-  }
-  void mark(int phase) {  // `phase` starts here (kPhases: the end)
-    if (!on) return;
-    hipEvent_t ev = nullptr;
-    if (hipEventCreate(&ev) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) on = false;
-    if (ev) marks.emplace_back(phase, ev);
-  }
-  long listed = -1;  // the plies on the draw rules' list (read back for the report only)
-  int quiesce = 0;   // the quiescence depth, with what the levels held and the slices of leaves
-  bool quiesce_checks = false;  // with the evasion records and the nodes in check per level
-  QuiesceStats qstats;
-  void report(size_t plies, size_t kids, size_t records, size_t chunks) {
-    static const char* const kName[kPhases] = {"level1", "child_states", "count", "expand", "eval", "reduce1",
-                                               "reduce2", "topk", "history", "mark", "quiesce"};
-    if (on && !marks.empty() && hipEventSynchronize(marks.back().second) == hipSuccess) {
-      double ms[kPhases] = {};
-      for (size_t i = 0; i + 1 < marks.size(); ++i) {
-        float t = 0;
-        if (hipEventElapsedTime(&t, marks[i].second, marks[i + 1].second) == hipSuccess) ms[marks[i].first] += t;
-      }
-      std::string line = "FNNUE_SEARCH2_TRACE {\"plies\":" + std::to_string(plies) + ",\"children\":" +
-                         std::to_string(kids) + ",\"grandchild_records\":" + std::to_string(records) +
-                         ",\"chunks\":" + std::to_string(chunks);
-      if (listed >= 0) line += ",\"draw_list\":" + std::to_string(listed);
-      if (quiesce > 0) {
-        line += ",\"quiesce\":" + std::to_string(quiesce) + ",\"quiesce_slices\":" + std::to_string(qstats.slices) +
-                ",\"quiesce_records\":[";
-        for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_records[l]);
-        if (quiesce_checks) {
-          line += "],\"quiesce_evasions\":[";
-          for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_evasions[l]);
-          line += "],\"quiesce_in_check\":[";
-          for (int l = 0; l < quiesce; ++l) line += (l ? "," : "") + std::to_string(qstats.level_in_check[l]);
-        }
-        line += "],\"quiesce_redone\":" + std::to_string(qstats.redone) + ",\"quiesce_roots_ms\":" +
-                std::to_string(qstats.roots_ms) + ",\"quiesce_gen_ms\":" + std::to_string(qstats.gen_ms) +
-                ",\"quiesce_eval_ms\":" + std::to_string(qstats.eval_ms) + ",\"quiesce_reduce_ms\":" +
-                std::to_string(qstats.reduce_ms);
-      }
-      for (int k = 0; k < kPhases; ++k) line += std::string(",\"") + kName[k] + "_ms\":" + std::to_string(ms[k]);
-      std::fprintf(stderr, "%s}\n", line.c_str());
-    }
-  }
-  ~Search2Trace() {
-    for (auto& m : marks) (void)hipEventDestroy(m.second);
-  }
-};
-
-// The net a two-ply search of `variant` needs: fnnue_search2* (vcall = false) a
-// chess net, fnnue_vsearch2* fnnue_vsearch1's (never a chess context).
-int search2_arch(const fnnue_ctx* ctx, int variant, bool vcall) {
-  if (!vcall)
-    return ctx->variant == kVariantChess ? (int)FNNUE_OK : fail(FNNUE_E_ARCH, "the two-ply search needs a chess net");
-  if (ctx->variant == kVariantChess || variant == kVariantChess)
-    return fail(FNNUE_E_ARCH, "the variant two-ply search needs a variant net");
-  return search1_arch(ctx, variant);
-}
-
-// The variant entry points hand their counts back zeroed on every error path, a null context included.
-void zero_counts(size_t* n_out, size_t* n_groups, size_t* n_children) {
-  if (n_out) *n_out = 0;
-  if (n_groups) *n_groups = 0;
-  if (n_children) *n_children = 0;
-}
-
-// fnnue_search2_device (variant = chess) and fnnue_vsearch2_device; with
-// d_child_best / d_child_map (child_cap entries each) also the children's
-// depth-1 records (fnnue_[v]search2_children); with k >= 1 also ply p's k best
-// lines at d_lines[p * k ..] (fnnue_[v]search2_lines_device): one more kernel
-// behind the second reduction, over the same arrays.
-int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                   size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap,
-                   fnnue_best* d_child_best, uint32_t* d_child_map, size_t child_cap, size_t* n_out, size_t* n_groups,
-                   size_t* n_children, void* stream, uint32_t k = 0, fnnue_line2* d_lines = nullptr,
-                   size_t lines_cap = 0) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (n_children) *n_children = 0;
-  if (int rc = search2_arch(ctx, variant, vcall)) return rc;
-  if (ngames == 0) return FNNUE_OK;
-  const bool chess = variant == kVariantChess;
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  int rc = order_workspace(ctx, s);
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  using W = BuilderScratch;
-  W& ws = ctx->bscratch;
-  Search2Trace trace(s);
-  trace.mark(Search2Trace::kLevel1);
-  // level 1: the plies' boards (scratch) and their STAR groups' offsets, moves and end flags
-  ChildrenBufs kids;
-  kids.max_groups = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  if (k) kids.max_groups = d_lines ? std::min(kids.max_groups, lines_cap / k) : 0;
-  size_t nrec = 0, nply = 0;
-  if (chess) {
-    rc = build_device(ctx, d_text, d_fen_off, d_moves_off, ngames, FNNUE_PLAYOUT_CHILDREN, nullptr, 0, nullptr, 0,
-                      nullptr, nullptr, &nrec, &nply, s, &kids);
-  } else {
-    VChildrenBufs vkids;
-    vkids.max_groups = kids.max_groups;
-    rc = build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
-                       &nrec, &nply, s, &vkids);
-    kids.off = vkids.off;
-    kids.moves = vkids.moves;
-    kids.end = vkids.end;
-    kids.ply_off = vkids.ply_off;
-  }
-  // the second reduction: the chess ranks, or the variants' (FNNUE_END_WON, every reply loses)
-  const auto reduce2 = chess ? launch_best_replies : launch_vbest_replies;
-  // a board of the variant: DBoard for chess, kingofthehill, racingkings and threecheck, vb::VBoard otherwise
-  const size_t state_bytes = chess ? sizeof(DBoard) : vstate_bytes(variant);
-  *n_out = nply;
-  *n_groups = nply || rc == FNNUE_OK ? ngames : 0;
-  if (rc) return rc;
-  if (nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  const size_t nkid = nrec - nply;
-  if (n_children) *n_children = nkid;
-  if (n_children && (nkid > child_cap || (nkid && (!d_child_best || !d_child_map))))
-    return fail(FNNUE_E_CAPACITY, "child buffers too small");
-  const void* plies = ws.p[W::kStates];
-  char* kid_states = nullptr;
-  uint32_t *kid_cnt = nullptr, *kid_off = nullptr, *spans = nullptr;
-  fnnue_best* kid_best = nullptr;
-  HIP_TRY(ws.get(W::kKidStates, (nkid + 1) * state_bytes, (void**)&kid_states), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kKidCnt, (nkid + 1) * 4, (void**)&kid_cnt), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kKidOff, (nkid + 1) * 4, (void**)&kid_off), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kKidBest, (nkid + 1) * sizeof(fnnue_best), (void**)&kid_best), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kPlySpans, (nply + 1) * 8, (void**)&spans), "device allocation (search scratch)");
-  if (nkid == 0) {  // every ply is a finished game's last
-    HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
-            "best_replies launch");
-    if (k)  // every slot all-zero
-      HIP_TRY(launch_topk_replies(!chess, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best,
-                                  nullptr, nullptr, k, d_lines, lines_cap, s),
-              "topk_replies launch");
-    HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
-    return FNNUE_OK;
-  }
-  // The draw rules (chess, fnnue_set_search_draws): the plies' history and the
-  // marks on the listed plies' children here, their grandchildren per chunk.
-  const bool draws = chess && ctx->search_draws;
-  DrawHistory hist;
-  if (draws) {
-    trace.mark(Search2Trace::kHistory);
-    HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames,
-                                static_cast<const DBoard*>(plies), (uint32_t)nply, draw_key_bits(), s, ws, &hist),
-            "game history launch");
-    trace.mark(Search2Trace::kMark);
-    HIP_TRY(mark_draws_level1(hist, static_cast<const DBoard*>(plies), (uint32_t)nply, kids.off, kids.moves, kids.end,
-                              s),
-            "draw marks launch");
-  }
-  trace.mark(Search2Trace::kChildStates);
-  if (chess)
-    HIP_TRY(child_states_device(static_cast<const DBoard*>(plies), (uint32_t)nply, kids.off, (uint32_t)nrec,
-                                reinterpret_cast<DBoard*>(kid_states), reinterpret_cast<uint2*>(d_child_map), s),
-            "child_states launch");
-  else
-    HIP_TRY(vchild_states_device(variant, plies, (uint32_t)nply, kids.off, (uint32_t)nrec, kid_states,
-                                 reinterpret_cast<uint2*>(d_child_map), s),
-            "child_states launch");
-  // level 2 sizes: every child's records, and per ply where its children and their records start
-  trace.mark(Search2Trace::kCount);
-  if (chess)
-    HIP_TRY(children_count_device(reinterpret_cast<DBoard*>(kid_states), (uint32_t)nkid, kid_cnt, kid_off, s, ws),
-            "children count");
-  else
-    HIP_TRY(vchildren_count_device(variant, kid_states, (uint32_t)nkid, kid_cnt, kid_off, s, ws), "children count");
-  HIP_TRY(ply_spans_device(kids.off, kid_off, (uint32_t)nply, spans, spans + nply + 1, s), "ply_spans launch");
-  std::vector<uint32_t> h((nply + 1) * 2);
-  HIP_TRY(hipMemcpyAsync(h.data(), spans, h.size() * 4, hipMemcpyDeviceToHost, s), "D2H(sizes)");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  const uint32_t *first_kid = h.data(), *first_rec = h.data() + nply + 1;
-  // chunks of whole plies within the budget; a ply larger than the budget (a
-  // crazyhouse ply has no fixed bound) is a chunk of its own.  One ply's records
-  // are the 32-bit difference of two offsets, as the device takes it (a ply's
-  // children times their children: far below 2^32); a chunk's are their sum in
-  // 64 bits, so a call whose grandchild records pass 2^32 in all still cuts
-  // right and runs chunk by chunk, and no chunk's count wraps (budget < 2^32).
-  const size_t budget = search2_budget();
-  std::vector<uint32_t> cuts{0};
-  size_t max_rec = 0, max_kid = 0, all_rec = 0;
-  for (size_t p = 0; p < nply;) {
-    size_t q = p + 1;
-    uint64_t sum = (uint32_t)(first_rec[q] - first_rec[p]);
-    while (q < nply && sum + (uint32_t)(first_rec[q + 1] - first_rec[q]) <= budget) {
-      sum += (uint32_t)(first_rec[q + 1] - first_rec[q]);
-      ++q;
-    }
-    max_rec = std::max<size_t>(max_rec, sum);
-    all_rec += sum;
-    max_kid = std::max<size_t>(max_kid, first_kid[q] - first_kid[p]);
-    cuts.push_back((uint32_t)q);
-    p = q;
-  }
-  uint32_t* ch_off = nullptr;
-  void* gpos = nullptr;
-  uint16_t* gmoves = nullptr;
-  uint8_t* gend = nullptr;
-  int32_t *gps = nullptr, *gpo = nullptr;
-  HIP_TRY(ws.get(W::kChunkOff, (max_kid + 1) * 4, (void**)&ch_off), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrand, max_rec * (chess ? sizeof(fnnue_pos) : sizeof(fnnue_vpos)), &gpos),
-          "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrandMoves, max_rec * 2, (void**)&gmoves), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrandEnd, max_rec, (void**)&gend), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrandPsqt, max_rec * 4, (void**)&gps), "device allocation (search scratch)");
-  HIP_TRY(ws.get(W::kGrandPositional, max_rec * 4, (void**)&gpo), "device allocation (search scratch)");
-  for (size_t i = 0; i + 1 < cuts.size(); ++i) {
-    const uint32_t k0 = first_kid[cuts[i]], nk = first_kid[cuts[i + 1]] - k0;
-    const uint32_t nr = first_rec[cuts[i + 1]] - first_rec[cuts[i]];
-    if (nk == 0) continue;  // plies without a legal move
-    trace.mark(Search2Trace::kExpand);
-    HIP_TRY(rebase_offsets_device(kid_off + k0, nk + 1, ch_off, s), "rebase_offsets launch");
-    const char* chunk_states = kid_states + (size_t)k0 * state_bytes;
-    if (chess)
-      HIP_TRY(children_write_device(reinterpret_cast<const DBoard*>(chunk_states), nk, ch_off, nr,
-                                    static_cast<fnnue_pos*>(gpos), gmoves, gend, s),
-              "children write");
-    else
-      HIP_TRY(vchildren_write_device(variant, chunk_states, nk, ch_off, nr, static_cast<fnnue_vpos*>(gpos), gmoves,
-                                     gend, s),
-              "children write");
-    if (draws) {  // behind the expansion, before the reduction reads the end bytes; offsets relative to the chunk
-      trace.mark(Search2Trace::kMark);
-      HIP_TRY(mark_draws_level2(hist, static_cast<const DBoard*>(plies), cuts[i], cuts[i + 1], kids.off,
-                                reinterpret_cast<const DBoard*>(kid_states), kid_off, first_rec[cuts[i]], gmoves, gend,
-                                s),
-              "draw marks launch");
-    }
-    trace.mark(Search2Trace::kEval);
-    rc = chess ? fnnue_eval_groups_device(ctx, static_cast<fnnue_pos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
-                                          gpo, s)
-               : fnnue_eval_vgroups_device(ctx, static_cast<fnnue_vpos*>(gpos), ch_off, nk, nr, FNNUE_GROUP_STAR, gps,
-                                           gpo, s);
-    if (rc) return rc;
-    if (chess && ctx->search_quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
-      trace.mark(Search2Trace::kQuiesce);
-      trace.quiesce = ctx->search_quiesce;
-      trace.qstats.timed = trace.on;
-      if ((rc = quiesce_leaves_device(ctx, ws, reinterpret_cast<const DBoard*>(chunk_states), nk, ch_off, nr, gend, gps,
-                                      gpo, ctx->search_quiesce, ctx->search_quiesce_checks, 2, s, &trace.qstats)))
-        return rc;
-      trace.quiesce_checks = ctx->search_quiesce_checks;
-    }
-    trace.mark(Search2Trace::kReduce1);
-    HIP_TRY(launch_best_children_own(gps, gpo, gend, gmoves, ch_off, nk, nr, kid_best + k0, s), "best_children launch");
-    if (draws) {  // a drawn child's pv ends at it: its own terms, while the chunk still holds them
-      trace.mark(Search2Trace::kMark);
-      HIP_TRY(draw_own_terms(hist, cuts[i], cuts[i + 1], kids.off, kids.end, kid_off, first_rec[cuts[i]], gps, gpo,
-                             kid_best, s),
-              "draw terms launch");
-    }
-  }
-  trace.mark(Search2Trace::kReduce2);
-  HIP_TRY(reduce2(kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best, nullptr, d_out, s),
-          "best_replies launch");
-  if (k) {
-    trace.mark(Search2Trace::kTopk);
-    HIP_TRY(launch_topk_replies(!chess, kids.end, kids.moves, kids.off, (uint32_t)nply, (uint32_t)nrec, kid_best,
-                                nullptr, nullptr, k, d_lines, lines_cap, s),
-            "topk_replies launch");
-  }
-  trace.mark(Search2Trace::kPhases);
-  if (draws && trace.on) {
-    uint32_t listed = 0;
-    HIP_TRY(hipMemcpyAsync(&listed, hist.list, 4, hipMemcpyDeviceToHost, s), "D2H(draw list)");
-    HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-    trace.listed = (long)listed;
-  }
-  trace.report(nply, nkid, all_rec, cuts.size() - 1);
-  if (n_children && nkid)
-    HIP_TRY(hipMemcpyAsync(d_child_best, kid_best, nkid * sizeof(fnnue_best), hipMemcpyDeviceToDevice, s),
-            "D2D(children)");
-  HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
-  return FNNUE_OK;
-}
-
-int search2_host(fnnue_ctx* ctx, int variant, bool vcall, const char* text, size_t text_len, const uint32_t* fen_off, const uint32_t* moves_off,
-                 size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap, fnnue_best* child_best,
-                 uint32_t* child_map, size_t child_cap, size_t* n_out, size_t* n_groups, size_t* n_children,
-                 uint32_t k = 0, fnnue_line2* lines = nullptr, size_t lines_cap = 0) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (n_children) *n_children = 0;
-  if (int rc = search2_arch(ctx, variant, vcall)) return rc;
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1 && (!k || lines);
-  const bool kroom = n_children && child_best && child_map;
-  if (!kroom) child_cap = 0;
-  // [best2 | child_best | child_map | lines | off]: the lines' room is cut to whole plies the records have room for
-  const size_t nl = k ? std::min(lines_cap / k, cap) * k : 0;
-  TempDev buf;
-  const size_t o_cb = cap * sizeof(fnnue_best2), o_cm = o_cb + child_cap * sizeof(fnnue_best);
-  const size_t o_lines = o_cm + child_cap * 8, o_off = o_lines + nl * sizeof(fnnue_line2);
-  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  rc = search2_device(ctx, variant, vcall, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_best2*>(d) : nullptr,
-                      room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr, room ? off_cap : 0,
-                      room && kroom ? reinterpret_cast<fnnue_best*>(d + o_cb) : nullptr,
-                      room && kroom ? reinterpret_cast<uint32_t*>(d + o_cm) : nullptr, room ? child_cap : 0, n_out,
-                      n_groups, n_children, s, k, room && k ? reinterpret_cast<fnnue_line2*>(d + o_lines) : nullptr,
-                      room ? nl : 0);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_best2), hipMemcpyDeviceToHost, s), "D2H");
-  if (k) HIP_TRY(hipMemcpyAsync(lines, d + o_lines, *n_out * k * sizeof(fnnue_line2), hipMemcpyDeviceToHost, s), "D2H");
-  if (n_children && *n_children) {
-    HIP_TRY(hipMemcpyAsync(child_best, d + o_cb, *n_children * sizeof(fnnue_best), hipMemcpyDeviceToHost, s), "D2H");
-    HIP_TRY(hipMemcpyAsync(child_map, d + o_cm, *n_children * 8, hipMemcpyDeviceToHost, s), "D2H");
-  }
-  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return latched(ctx);
-}
-
-}  // namespace
-
-extern "C" {
-
-int fnnue_search2_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                         size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out,
-                         size_t* n_groups, void* stream) {
-  return search2_device(ctx, kVariantChess, false, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
-                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream);
-}
-
-int fnnue_search2(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                  const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off, size_t off_cap,
-                  size_t* n_out, size_t* n_groups) {
-  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
-                      nullptr, nullptr, 0, n_out, n_groups, nullptr);
-}
-
-int fnnue_search2_children(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                           const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
-                           size_t off_cap, fnnue_best* child_best, uint32_t* child_map, size_t child_cap,
-                           size_t* n_out, size_t* n_groups, size_t* n_children) {
-  if (!n_children) return fail(FNNUE_E_ARG, "null argument");
-  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
-                      child_best, child_map, child_cap, n_out, n_groups, n_children);
-}
-
-int fnnue_vsearch2_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                          const uint32_t* d_moves_off, size_t ngames, fnnue_best2* d_out, size_t cap, uint32_t* d_off,
-                          size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  zero_counts(n_out, n_groups, nullptr);
-  return search2_device(ctx, variant, true, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
-                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream);
-}
-
-int fnnue_vsearch2(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                   const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
-                   size_t off_cap, size_t* n_out, size_t* n_groups) {
-  zero_counts(n_out, n_groups, nullptr);
-  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr,
-                      nullptr, 0, n_out, n_groups, nullptr);
-}
-
-int fnnue_vsearch2_children(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                            const uint32_t* moves_off, size_t ngames, fnnue_best2* out, size_t cap, uint32_t* off,
-                            size_t off_cap, fnnue_best* child_best, uint32_t* child_map, size_t child_cap,
-                            size_t* n_out, size_t* n_groups, size_t* n_children) {
-  zero_counts(n_out, n_groups, n_children);
-  if (!n_children) return fail(FNNUE_E_ARG, "null argument");
-  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
-                      child_best, child_map, child_cap, n_out, n_groups, n_children);
-}
-
-static int lines2_k(uint32_t k, size_t* n_out, size_t* n_groups) {
-  zero_counts(n_out, n_groups, nullptr);
-  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return FNNUE_OK;
-}
-
-int fnnue_search2_lines_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                               const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best2* d_out, size_t cap,
-                               uint32_t* d_off, size_t off_cap, fnnue_line2* d_lines, size_t lines_cap, size_t* n_out,
-                               size_t* n_groups, void* stream) {
-  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
-  return search2_device(ctx, kVariantChess, false, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
-                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream, k, d_lines, lines_cap);
-}
-
-int fnnue_search2_lines(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                        const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best2* out, size_t cap,
-                        uint32_t* off, size_t off_cap, fnnue_line2* lines, size_t lines_cap, size_t* n_out,
-                        size_t* n_groups) {
-  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
-  return search2_host(ctx, kVariantChess, false, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap,
-                      nullptr, nullptr, 0, n_out, n_groups, nullptr, k, lines, lines_cap);
-}
-
-int fnnue_vsearch2_lines_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                                const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best2* d_out, size_t cap,
-                                uint32_t* d_off, size_t off_cap, fnnue_line2* d_lines, size_t lines_cap, size_t* n_out,
-                                size_t* n_groups, void* stream) {
-  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
-  return search2_device(ctx, variant, true, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap,
-                        nullptr, nullptr, 0, n_out, n_groups, nullptr, stream, k, d_lines, lines_cap);
-}
-
-int fnnue_vsearch2_lines(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                         const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best2* out, size_t cap,
-                         uint32_t* off, size_t off_cap, fnnue_line2* lines, size_t lines_cap, size_t* n_out,
-                         size_t* n_groups) {
-  if (int rc = lines2_k(k, n_out, n_groups)) return rc;
-  return search2_host(ctx, variant, true, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, nullptr,
-                      nullptr, 0, n_out, n_groups, nullptr, k, lines, lines_cap);
 }
 
 int fnnue_vmove_uci(fnnue_move m, char out[8]) {
@@ -2424,124 +1355,6 @@ int fnnue_vmove_uci(fnnue_move m, char out[8]) {
     return FNNUE_OK;
   }
   return fnnue_move_uci(m, out);
-}
-
-int fnnue_build_vchildren_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                                 const uint32_t* d_moves_off, size_t ngames, fnnue_vpos* d_out, size_t cap,
-                                 uint32_t* d_off, size_t off_cap, fnnue_move* d_moves, uint8_t* d_end, size_t* n_out,
-                                 size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  if (d_out && (!d_moves || !d_end)) return fail(FNNUE_E_ARG, "null moves / end buffer");
-  return build_vdevice(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, d_moves,
-                       d_end, n_out, n_groups, stream);
-}
-
-int fnnue_build_vchildren(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                          const uint32_t* moves_off, size_t ngames, fnnue_vpos* out, size_t cap, uint32_t* off,
-                          size_t off_cap, fnnue_move* moves, uint8_t* end, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (!variant_net_id(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  rc = fnnue_build_vchildren_device(ctx, variant, d_text, d_fo, d_mo, ngames, nullptr, 0, nullptr, 0, nullptr, nullptr,
-                                    n_out, n_groups, s);
-  if (rc != FNNUE_E_CAPACITY) return rc;  // sizing pass: always "too small" with no outputs
-  if (!out || !off || !moves || !end || cap < *n_out || off_cap < *n_groups + 1)
-    return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  const size_t nrec = *n_out, ng = *n_groups;
-  TempDev buf;  // [records | off | moves | end]
-  const size_t o_off = nrec * sizeof(fnnue_vpos), o_mv = o_off + (ng + 1) * 4, o_end = o_mv + nrec * 2;
-  if ((rc = buf.get(o_end + nrec))) return rc;
-  char* d = static_cast<char*>(buf.p);
-  rc = fnnue_build_vchildren_device(ctx, variant, d_text, d_fo, d_mo, ngames, reinterpret_cast<fnnue_vpos*>(d), nrec,
-                                    reinterpret_cast<uint32_t*>(d + o_off), ng + 1,
-                                    reinterpret_cast<fnnue_move*>(d + o_mv), reinterpret_cast<uint8_t*>(d + o_end),
-                                    n_out, n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_vpos), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, d + o_off, (*n_groups + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(moves, d + o_mv, *n_out * 2, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(end, d + o_end, *n_out, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
-}
-
-int fnnue_vsearch1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                          const uint32_t* d_moves_off, size_t ngames, fnnue_best* d_out, size_t cap, uint32_t* d_off,
-                          size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  return search1_device(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, 0, d_out, cap, d_off, off_cap, nullptr,
-                        0, n_out, n_groups, stream);
-}
-
-int fnnue_vsearch1_lines_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
-                                const uint32_t* d_moves_off, size_t ngames, uint32_t k, fnnue_best* d_out, size_t cap,
-                                uint32_t* d_off, size_t off_cap, fnnue_line* d_lines, size_t lines_cap, size_t* n_out,
-                                size_t* n_groups, void* stream) {
-  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_device(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, k, d_out, cap, d_off, off_cap, d_lines,
-                        lines_cap, n_out, n_groups, stream);
-}
-
-int fnnue_vsearch1_lines(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                         const uint32_t* moves_off, size_t ngames, uint32_t k, fnnue_best* out, size_t cap,
-                         uint32_t* off, size_t off_cap, fnnue_line* lines, size_t lines_cap, size_t* n_out,
-                         size_t* n_groups) {
-  if (k < 1 || k > FNNUE_MAX_CHILDREN) return fail(FNNUE_E_ARG, "k must be 1.." + std::to_string(FNNUE_MAX_CHILDREN));
-  return search1_host(ctx, variant, text, text_len, fen_off, moves_off, ngames, k, out, cap, off, off_cap, lines,
-                      lines_cap, n_out, n_groups);
-}
-
-int fnnue_vsearch1(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
-                   const uint32_t* moves_off, size_t ngames, fnnue_best* out, size_t cap, uint32_t* off,
-                   size_t off_cap, size_t* n_out, size_t* n_groups) {
-  return search1_host(ctx, variant, text, text_len, fen_off, moves_off, ngames, 0, out, cap, off, off_cap, nullptr, 0,
-                      n_out, n_groups);
-}
-
-int fnnue_build_batch(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                      const uint32_t* moves_off, size_t ngames, int mode, fnnue_pos* out, size_t cap, uint32_t* off,
-                      size_t off_cap, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (ngames == 0) return FNNUE_OK;
-  if (fen_off[ngames] > text_len) return fail(FNNUE_E_ARG, "offsets exceed the text");
-  for (size_t i = 0; i < ngames; ++i)
-    if (fen_off[i] > moves_off[i] || moves_off[i] > fen_off[i + 1]) return fail(FNNUE_E_ARG, "offsets out of order");
-  DeviceGuard g(ctx->device);
-  // Input and output staging are per-context and grow-only (host-API calls are
-  // synchronous), so a steady stream of batches allocates nothing.
-  const size_t text_bytes = (text_len + 255) / 256 * 256;
-  const size_t fo_bytes = (ngames + 1) * 4, mo_bytes = ngames * 4;
-  int rc = ensure_builder_input(ctx, text_bytes + fo_bytes + mo_bytes);
-  if (rc) return rc;
-  char* d_text = ctx->d_btext;
-  uint32_t* d_fo = reinterpret_cast<uint32_t*>(d_text + text_bytes);
-  uint32_t* d_mo = d_fo + (ngames + 1);
-  hipStream_t s = ctx->stream;
-  HIP_TRY(hipMemcpyAsync(d_text, text, text_len, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(d_fo, fen_off, fo_bytes, hipMemcpyHostToDevice, s), "H2D");
-  HIP_TRY(hipMemcpyAsync(d_mo, moves_off, mo_bytes, hipMemcpyHostToDevice, s), "H2D");
-  rc = fnnue_build_batch_device(ctx, d_text, d_fo, d_mo, ngames, mode, nullptr, 0, nullptr, 0, n_out, n_groups, s);
-  if (rc != FNNUE_E_CAPACITY) return rc;  // sizing pass: always "too small" with no outputs
-  if (!out || !off || cap < *n_out || off_cap < *n_groups + 1) return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  if ((rc = ensure_stage(ctx, *n_out, *n_groups + 1))) return rc;
-  fnnue_pos* d_out = ctx->d_pos;
-  uint32_t* d_off = ctx->d_off;
-  rc = fnnue_build_batch_device(ctx, d_text, d_fo, d_mo, ngames, mode, d_out, *n_out, d_off, *n_groups + 1, n_out,
-                                n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d_out, *n_out * sizeof(fnnue_pos), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, d_off, (*n_groups + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
 }
 
 int fnnue_perft_device(fnnue_ctx* ctx, const char* fen, int depth, uint64_t* nodes) {
@@ -2589,42 +1402,6 @@ int fnnue_random_game(uint64_t seed, const char* fen, uint32_t plies, char* move
   *len = out.size();
   if (!moves || cap < out.size() + 1) return fail(FNNUE_E_CAPACITY, "output buffer too small");
   std::memcpy(moves, out.c_str(), out.size() + 1);
-  return FNNUE_OK;
-}
-}  // extern "C"
-
-// ---- capture quiescence (ABI 3.13; the kernels: quiesce.hip) ----
-extern "C" {
-
-int fnnue_set_search_quiesce(fnnue_ctx* ctx, int depth) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  if (depth < 0 || depth > FNNUE_QUIESCE_MAX)
-    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
-  ctx->search_quiesce = depth;
-  return FNNUE_OK;
-}
-
-int fnnue_get_search_quiesce(const fnnue_ctx* ctx, int* depth) {
-  if (!ctx || !depth) return fail(FNNUE_E_ARG, "null argument");
-  *depth = ctx->search_quiesce;
-  return FNNUE_OK;
-}
-
-int fnnue_set_search_quiesce_checks(fnnue_ctx* ctx, int on) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  ctx->search_quiesce_checks = on != 0;
-  return FNNUE_OK;
-}
-
-int fnnue_get_search_quiesce_checks(const fnnue_ctx* ctx, int* on) {
-  if (!ctx || !on) return fail(FNNUE_E_ARG, "null argument");
-  *on = ctx->search_quiesce_checks ? 1 : 0;
-  return FNNUE_OK;
-}
-
-int fnnue_quiesce_slices(const fnnue_ctx* ctx, uint64_t* slices) {
-  if (!ctx || !slices) return fail(FNNUE_E_ARG, "null argument");
-  *slices = ctx->quiesce_slices;
   return FNNUE_OK;
 }
 
@@ -2681,155 +1458,6 @@ int fnnue_game_quiet_moves(const char* fen, const char* moves, fnnue_pos* out, s
   *n_out = 0;
   *in_check = 0;
   return game_candidates(fen, moves, out, cap, mv, true, in_check, n_out);
-}
-
-int fnnue_quiesce_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
-                         size_t ngames, uint32_t depth, fnnue_quiet* d_out, size_t cap, uint32_t* d_off,
-                         size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (depth > FNNUE_QUIESCE_MAX)
-    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "quiescence needs a chess net");
-  if (ngames == 0) return FNNUE_OK;
-  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  int rc = order_workspace(ctx, s);  // the scratch is the context's: ordered like its workspace
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  const DBoard* states = nullptr;
-  const uint32_t* ply_off = nullptr;
-  const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  const BuildResult R = replay_states_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s, ctx->bscratch,
-                                             &states, &ply_off);
-  if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
-  *n_out = R.n_out;
-  *n_groups = R.n_groups;
-  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(R.err_game));
-  if (R.err_code)
-    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
-                                  std::to_string(R.err_game));
-  if (R.n_out > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-  if ((rc = quiesce_nodes_device(ctx, ctx->bscratch, states, (uint32_t)R.n_out, (int)depth, ctx->search_quiesce_checks,
-                                 d_out, s, nullptr)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
-  return FNNUE_OK;
-}
-
-int fnnue_quiesce(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                  const uint32_t* moves_off, size_t ngames, uint32_t depth, fnnue_quiet* out, size_t cap,
-                  uint32_t* off, size_t off_cap, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (depth > FNNUE_QUIESCE_MAX)
-    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
-  if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "quiescence needs a chess net");
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1;
-  TempDev buf;  // [results | off]
-  const size_t o_off = (cap * sizeof(fnnue_quiet) + 15) / 16 * 16;
-  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  rc = fnnue_quiesce_device(ctx, d_text, d_fo, d_mo, ngames, depth, room ? reinterpret_cast<fnnue_quiet*>(d) : nullptr,
-                            room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
-                            room ? off_cap : 0, n_out, n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_quiet), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return latched(ctx);
-}
-
-}  // extern "C"
-
-// ---- repetition and fifty-move draws (ABI 3.12; the kernels: draws.hip) ----
-extern "C" {
-
-int fnnue_set_search_draws(fnnue_ctx* ctx, int on) {
-  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
-  ctx->search_draws = on != 0;
-  return FNNUE_OK;
-}
-
-int fnnue_get_search_draws(const fnnue_ctx* ctx, int* on) {
-  if (!ctx || !on) return fail(FNNUE_E_ARG, "null argument");
-  *on = ctx->search_draws ? 1 : 0;
-  return FNNUE_OK;
-}
-
-int fnnue_game_history_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                              const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap,
-                              uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (ngames == 0) return FNNUE_OK;
-  if (!d_text || !d_fen_off || !d_moves_off) return fail(FNNUE_E_ARG, "null buffer");
-  if (ngames > (1u << 26)) return fail(FNNUE_E_ARG, "too many games");
-  DeviceGuard g(ctx->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  int rc = order_workspace(ctx, s);  // the scratch is the context's: ordered like its workspace
-  if (rc) return rc;
-  WorkspaceUse use{ctx, s};
-  const DBoard* states = nullptr;
-  const uint32_t* ply_off = nullptr;
-  const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  const BuildResult R = replay_states_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s, ctx->bscratch,
-                                             &states, &ply_off);
-  if (R.hip != hipSuccess) return hip_fail(R.hip, "device batch builder");
-  *n_out = R.n_out;
-  *n_groups = R.n_groups;
-  if (R.capacity) return fail(FNNUE_E_CAPACITY, "output buffer too small");
-  if (R.err_code == kBuildErrFen) return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(R.err_game));
-  if (R.err_code)
-    return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(R.err_ply) + " of game " +
-                                  std::to_string(R.err_game));
-  DrawHistory hist;
-  HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, ply_off, (uint32_t)ngames, states, (uint32_t)R.n_out,
-                              draw_key_bits(), s, ctx->bscratch, &hist),
-          "game history launch");
-  HIP_TRY(hipMemcpyAsync(d_out, hist.hist, R.n_out * sizeof(fnnue_ply_history), hipMemcpyDeviceToDevice, s),
-          "D2D(history)");
-  HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
-  return FNNUE_OK;
-}
-
-int fnnue_ctx_game_history(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,
-                           const uint32_t* moves_off, size_t ngames, fnnue_ply_history* out, size_t cap, uint32_t* off,
-                           size_t off_cap, size_t* n_out, size_t* n_groups) {
-  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
-    return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
-  if (ngames == 0) return FNNUE_OK;
-  DeviceGuard g(ctx->device);
-  char* d_text = nullptr;
-  uint32_t *d_fo = nullptr, *d_mo = nullptr;
-  int rc = stage_games(ctx, text, text_len, fen_off, moves_off, ngames, &d_text, &d_fo, &d_mo);
-  if (rc) return rc;
-  const bool room = out && off && off_cap >= ngames + 1;
-  TempDev buf;  // [history | off]
-  const size_t o_off = cap * sizeof(fnnue_ply_history);
-  if (room && (rc = buf.get(o_off + (ngames + 1) * 4))) return rc;
-  char* d = static_cast<char*>(buf.p);
-  hipStream_t s = ctx->stream;
-  rc = fnnue_game_history_device(ctx, d_text, d_fo, d_mo, ngames, room ? reinterpret_cast<fnnue_ply_history*>(d) : nullptr,
-                                 room ? cap : 0, room ? reinterpret_cast<uint32_t*>(d + o_off) : nullptr,
-                                 room ? off_cap : 0, n_out, n_groups, s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d, *n_out * sizeof(fnnue_ply_history), hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipMemcpyAsync(off, d + o_off, (ngames + 1) * 4, hipMemcpyDeviceToHost, s), "D2H");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return FNNUE_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // internal.h — host-side internals shared by the C ABI translation units
-// (capi.cpp: single-device contexts; multi.cpp: one process driving several
-// devices over RCCL).  Not part of the ABI.
+// (capi.cpp: nets, contexts, evaluation; search_api.cpp: the device builder and
+// searches; multi.cpp: one process driving several devices over RCCL).  Not
+// part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -104,6 +105,36 @@ int ensure_stage(fnnue_ctx* c, size_t npos, size_t noff);
 int ensure_builder_input(fnnue_ctx* c, size_t bytes);
 // Reads and clears the latched device error word.
 int latched(fnnue_ctx* c);
+// Workspace ordering across streams (the workspace is shared by every call on
+// a ctx): a call on a caller's stream records ws_event on it when its work is
+// enqueued (also after an error: part of it may be), and each call first
+// waits for that event.  No caller stream handle of an earlier call is ever
+// used again, so a caller may destroy a stream right after a call on it.  A
+// call on the context's own stream records nothing (an event record between
+// two kernels idles the stream for microseconds): the next call on the same
+// stream is ordered by the stream, and a call on another stream records
+// ws_event on the own stream, which lives as long as the context, first.
+struct WorkspaceUse {
+  fnnue_ctx* c;
+  hipStream_t s;
+  ~WorkspaceUse() {
+    if (s == c->stream) {
+      c->ws_own_pending = true;
+    } else if (hipEventRecord(c->ws_event, s) == hipSuccess) {
+      c->ws_recorded = true;
+      c->ws_own_pending = false;
+    } else {
+      // No event for this call's work: the stale one (an earlier call's) would
+      // let the next call on another stream overwrite the workspace while this
+      // one still reads it.  Wait for the work instead (a destructor cannot
+      // return the error; the ordering is what must hold).
+      (void)hipStreamSynchronize(s);
+      c->ws_recorded = false;
+      c->ws_own_pending = false;
+    }
+  }
+};
+int order_workspace(fnnue_ctx* c, hipStream_t s);
 // The device's position rule on the host (one king per side, <= 32 pieces, valid codes, stm 0/1).
 bool valid_host_pos(const fnnue_pos& p);
 // After FNNUE_E_POSITION latched: names the first invalid position, as index

@@ -339,6 +339,51 @@ def want_score(kind, value):
     return B.Score("cp", trunc_div(value * 100, NORM))
 
 
+def test_actor_with_every_search_setting_matches_the_library(data):
+    """The draw rules, quiescence 1 with checks and MultiPV lines at two plies, all on at once: the actor's
+    answers and lines against search2_lines, record for record (both run the same level-2 steps)."""
+    games = [(D.START, " ".join([D.SHUFFLE] * 2)),                      # a threefold repetition in reach
+             (START, "f2f3 e7e5 g2g4 d8h4"),                            # ends in mate
+             ("7k/5Q2/5K2/8/8/8/8/8 w - - 0 1", "f6g6"),                # ends in stalemate
+             SCANDI]                                                    # captures and checks about
+    e = F.Evaluator(F.Net.from_bytes(data), 0)
+    stub, actor = make_channel(data, draw_rules=True, quiesce=1, quiesce_checks=True, analysis_plies=2)
+    try:
+        e.set_search_draws(True)
+        e.set_search_quiesce(1)
+        e.set_search_quiesce_checks(True)
+        out, off, l2 = e.search2_lines(games, K)
+        n0 = off[1]   # the shuffle game's plies: the repetition is in reach, so the draw rules change their answers
+        e.set_search_draws(False)
+        assert e.search2_lines(games, K)[2][:n0].tobytes() != l2[:n0].tobytes()
+        e.set_search_draws(True)
+        res = stub.go_lines_pv(bodies_of(games, multipv=K))
+        uci = lambda m: F.move_uci(int(m))
+        ended = 0
+        for i, rows in enumerate(res):
+            assert not isinstance(rows, B.PositionFailed), rows
+            assert len(rows) == off[i + 1] - off[i]
+            for q, r in enumerate(rows):
+                b, ls = out[off[i] + q], l2[off[i] + q]
+                if b["kind"] == F.BEST_NONE:
+                    ended += 1
+                    assert r.depth == 0 and r.best_move is None and not r.lines
+                    continue
+                want = want_score(int(b["kind"]), int(b["value"]))
+                assert (r.score, r.depth, r.nodes, r.best_move, r.psqt, r.positional) == \
+                    (want, int(b["pv_len"]), int(b["nodes"]), uci(b["move"]), int(b["psqt"]), int(b["positional"]))
+                legal = ls[ls["kind"] != F.BEST_NONE]
+                assert 1 <= len(legal) <= K
+                assert [(l.score, tuple(l.pv), l.psqt, l.positional) for l in r.lines] == \
+                    [(want_score(int(l["kind"]), int(l["value"])),
+                      (uci(l["move"]),) + ((uci(l["reply"]),) if int(l["pv_len"]) == 2 else ()),
+                      int(l["psqt"]), int(l["positional"])) for l in legal]
+        assert ended == 2   # the mated and the stalemated last plies
+    finally:
+        actor.close()
+        e.close()
+
+
 def test_actor_with_quiescence_checks_matches_the_library(data, ce):
     made = [make_channel(data, quiesce=1, quiesce_checks=True, analysis_depth=1),
             make_channel(data, quiesce=1, quiesce_checks=True, analysis_plies=2),
