@@ -63,14 +63,21 @@ __global__ __launch_bounds__(1024) void plan_count_kernel(const fnnue_pos* __res
 // (slot < 2^20: chunk_for_hd).
 // One lane per position; the workgroup's 256 positions get local ranks from
 // LDS atomics, then reserve one range per bin with a single global atomic.
-__global__ __launch_bounds__(kScatterPositions) void plan_scatter_kernel(const fnnue_pos* __restrict__ pos, uint32_t n,
+// Both lists of a position come from one walk over its board (plan_lists.h).
+// The walk needs no item index, so it runs between the range reservations
+// (global atomics on 1065 contended words) and the first use of what they
+// return.  The list building is a serial chain per piece and hides its
+// latencies only with every wave slot filled: 78 KB of LDS and at most 64
+// VGPRs (waves_per_eu 8) keep two workgroups, 8 waves per SIMD, on a CU.
+__global__ __launch_bounds__(kScatterPositions) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void plan_scatter_kernel(const fnnue_pos* __restrict__ pos, uint32_t n,
                                                            uint32_t* __restrict__ ctr, uint32_t* __restrict__ items,
                                                            uint16_t* __restrict__ flist, uint32_t* __restrict__ perm,
                                                            uint8_t* __restrict__ bucket_out,
                                                            int32_t* __restrict__ psqt_out) {
   __shared__ uint32_t lcnt[kBins];
   __shared__ uint32_t lbase[kBins];
-  __shared__ uint32_t lists[kScatterPositions * kListStrideWords];  // write_rows staging, one row per lane
+  __shared__ uint32_t lists[kScatterPositions * kListStrideWords];  // list staging, one row per lane
   for (int i = threadIdx.x; i < kBins; i += blockDim.x) lcnt[i] = 0;
   __syncthreads();
   const uint32_t p = blockIdx.x * kScatterPositions + threadIdx.x;
@@ -78,9 +85,11 @@ __global__ __launch_bounds__(kScatterPositions) void plan_scatter_kernel(const f
   LaneBoard b;
   int kw = 0, kb = 0, kp = kItemBins + 8;
   uint32_t rw = 0, rb = 0, rp = 0;
+  bool ok = false;  // a position that gets lists
   if (live) {
     b = lane_decode(pos + p);
-    if (b.ok) {
+    ok = b.ok;
+    if (ok) {
       kw = king_block(0, b.wk) * 33 + b.cnt;
       kb = king_block(1, b.bk) * 33 + b.cnt;
       kp = kItemBins + ((b.cnt - 1) >> 2);
@@ -90,22 +99,39 @@ __global__ __launch_bounds__(kScatterPositions) void plan_scatter_kernel(const f
     rp = atomicAdd(&lcnt[kp], 1u);
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < kBins; i += blockDim.x)
-    lbase[i] = lcnt[i] ? atomicAdd(&ctr[kCur + i], lcnt[i]) : 0;
+  constexpr int kBinsPerLane = (kBins + kScatterPositions - 1) / kScatterPositions;
+  uint32_t base[kBinsPerLane];
+#pragma unroll
+  for (int k = 0; k < kBinsPerLane; ++k) {
+    const int i = threadIdx.x + k * kScatterPositions;
+    const uint32_t c = i < kBins ? lcnt[i] : 0;
+    base[k] = c ? atomicAdd(&ctr[kCur + i], c) : 0;
+  }
+  uint32_t* mine = lists + threadIdx.x * kListStrideWords;
+  ListWalk walk{};
+  uint32_t firstw = 0, firstb = 0;  // first items of the two king blocks
+  if (ok) {
+    firstw = ctr[kOff + king_block(0, b.wk) * 33];
+    firstb = ctr[kOff + king_block(1, b.bk) * 33];
+    walk = walk_board(b.w, b.occ, b.wk, b.bk, mine);
+  }
+#pragma unroll
+  for (int k = 0; k < kBinsPerLane; ++k) {
+    const int i = threadIdx.x + k * kScatterPositions;
+    if (i < kBins) lbase[i] = base[k];
+  }
   __syncthreads();
   if (!live) return;
   const uint32_t slot = lbase[kp] + rp;
   perm[slot] = p;
-  if (!b.ok) {
+  if (!ok) {
     bucket_out[slot] = 0xFF;
     psqt_out[p] = 0;
     return;
   }
   const int bucket = (b.cnt - 1) >> 2;
   const uint32_t iw = lbase[kw] + rw, ib = lbase[kb] + rb;
-  uint32_t* mine = lists + threadIdx.x * kListStrideWords;
-  write_rows(b, 0, b.wk, iw, (iw - ctr[kOff + king_block(0, b.wk) * 33]) & 1u, mine, flist);
-  write_rows(b, 1, b.bk, ib, (ib - ctr[kOff + king_block(1, b.bk) * 33]) & 1u, mine, flist);
+  emit_list_pair(walk, b.wk, b.bk, iw, (iw - firstw) & 1u, ib, (ib - firstb) & 1u, mine, flist);
   items[iw] = ((uint32_t)b.cnt << 24) | ((uint32_t)bucket << 21) | (slot << 1) | (uint32_t)(b.stm != 0);
   items[ib] = ((uint32_t)b.cnt << 24) | ((uint32_t)bucket << 21) | (slot << 1) | (uint32_t)(b.stm != 1);
   bucket_out[slot] = (uint8_t)bucket;

@@ -8,6 +8,7 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "net.h"
+#include "plan_lists.h"
 #include "psqt_tile.h"
 #include "slice_units.h"
 
@@ -420,6 +421,10 @@ __host__ __device__ constexpr uint64_t plane_table(int persp) {
   }
   return t;
 }
+// plan_lists.h (build_list_pair: both lists of a position from one walk) states
+// the same layout for the host
+static_assert(kListNoEntry == kNoEntry && kListRows == kRowsPerBlock, "plan_lists.h: the zero row");
+static_assert((plane_table(0) & 0xF0FFFFFFF0FFFFFFull) == white_plane_table(), "plan_lists.h: white's planes, kings aside");
 
 // Writes item `it`'s 32 feature-list entries (rows relative to its king block,
 // padded with the zero row): every piece except the perspective's own king,

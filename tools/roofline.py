@@ -48,7 +48,7 @@ def tree_hash() -> str:
     """sha256 over the sources of the evaluation kernels (what their counters depend on)."""
     h = hashlib.sha256()
     src = os.path.join(ROOT, "fishnet_amd", "csrc")
-    files = ("kernels.hip", "ft_sliced.hip", "ft_segments.hip", "device_common.h", "sliced_common.h", "kernels.h",
+    files = ("kernels.hip", "ft_sliced.hip", "ft_segments.hip", "device_common.h", "sliced_common.h", "plan_lists.h", "kernels.h",
              # the engine actor's replay (backend:<k> workloads)
              "builder.hip", "vbuilder.hip", "replay_wave.h", "board.h", "vboard.h")
     for f in sorted(os.path.join(src, f) for f in files):
