@@ -233,6 +233,16 @@ SIGNATURES = {
     "fnnue_game_quiet_moves": ([C.c_char_p, C.c_char_p, _vp, _sz, _vp, _P(_i32), _P(_sz)], _i32),
     "fnnue_backend_set_quiesce_checks": ([_vp, _i32], _i32),
     "fnnue_backend_quiesce_checks": ([_vp, _P(_i32)], _i32),
+    # capture quiescence for the variant searches (ABI 3.15)
+    "fnnue_game_vquiet_moves": ([_i32, C.c_char_p, C.c_char_p, _i32, _vp, _sz, _vp, _P(_i32), _P(_sz)], _i32),
+    "fnnue_vquiesce_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _u32, _i32, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp],
+                              _i32),
+    "fnnue_vquiesce": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _u32, _i32, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)],
+                       _i32),
+    "fnnue_set_search_vquiesce": ([_vp, _i32, _i32], _i32),
+    "fnnue_get_search_vquiesce": ([_vp, _P(_i32), _P(_i32)], _i32),
+    "fnnue_backend_set_variant_quiesce": ([_vp, _i32, _i32], _i32),
+    "fnnue_backend_variant_quiesce": ([_vp, _P(_i32), _P(_i32)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

@@ -376,6 +376,17 @@ class GpuEvalStub:
         N.check(N.lib.fnnue_backend_quiesce_checks(self._actor._h, C.byref(on)))
         return bool(on.value)
 
+    def set_variant_quiesce(self, depth: int, checks: bool = False) -> None:
+        """fnnue_backend_set_variant_quiesce: variant analysis batches at 1 or 2 plies resolve captures below their
+        leaves under the variant's rule, `depth` deep at most (0: off); `checks`: evasions and mates inside it.
+        With a depth set, coded mates are answered as Score::Mate."""
+        N.check(N.lib.fnnue_backend_set_variant_quiesce(self._actor._h, int(depth), 1 if checks else 0))
+
+    def variant_quiesce(self) -> tuple[int, bool]:
+        d, on = C.c_int(), C.c_int()
+        N.check(N.lib.fnnue_backend_variant_quiesce(self._actor._h, C.byref(d), C.byref(on)))
+        return d.value, bool(on.value)
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -407,7 +418,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
             analysis_plies: int | None = None,
             variant_analysis_plies: int | None = None,
             draw_rules: bool = False, quiesce: int = 0,
-            quiesce_checks: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
+            quiesce_checks: bool = False, variant_quiesce: int = 0,
+            variant_quiesce_checks: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -420,7 +432,9 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     `variant_analysis_depth`); `draw_rules`: repetition and fifty-move draws in the chess searches
     (GpuEvalStub.set_draw_rules; off by default); `quiesce`: the capture quiescence depth below the chess
     searches' leaves (GpuEvalStub.set_quiesce; 0 by default); `quiesce_checks`: check evasions and mates inside
-    that quiescence (GpuEvalStub.set_quiesce_checks; off by default)."""
+    that quiescence (GpuEvalStub.set_quiesce_checks; off by default); `variant_quiesce` /
+    `variant_quiesce_checks`: the same for the variant nets' batches under the variants' rule
+    (GpuEvalStub.set_variant_quiesce; 0 / off by default)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -449,6 +463,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_quiesce(quiesce)
     if quiesce_checks:
         stub.set_quiesce_checks(True)
+    if variant_quiesce or variant_quiesce_checks:
+        stub.set_variant_quiesce(variant_quiesce, variant_quiesce_checks)
     return stub, actor
 
 

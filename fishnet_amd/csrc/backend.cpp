@@ -522,6 +522,10 @@ struct fnnue_backend {
   bool draw_rules = false;  // fnnue_backend_set_draw_rules: repetition and fifty-move draws in the chess searches
   int quiesce = 0;  // fnnue_backend_set_quiesce: capture quiescence depth below the chess searches' leaves
   bool quiesce_checks = false;  // fnnue_backend_set_quiesce_checks: evasions and mates inside it, coded mates answered
+  // fnnue_backend_set_variant_quiesce: the same below the variant searches' leaves, with the variants' rule
+  // (decided values exist with checks off too: coded mates are answered whenever the depth is set)
+  int vquiesce = 0;
+  bool vquiesce_checks = false;
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
   int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
@@ -994,7 +998,7 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   // whole games (plan() never cuts one), so the history of its plies is
   // complete; the marks go on the listed plies' children here and on their
   // grandchildren behind the second expansion, before the reductions.
-  SearchSettings set{nullptr, rules.chess() ? quiesce : 0, quiesce_checks};
+  SearchSettings set{nullptr, rules.chess() ? quiesce : vquiesce, rules.chess() ? quiesce_checks : vquiesce_checks};
   DrawHistory hist;
   if (rules.chess() && draw_rules) {
     if (int rc = draw_history_level1(dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
@@ -1046,7 +1050,7 @@ int fnnue_backend::stage_search(int k, size_t pi) {
               "topk_replies launch");
   } else {
     // One ply: the reduction into the results image, and the lines of a go_lines() call that asked for MultiPV
-    if (int rc = reduce_level1(c, W.bscratch, set, g, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
+    if (int rc = reduce_level1(c, W.bscratch, rules, set, g, reinterpret_cast<fnnue_best*>(dimg + P.o_best),
                                reinterpret_cast<const uint32_t*>(dimg + P.o_loff), 0,
                                P.nslots ? reinterpret_cast<fnnue_line*>(dimg + P.o_lines) : nullptr, P.nslots, s, &qs))
       return rc;
@@ -1199,8 +1203,9 @@ void fnnue_backend::fill(Job& j, int k, const Piece& P) {
   const uint32_t nps = el > 0 ? (uint32_t)std::min(4.0e9, (double)filled / (el * 1e-3)) : 0;
   const int32_t nrm = norm;
   const ResponseTail tail(ms, nps);
-  // coded mates: chess searches with quiescence checks only; otherwise no value is ever remapped
-  const ScoreRule rule{nrm, k == kVariantChess && quiesce_checks && quiesce > 0};
+  // coded mates: chess searches with quiescence checks, variant searches with a quiescence depth (the variants'
+  // rule decides finished positions with checks off too); otherwise no value is ever remapped
+  const ScoreRule rule{nrm, k == kVariantChess ? quiesce_checks && quiesce > 0 : vquiesce > 0};
   pool.run(P.ng, fill_grain, [&](size_t lo, size_t hi) {
     for (size_t g = lo; g < hi; ++g) {
       const size_t i = P.games[g];
@@ -1989,6 +1994,24 @@ int fnnue_backend_quiesce_checks(fnnue_backend* b, int* on) {
   if (!b || !on) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->run_mu);
   *on = b->quiesce_checks ? 1 : 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_variant_quiesce(fnnue_backend* b, int depth, int checks) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  if (depth < 0 || depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->vquiesce = depth;
+  b->vquiesce_checks = checks != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_variant_quiesce(fnnue_backend* b, int* depth, int* checks) {
+  if (!b || !depth || !checks) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);
+  *depth = b->vquiesce;
+  *checks = b->vquiesce_checks ? 1 : 0;
   return FNNUE_OK;
 }
 

@@ -153,12 +153,13 @@ hipError_t ply_spans_device(const uint32_t* d_off, const uint32_t* d_kid_off, ui
 // d_dst[i] = d_src[i] - d_src[0], i < n: a chunk's offsets from the whole array's.
 hipError_t rebase_offsets_device(const uint32_t* d_src, uint32_t n, uint32_t* d_dst, hipStream_t s);
 
-// The replay alone, into the scratch: every ply's board (kStates) and the games'
-// ply offsets (kPlyOff, ngames + 1).  More than max_plies plies: capacity, with
+// The replay alone, into the scratch: every ply's board (kStates: DBoard for
+// kVariantChess, vstate_bytes(variant) each for a variant) and the games' ply
+// offsets (kPlyOff, ngames + 1).  More than max_plies plies: capacity, with
 // n_out = the plies, before any is replayed.  Synchronises `s` (sizes, errors).
-BuildResult replay_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+BuildResult replay_states_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                  uint32_t ngames, size_t max_plies, hipStream_t s, BuilderScratch& ws,
-                                 const DBoard** d_states, const uint32_t** d_ply_off);
+                                 const void** d_states, const uint32_t** d_ply_off);
 
 // ---- draws.hip: repetition and fifty-move draws (include/fnnue.h, ABI 3.12) ----
 // The history of n plies (d_states: the replay's boards, d_ply_off: ngames + 1)

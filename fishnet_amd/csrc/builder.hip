@@ -457,9 +457,9 @@ BuildResult build_batch_device(const char* d_text, const uint32_t* d_fen_off, co
   return R;
 }
 
-BuildResult replay_states_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+BuildResult replay_states_device(int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                                  uint32_t ngames, size_t max_plies, hipStream_t s, BuilderScratch& ws,
-                                 const DBoard** d_states, const uint32_t** d_ply_off) {
+                                 const void** d_states, const uint32_t** d_ply_off) {
   BuildResult R;
   auto fail = [&](hipError_t e) {
     R.hip = e;
@@ -467,7 +467,8 @@ BuildResult replay_states_device(const char* d_text, const uint32_t* d_fen_off, 
   };
   hipError_t e;
   uint32_t *plies = nullptr, *ply_off = nullptr, *err = nullptr;
-  DBoard* states = nullptr;
+  void* states = nullptr;
+  const size_t state_bytes = variant == kVariantChess ? sizeof(DBoard) : vstate_bytes(variant);
   using W = BuilderScratch;
   if ((e = ws.get(W::kPlies, (size_t)(ngames + 1) * 4, (void**)&plies)) != hipSuccess) return fail(e);
   if ((e = ws.get(W::kPlyOff, (size_t)(ngames + 1) * 4, (void**)&ply_off)) != hipSuccess) return fail(e);
@@ -488,10 +489,12 @@ BuildResult replay_states_device(const char* d_text, const uint32_t* d_fen_off, 
     R.capacity = true;
     return R;
   }
-  if ((e = ws.get(W::kStates, (size_t)total_plies * sizeof(DBoard), (void**)&states)) != hipSuccess) return fail(e);
-  if ((e = launch_chess_replay(d_text, d_fen_off, d_mv_off, ply_off, ngames, nullptr, states, nullptr, err, s)) !=
-      hipSuccess)
-    return fail(e);
+  if ((e = ws.get(W::kStates, (size_t)total_plies * state_bytes, &states)) != hipSuccess) return fail(e);
+  e = variant == kVariantChess
+          ? launch_chess_replay(d_text, d_fen_off, d_mv_off, ply_off, ngames, nullptr, static_cast<DBoard*>(states),
+                                nullptr, err, s)
+          : replay_vgames_device(variant, d_text, d_fen_off, d_mv_off, ply_off, ngames, nullptr, states, nullptr, err, s);
+  if (e != hipSuccess) return fail(e);
   uint32_t herr[4];
   if ((e = hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);

@@ -384,7 +384,10 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.14: check evasions and mates inside the quiescence: FNNUE_VALUE_MATE, FNNUE_QUIET_DECIDED,
 //       fnnue_set_search_quiesce_checks / fnnue_get_search_quiesce_checks, fnnue_game_quiet_moves,
 //       fnnue_backend_set_quiesce_checks / fnnue_backend_quiesce_checks
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 14u; }
+// 3.15: capture quiescence for the variant searches: fnnue_vquiesce[_device], fnnue_game_vquiet_moves and the
+//       FNNUE_VQ_* states, fnnue_set_search_vquiesce / fnnue_get_search_vquiesce,
+//       fnnue_backend_set_variant_quiesce / fnnue_backend_variant_quiesce
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 15u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");

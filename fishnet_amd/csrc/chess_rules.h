@@ -316,6 +316,77 @@ __device__ void for_each_legal(const DBoard& b, F&& f, uint64_t from_mask = ~0ul
   }
 }
 
+// ---- the plain variants' capture quiescence (include/fnnue.h, ABI 3.15) ----
+// vboard.h's over_state on a DBoard: 0 while the game goes on, else
+// FNNUE_VQ_LOST (no king, a king on the hill, the other side's counter at 0,
+// the other king alone on rank 8), FNNUE_VQ_WON (the own counter at 0, the own
+// king alone on rank 8) or FNNUE_VQ_DRAWN (both kings on rank 8).
+template <int V>
+__device__ __forceinline__ int plain_over_state(const DBoard& b) {
+  if (king_sq(b, b.stm) < 0) return FNNUE_VQ_LOST;
+  if (!plain_over<V>(b)) return 0;
+  if constexpr (V == kVariantThreeCheck) {
+    return ((uint32_t)b.bt[0] >> (8 * (b.stm ^ 1))) & 0xFFu ? FNNUE_VQ_WON : FNNUE_VQ_LOST;
+  } else if constexpr (V == kVariantRacingKings) {
+    const uint64_t goal = b.bt[KING] & 0xFF00000000000000ull;
+    if (!(goal & colour(b, b.stm))) return FNNUE_VQ_LOST;
+    return (goal & colour(b, b.stm ^ 1)) ? FNNUE_VQ_DRAWN : FNNUE_VQ_WON;
+  } else {
+    return FNNUE_VQ_LOST;
+  }
+}
+// chk(X) of variant V: no racingkings position is in check.
+template <int V>
+__device__ __forceinline__ bool plain_quiet_check(const DBoard& b) {
+  if constexpr (V == kVariantRacingKings) return false;
+  else return in_check(b);
+}
+
+// The legal captures of b under variant V's rules, in for_each_legal<V>'s
+// order restricted to captures: own pieces by square; a pawn's captures by
+// square (promotions Q, R, B, N), then en passant with an opponent's piece
+// behind the square.  Castling and pushes take nothing; a finished position
+// has no move.  f(move) returns false to stop early.
+template <int V, class F>
+__device__ void for_each_capture(const DBoard& b, F&& f) {
+  if (plain_over<V>(b)) return;
+  const int us = b.stm, them = us ^ 1;
+  const uint64_t occ = b.bc[0] | b.bc[1], own = colour(b, us), opp = colour(b, them);
+  const int rank7 = us == WHITE ? 6 : 1, down = us == WHITE ? -8 : 8;
+  auto emit = [&](int from, int to, int promo) -> bool {
+    const DMove m{from, to, promo, 0};
+    return !legal<V>(b, m) || f(m);
+  };
+  for (uint64_t pcs = own; pcs; pcs &= pcs - 1) {
+    const int s = lsb(pcs);
+    const uint64_t sm = 1ull << s;
+    if (b.bt[PAWN] & sm) {
+      const bool promo = (s >> 3) == rank7;
+      for (uint64_t a = pawn_att(us, s) & opp; a; a &= a - 1) {
+        const int t = lsb(a);
+        if (promo) {
+          for (int p = QUEEN; p >= KNIGHT; --p)
+            if (!emit(s, t, p)) return;
+        } else if (!emit(s, t, 0)) {
+          return;
+        }
+      }
+      if (b.ep >= 0 && b.ep < 64 && (pawn_att(us, s) & (1ull << b.ep)) && !(occ & (1ull << b.ep)) &&
+          b.ep + down >= 0 && b.ep + down < 64 && (opp & (1ull << (b.ep + down))) && !emit(s, b.ep, 0))
+        return;
+      continue;
+    }
+    uint64_t targets;
+    if (b.bt[KNIGHT] & sm) targets = knight_att(s);
+    else if (b.bt[BISHOP] & sm) targets = bishop_att(s, occ);
+    else if (b.bt[ROOK] & sm) targets = rook_att(s, occ);
+    else if (b.bt[QUEEN] & sm) targets = bishop_att(s, occ) | rook_att(s, occ);
+    else targets = king_att(s);
+    for (uint64_t t = targets & opp; t; t &= t - 1)
+      if (!emit(s, lsb(t), 0)) return;
+  }
+}
+
 // Is m one of Board::pseudo_moves' moves?  (The set the host builder matches
 // UCI tokens against, before the legality filter.)
 __device__ __forceinline__ bool pseudo_member(const DBoard& b, const DMove& m) {

@@ -45,6 +45,8 @@ struct fnnue_ctx {
   bool search_draws = false;   // fnnue_set_search_draws: repetition and fifty-move draws in fnnue_search1 / 2
   int search_quiesce = 0;      // fnnue_set_search_quiesce: capture quiescence depth below the searches' leaves
   bool search_quiesce_checks = false;  // fnnue_set_search_quiesce_checks: evasions and mates inside that tree
+  int search_vquiesce = 0;     // fnnue_set_search_vquiesce: the variant searches' quiescence depth and its checks
+  bool search_vquiesce_checks = false;
   uint64_t quiesce_slices = 0; // slices of root frontiers quiesce.hip has worked through (fnnue_quiesce_slices)
   int32_t acc_bound = 0;       // accumulator_bound of the net (the largest slice bound)
   uint64_t swar_eligible = 0;  // bit s: slice s's bound < 2^15, SWAR rows allowed (plan.swar: the enabled ones)
@@ -156,23 +158,3 @@ int eval_vpositions_at(fnnue_ctx* ctx, const fnnue_vpos* pos, size_t n, int32_t*
 int game_end_chess(const char* fen, const char* moves, int* flags);
 
 }  // namespace fnnue::detail
-
-namespace fnnue {
-
-// quiesce.hip.  The search's form: the leaves are the records j >= 1 of the n
-// parents' STAR groups (d_off: n + 1, total = d_off[n]; d_parents: the groups'
-// first records' boards); every leaf whose end byte has neither kFinalNoMoves
-// nor kFinalDraw gets its two terms replaced in place by the reported terms of
-// Q_depth.  Runs behind the groups' evaluation on `s`, reads each level's size
-// back (synchronises `s`), evaluates through ctx, temporaries from ws.
-// checks: the rule Q'_depth (ABI 3.14); a decided leaf then gets (0, 16 * v) with
-// v `ply` further from the mate value (the leaves' depth in the search, 1 or 2).
-int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_parents, uint32_t n,
-                          const uint32_t* d_off, uint32_t total, const uint8_t* d_end, int32_t* d_psqt,
-                          int32_t* d_positional, int depth, bool checks, int ply, hipStream_t s, QuiesceStats* st);
-// fnnue_quiesce_device's form: the n boards themselves are the roots, one
-// fnnue_quiet each (their own evaluation included).
-int quiesce_nodes_device(fnnue_ctx* ctx, BuilderScratch& ws, const DBoard* d_states, uint32_t n, int depth,
-                         bool checks, fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st);
-
-}  // namespace fnnue

@@ -165,11 +165,11 @@ int build_children_host(fnnue_ctx* ctx, const char* text, size_t text_len, const
   return FNNUE_OK;
 }
 
-// What fnnue_quiesce_device and fnnue_game_history_device share: the games'
+// What fnnue_[v]quiesce_device and fnnue_game_history_device share: the games'
 // plies replayed into the context's scratch (ordered like its workspace),
 // body(boards, plies, ply_off, s) over them, then the games' offsets to d_off.
 template <class Body>
-int replayed_plies(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
+int replayed_plies(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_moves_off,
                    size_t ngames, size_t room, uint32_t* d_off, size_t* n_out, size_t* n_groups, void* stream,
                    Body body) {
   if (ngames == 0) return FNNUE_OK;
@@ -180,11 +180,12 @@ int replayed_plies(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off
   int rc = order_workspace(ctx, s);
   if (rc) return rc;
   WorkspaceUse use{ctx, s};
-  const DBoard* states = nullptr;
+  const void* states = nullptr;
   const uint32_t* ply_off = nullptr;
-  const BuildResult R = replay_states_device(d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s, ctx->bscratch,
-                                             &states, &ply_off);
-  if ((rc = builder_result(R, false, n_out, n_groups)) || (rc = body(states, R.n_out, ply_off, s))) return rc;
+  const BuildResult R = replay_states_device(variant, d_text, d_fen_off, d_moves_off, (uint32_t)ngames, room, s,
+                                             ctx->bscratch, &states, &ply_off);
+  if ((rc = builder_result(R, variant != kVariantChess, n_out, n_groups)) || (rc = body(states, R.n_out, ply_off, s)))
+    return rc;
   HIP_TRY(hipMemcpyAsync(d_off, ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
   return FNNUE_OK;
 }
@@ -405,7 +406,8 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
   HIP_TRY(ws.get(BuilderScratch::kKidPsqt, nrec * 4, (void**)&ps), "device allocation (search scratch)");
   HIP_TRY(ws.get(BuilderScratch::kKidPositional, nrec * 4, (void**)&po), "device allocation (search scratch)");
   if ((rc = eval_groups(rules, ctx, kids.pos, kids.off, nply, nrec, FNNUE_GROUP_STAR, ps, po, s))) return rc;
-  SearchSettings set{nullptr, rules.chess() ? ctx->search_quiesce : 0, ctx->search_quiesce_checks};
+  SearchSettings set{nullptr, rules.chess() ? ctx->search_quiesce : ctx->search_vquiesce,
+                     rules.chess() ? ctx->search_quiesce_checks : ctx->search_vquiesce_checks};
   if (set.quiesce > 0 && nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
   const StarGroups l1{ws.p[BuilderScratch::kStates], (uint32_t)nply, kids.off, (uint32_t)nrec, kids.moves, kids.end, ps, po};
   DrawHistory hist;
@@ -415,7 +417,7 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
       return rc;
     set.draws = &hist;
   }
-  if ((rc = reduce_level1(ctx, ws, set, l1, d_out, nullptr, k, k ? d_lines : nullptr, lines_cap, s, nullptr))) return rc;
+  if ((rc = reduce_level1(ctx, ws, rules, set, l1, d_out, nullptr, k, k ? d_lines : nullptr, lines_cap, s, nullptr))) return rc;
   HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
   return FNNUE_OK;
 }
@@ -802,7 +804,8 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
   }
   // The draw rules (chess, fnnue_set_search_draws): the plies' history and the
   // marks on the listed plies' children here, their grandchildren per chunk.
-  SearchSettings set{nullptr, rules.chess() ? ctx->search_quiesce : 0, ctx->search_quiesce_checks};
+  SearchSettings set{nullptr, rules.chess() ? ctx->search_quiesce : ctx->search_vquiesce,
+                     rules.chess() ? ctx->search_quiesce_checks : ctx->search_vquiesce_checks};
   DrawHistory hist;
   if (rules.chess() && ctx->search_draws) {
     if ((rc = draw_history_level1(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, l1.states, l1.n,
@@ -1156,11 +1159,11 @@ int fnnue_quiesce_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_f
     return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
   if (ctx->variant != kVariantChess) return fail(FNNUE_E_ARCH, "quiescence needs a chess net");
   const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  return replayed_plies(ctx, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
-                        [&](const DBoard* states, size_t n, const uint32_t*, hipStream_t s) {
+  return replayed_plies(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
+                        [&](const void* states, size_t n, const uint32_t*, hipStream_t s) {
                           if (n > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
-                          return quiesce_nodes_device(ctx, ctx->bscratch, states, (uint32_t)n, (int)depth,
-                                                      ctx->search_quiesce_checks, d_out, s, nullptr);
+                          return quiesce_nodes_device(ctx, ctx->bscratch, SearchRules{}, states, (uint32_t)n,
+                                                      (int)depth, ctx->search_quiesce_checks, d_out, s, nullptr);
                         });
 }
 
@@ -1181,6 +1184,58 @@ int fnnue_quiesce(fnnue_ctx* ctx, const char* text, size_t text_len, const uint3
                     });
 }
 
+// ---- the variants' capture quiescence (ABI 3.15) ----
+int fnnue_set_search_vquiesce(fnnue_ctx* ctx, int depth, int checks) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  if (depth < 0 || depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  ctx->search_vquiesce = depth;
+  ctx->search_vquiesce_checks = checks != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_get_search_vquiesce(const fnnue_ctx* ctx, int* depth, int* checks) {
+  if (!ctx || !depth || !checks) return fail(FNNUE_E_ARG, "null argument");
+  *depth = ctx->search_vquiesce;
+  *checks = ctx->search_vquiesce_checks ? 1 : 0;
+  return FNNUE_OK;
+}
+
+int fnnue_vquiesce_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                          const uint32_t* d_moves_off, size_t ngames, uint32_t depth, int checks, fnnue_quiet* d_out,
+                          size_t cap, uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  if (variant == kVariantChess) return fail(FNNUE_E_ARCH, "the variants' quiescence needs a variant");
+  if (int rc = search1_arch(ctx, variant)) return rc;
+  const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
+  return replayed_plies(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
+                        [&](const void* states, size_t n, const uint32_t*, hipStream_t s) {
+                          if (n > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
+                          return quiesce_nodes_device(ctx, ctx->bscratch, SearchRules{variant}, states, (uint32_t)n,
+                                                      (int)depth, checks != 0, d_out, s, nullptr);
+                        });
+}
+
+int fnnue_vquiesce(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                   const uint32_t* moves_off, size_t ngames, uint32_t depth, int checks, fnnue_quiet* out, size_t cap,
+                   uint32_t* off, size_t off_cap, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (depth > FNNUE_QUIESCE_MAX)
+    return fail(FNNUE_E_ARG, "quiescence depth must be 0.." + std::to_string(FNNUE_QUIESCE_MAX));
+  if (variant == kVariantChess) return fail(FNNUE_E_ARCH, "the variants' quiescence needs a variant");
+  if (int rc = search1_arch(ctx, variant)) return rc;
+  if (ngames == 0) return FNNUE_OK;
+  return plies_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, n_out, true,
+                    [&](const StagedGames& d, hipStream_t s, auto... outputs) {
+                      return fnnue_vquiesce_device(ctx, variant, d.text, d.fen_off, d.moves_off, ngames, depth, checks,
+                                                   outputs..., n_out, n_groups, s);
+                    });
+}
 
 }  // extern "C"
 
@@ -1205,11 +1260,12 @@ int fnnue_game_history_device(fnnue_ctx* ctx, const char* d_text, const uint32_t
   if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
   *n_out = *n_groups = 0;
   const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  return replayed_plies(ctx, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
-                        [&](const DBoard* states, size_t n, const uint32_t* ply_off, hipStream_t s) {
+  return replayed_plies(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
+                        [&](const void* states, size_t n, const uint32_t* ply_off, hipStream_t s) {
                           DrawHistory hist;
-                          HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, ply_off, (uint32_t)ngames, states,
-                                                      (uint32_t)n, draw_key_bits(), s, ctx->bscratch, &hist),
+                          HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, ply_off, (uint32_t)ngames,
+                                                      static_cast<const DBoard*>(states), (uint32_t)n, draw_key_bits(),
+                                                      s, ctx->bscratch, &hist),
                                   "game history launch");
                           HIP_TRY(hipMemcpyAsync(d_out, hist.hist, n * sizeof(fnnue_ply_history),
                                                  hipMemcpyDeviceToDevice, s),

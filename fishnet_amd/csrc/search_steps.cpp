@@ -62,12 +62,12 @@ int draw_history_level1(const char* d_text, const uint32_t* d_fen_off, const uin
   return FNNUE_OK;
 }
 
-int reduce_level1(fnnue_ctx* ctx, BuilderScratch& ws, const SearchSettings& set, const StarGroups& g,
+int reduce_level1(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const SearchSettings& set, const StarGroups& g,
                   fnnue_best* d_out, const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line* d_lines,
                   size_t lines_cap, hipStream_t s, QuiesceStats* qs) {
   if (set.quiesce > 0) {  // the children's terms become those of their capture lines' ends, before any reduction
-    if (int rc = quiesce_leaves_device(ctx, ws, static_cast<const DBoard*>(g.states), g.n, g.off, g.total, g.end,
-                                       g.psqt, g.positional, set.quiesce, set.quiesce_checks, 1, s, qs))
+    if (int rc = quiesce_leaves_device(ctx, ws, r, g.states, g.n, g.off, g.total, g.end, g.psqt, g.positional,
+                                       set.quiesce, set.quiesce_checks, 1, s, qs))
       return rc;
   }
   HIP_TRY(launch_best_children(g.psqt, g.positional, g.end, g.moves, g.off, g.n, g.total, d_out, s),
@@ -95,8 +95,8 @@ int search_level2_chunk(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const
   if (int rc = eval_groups(r, ctx, c.pos, c.ch_off, c.nk, c.nr, FNNUE_GROUP_STAR, c.psqt, c.positional, s)) return rc;
   if (set.quiesce > 0) {  // the grandchildren's terms become those of their capture lines' ends
     begin_phase(hook, kPhaseQuiesce);
-    if (int rc = quiesce_leaves_device(ctx, ws, reinterpret_cast<const DBoard*>(chunk_states), c.nk, c.ch_off, c.nr,
-                                       c.end, c.psqt, c.positional, set.quiesce, set.quiesce_checks, 2, s, qs))
+    if (int rc = quiesce_leaves_device(ctx, ws, r, chunk_states, c.nk, c.ch_off, c.nr, c.end, c.psqt, c.positional,
+                                       set.quiesce, set.quiesce_checks, 2, s, qs))
       return rc;
   }
   begin_phase(hook, kPhaseReduce1);

@@ -38,12 +38,31 @@ hipError_t topk_replies(bool vranks, const uint8_t* d_end, const uint16_t* d_mov
                         const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line2* d_lines, size_t lines_cap,
                         hipStream_t s);
 
-// A caller's copy of its search settings (chess only: a variant caller leaves them off).
+// A caller's copy of its search settings: the draws are chess's alone, the quiescence the
+// caller's setting for the rules it searches under (a chess one or a variant one).
 struct SearchSettings {
   const DrawHistory* draws = nullptr;  // the plies' history (draw_history_level1), or none
   int quiesce = 0;                     // capture quiescence depth below the leaves
   bool quiesce_checks = false;         // evasions and mates inside that tree
 };
+
+// quiesce.hip.  The search's form: the leaves are the records j >= 1 of the n
+// parents' STAR groups (d_off: n + 1, total = d_off[n]; d_parents: the groups'
+// first records' boards, r.state_bytes() each); every leaf whose end byte has
+// neither kFinalNoMoves nor kFinalDraw (a variant's kFinalWon children have
+// kFinalNoMoves too) gets its two terms replaced in place by the reported terms
+// of Q_depth.  Runs behind the groups' evaluation on `s`, reads each level's size
+// back (synchronises `s`), evaluates through ctx, temporaries from ws.
+// checks: the rule Q'_depth (ABI 3.14; a variant: chk() of ABI 3.15).  A decided
+// leaf gets (0, 16 * v) with v `ply` further from the mate value (the leaves'
+// depth in the search, 1 or 2), a decided draw (0, 0).
+int quiesce_leaves_device(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const void* d_parents, uint32_t n,
+                          const uint32_t* d_off, uint32_t total, const uint8_t* d_end, int32_t* d_psqt,
+                          int32_t* d_positional, int depth, bool checks, int ply, hipStream_t s, QuiesceStats* st);
+// fnnue_[v]quiesce_device's form: the n boards themselves are the roots, one
+// fnnue_quiet each (their own evaluation included).
+int quiesce_nodes_device(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const void* d_states, uint32_t n, int depth,
+                         bool checks, fnnue_quiet* d_out, hipStream_t s, QuiesceStats* st);
 
 // The phases FNNUE_SEARCH2_TRACE times (search_api.cpp); a step that begins one
 // tells the hook, when there is one.  kSearchPhases: the end of the call.
@@ -82,7 +101,7 @@ struct StarGroups {
 // The end of a one-ply search over evaluated groups: the quiescence of the
 // children's terms (set.quiesce > 0), the reduction into d_out, and with
 // d_lines the k best children (slots: launch_topk_children's).
-int reduce_level1(fnnue_ctx* ctx, BuilderScratch& ws, const SearchSettings& set, const StarGroups& g,
+int reduce_level1(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const SearchSettings& set, const StarGroups& g,
                   fnnue_best* d_out, const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line* d_lines,
                   size_t lines_cap, hipStream_t s, QuiesceStats* qs);
 

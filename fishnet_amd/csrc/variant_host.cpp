@@ -294,6 +294,39 @@ int fnnue_game_end(int variant, const char* fen, const char* moves, int* flags) 
   return FNNUE_OK;
 }
 
+int fnnue_game_vquiet_moves(int variant, const char* fen, const char* moves, int checks, fnnue_vpos* out, size_t cap,
+                            fnnue_move* mv, int* state, size_t* n_out) {
+  if (!fen || !n_out || !state) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = 0;
+  *state = 0;
+  if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  vb::VBoard b{};
+  const int rc = vreplay(variant, fen, moves, [&](const vb::VBoard& x) {
+    b = x;
+    return (int)FNNUE_OK;
+  });
+  if (rc) return rc;
+  std::vector<fnnue_vpos> res{vb::pack(b)};
+  std::vector<fnnue_move> codes{0};
+  const int over = vb::over_state(b);
+  const bool all = !over && checks && vb::quiet_check(b);
+  *state = over | (all ? FNNUE_VQ_CHECK : 0);
+  auto take = [&](const vb::VMove& m) -> bool {
+    vb::VBoard c = b;
+    vb::do_move(c, m);
+    res.push_back(vb::pack(c));
+    codes.push_back(vb::move_code(b, m));
+    return true;
+  };
+  if (all) vb::for_each_legal(b, take);
+  else if (!over) vb::for_each_capture(b, take);
+  *n_out = res.size();
+  if (!out || !mv || cap < res.size()) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  std::memcpy(out, res.data(), res.size() * sizeof(fnnue_vpos));
+  std::memcpy(mv, codes.data(), codes.size() * sizeof(fnnue_move));
+  return FNNUE_OK;
+}
+
 int fnnue_vperft(int variant, const char* fen, int depth, uint64_t* nodes) {
   if (!fen || !nodes || depth < 0) return fail(FNNUE_E_ARG, "bad argument");
   if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));

@@ -490,6 +490,81 @@ __host__ __device__ void for_each_legal(const VBoard& b, F&& f, uint64_t from_ma
   }
 }
 
+// ---- the variants' capture quiescence (include/fnnue.h, ABI 3.15) ----
+// over(X), decided without generating a move: 0 while the game goes on, else
+// FNNUE_VQ_LOST (the side to move has no king, or lost by the variant's rule),
+// FNNUE_VQ_WON or FNNUE_VQ_DRAWN (variant_lost / variant_won's classes).
+FNNUE_HD int over_state(const VBoard& b) {
+  if (king_sq(b, b.stm) < 0) return FNNUE_VQ_LOST;
+  if (!variant_over(b)) return 0;
+  return variant_lost(b) ? FNNUE_VQ_LOST : variant_won(b) ? FNNUE_VQ_WON : FNNUE_VQ_DRAWN;
+}
+// chk(X): the side to move's king in danger by the variant's rule; no
+// racingkings position is in check.
+FNNUE_HD bool quiet_check(const VBoard& b) {
+  if (b.variant == kRacingKings) return false;
+  const int k = king_sq(b, b.stm);
+  return k >= 0 && king_danger(b, k, b.stm, occupied(b));
+}
+
+// vcaps(X): the legal moves (no drop, no castling) whose capture square holds
+// an opponent's piece, in for_each_legal's order: own pieces by square; a
+// pawn's captures by square (promotions Q R B N), then en passant onto an
+// empty square with an opponent's piece behind it.  Atomic kings never
+// capture.  f(move) returns false to stop early.
+template <class F>
+__host__ __device__ void for_each_capture(const VBoard& b, F&& f) {
+  const int us = b.stm, them = us ^ 1;
+  const uint64_t occ = occupied(b), own = colour(b, us), opp = colour(b, them);
+  if (variant_over(b)) return;
+  auto emit = [&](int from, int to, int piece) -> bool {
+    const VMove m{(int8_t)from, (int8_t)to, (int8_t)piece, 0};
+    VBoard c = b;
+    do_move(c, m);
+    return !legal_after(b, c) || f(m);
+  };
+  const int rank7 = us == 0 ? 6 : 1, down = us == 0 ? -8 : 8;
+  for (uint64_t pcs = own; pcs; pcs &= pcs - 1) {
+    const int s = vlsb(pcs);
+    const uint64_t sm = 1ull << s;
+    if (b.bt[PAWN] & sm) {
+      const bool promo = (s >> 3) == rank7;
+      for (uint64_t a = pawn_att(us, s) & opp; a; a &= a - 1) {
+        const int t = vlsb(a);
+        if (promo) {
+          for (int p = QUEEN; p >= KNIGHT; --p)
+            if (!emit(s, t, p)) return;
+        } else if (!emit(s, t, 0)) {
+          return;
+        }
+      }
+      const int behind = b.ep + down;
+      if (b.ep >= 0 && (pawn_att(us, s) & (1ull << b.ep)) && !(occ & (1ull << b.ep)) && behind >= 0 && behind < 64 &&
+          (opp & (1ull << behind)) && !emit(s, b.ep, 0))
+        return;
+      continue;
+    }
+    uint64_t targets;
+    if (b.bt[KNIGHT] & sm) targets = knight_att(s);
+    else if (b.bt[BISHOP] & sm) targets = bishop_att(s, occ);
+    else if (b.bt[ROOK] & sm) targets = rook_att(s, occ);
+    else if (b.bt[QUEEN] & sm) targets = bishop_att(s, occ) | rook_att(s, occ);
+    else targets = b.variant == kAtomic ? 0ull : king_att(s);  // atomic kings never capture
+    for (uint64_t t = targets & opp; t; t &= t - 1)
+      if (!emit(s, vlsb(t), 0)) return;
+  }
+}
+
+// fnnue_vmove_uci's code of m on b (vuci): a drop is from == to with the piece
+// type in the promo field; castling carries the king's two-square step unless
+// the game needs Chess960 notation.
+FNNUE_HD uint16_t move_code(const VBoard& b, const VMove& m) {
+  if (m.kind == 2) return (uint16_t)((uint32_t)m.to | (uint32_t)m.to << 6 | (uint32_t)m.piece << 12);
+  int to = m.to;
+  if (m.kind == 1 && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
+  return (uint16_t)((uint32_t)m.from | (uint32_t)to << 6 | (uint32_t)(m.kind == 0 ? m.piece : 0) << 12);
+}
+
 // Game-end flags of a position (builder.h kFinal*): no legal move (bit 0),
 // the side to move's king attacked (bit 1), its king exploded (bit 2, atomic),
 // the game decided by the variant's own rule (bit 3: kingofthehill,

@@ -553,15 +553,9 @@ __global__ void vwrite_children_kernel(const vb::VBoard* __restrict__ states, ui
 // pockets has several hundred children: one thread per ply would leave a piece
 // of a few thousand plies on a handful of waves).
 
-// fnnue_vmove_uci's code of m on b (vb::vuci): a drop is from == to with the
-// piece type in the promo field; castling carries the king's two-square step
-// unless the game needs Chess960 notation.
-__device__ __forceinline__ uint16_t vmove_code(const vb::VBoard& b, const vb::VMove& m) {
-  if (m.kind == 2) return (uint16_t)((uint32_t)m.to | (uint32_t)m.to << 6 | (uint32_t)m.piece << 12);
-  int to = m.to;
-  if (m.kind == 1 && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
-  return (uint16_t)((uint32_t)m.from | (uint32_t)to << 6 | (uint32_t)(m.kind == 0 ? m.piece : 0) << 12);
-}
+// fnnue_vmove_uci's codes: vb::move_code for the VBoard variants; the plain
+// variants' castling carries the king's two-square step unless the game needs
+// Chess960 notation.
 __device__ __forceinline__ uint16_t pmove_code(const DBoard& b, const DMove& m) {
   int to = m.to;
   if (m.castle && !b.c960) to = (m.from & 56) + (m.to > m.from ? 6 : 2);
@@ -594,7 +588,7 @@ __global__ __launch_bounds__(64) void vwrite_children_record_kernel(
     vb::for_each_legal(b, [&](const vb::VMove& m) -> bool {
       if (++k < j) return true;
       vb::do_move(c, m);
-      mv = vmove_code(b, m);
+      mv = vb::move_code(b, m);
       return false;
     });
   }

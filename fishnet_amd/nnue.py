@@ -586,6 +586,41 @@ class Evaluator:
                                            C.byref(n), C.byref(g), C.c_void_p(stream)))
         return n.value, g.value
 
+    # capture quiescence for the variant searches (ABI 3.15)
+    def set_search_vquiesce(self, depth: int, checks: bool = False) -> None:
+        """fnnue_set_search_vquiesce: the leaves of vsearch1 / vsearch1_lines / vsearch2 / vsearch2_children /
+        vsearch2_lines take the terms of their capture line's end under the variant's rule, `depth` captures
+        deep at most (0: off); `checks`: nodes in check list their evasions (drops included) and may be mated."""
+        N.check(N.lib.fnnue_set_search_vquiesce(self._h, depth, 1 if checks else 0))
+
+    def search_vquiesce(self) -> tuple[int, bool]:
+        d, on = C.c_int(), C.c_int()
+        N.check(N.lib.fnnue_get_search_vquiesce(self._h, C.byref(d), C.byref(on)))
+        return d.value, bool(on.value)
+
+    def vquiesce(self, variant: int, games, depth: int, checks: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_vquiesce: the variant's Q_depth of every ply -> (QUIET_DTYPE records, CHAIN offsets per game)."""
+        text, fen_off, mv_off = pack_games(games)
+        cap = sum(len((m if isinstance(m, str) else " ".join(m)).split()) + 1 for _, m in games)
+        out = np.zeros(max(cap, 1), dtype=QUIET_DTYPE)
+        off = np.zeros(len(games) + 1, dtype=np.uint32)
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vquiesce(self._h, variant, text, len(text), N.ptr(fen_off), N.ptr(mv_off), len(games),
+                                     depth, 1 if checks else 0, N.ptr(out), cap, N.ptr(off), len(off), C.byref(n),
+                                     C.byref(g)))
+        return out[: n.value], off[: g.value + 1]
+
+    def vquiesce_device(self, variant: int, d_text: int, d_fen_off: int, d_moves_off: int, ngames: int, depth: int,
+                        checks: bool, d_out: int, cap: int, d_off: int, off_cap: int,
+                        stream: int | None) -> tuple[int, int]:
+        """fnnue_vquiesce_device -> (plies, games); FnnueError FNNUE_E_CAPACITY when out / off are too small."""
+        n, g = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.fnnue_vquiesce_device(self._h, variant, C.c_void_p(d_text), C.c_void_p(d_fen_off),
+                                            C.c_void_p(d_moves_off), ngames, depth, 1 if checks else 0,
+                                            C.c_void_p(d_out), cap, C.c_void_p(d_off), off_cap, C.byref(n), C.byref(g),
+                                            C.c_void_p(stream)))
+        return n.value, g.value
+
     # the two-ply search (ABI 3.7)
     def best_replies(self, end, moves, off, child_best) -> np.ndarray:
         """fnnue_best_replies: the second reduction, one BEST2_DTYPE record per STAR group from the
@@ -1159,6 +1194,30 @@ def game_quiet_moves(fen: str, moves: str | list[str] = "") -> tuple[np.ndarray,
     N.check(N.lib.fnnue_game_quiet_moves(fen.encode(), moves.encode(), N.ptr(out), cap, N.ptr(mv), C.byref(chk),
                                          C.byref(n)))
     return out[: n.value], mv[: n.value], bool(chk.value)
+
+
+VQ_CHECK, VQ_LOST, VQ_WON, VQ_DRAWN = 1, 2, 4, 8  # FNNUE_VQ_*: game_vquiet_moves' state bits
+
+
+def game_vquiet_moves(variant: int, fen: str, moves: str | list[str] = "",
+                      checks: bool = False) -> tuple[np.ndarray, np.ndarray, int]:
+    """fnnue_game_vquiet_moves: the variant game's last position followed by the candidates of the variants'
+    quiescence (every legal move, drops included, when `checks` and the position is in check; its captures
+    otherwise; nothing when the game is over) -> (positions, uint16 variant move codes with codes[0] = 0,
+    VQ_* state bits)."""
+    if not isinstance(moves, str):
+        moves = " ".join(moves)
+    n, state = C.c_size_t(), C.c_int()
+    rc = N.lib.fnnue_game_vquiet_moves(variant, fen.encode(), moves.encode(), 1 if checks else 0, None, 0, None,
+                                       C.byref(state), C.byref(n))
+    if rc != -10:
+        N.check(rc)
+    cap = n.value
+    out = N.vpositions_array(cap)
+    mv = np.zeros(cap, dtype=np.uint16)
+    N.check(N.lib.fnnue_game_vquiet_moves(variant, fen.encode(), moves.encode(), 1 if checks else 0, N.ptr(out), cap,
+                                          N.ptr(mv), C.byref(state), C.byref(n)))
+    return out[: n.value], mv[: n.value], state.value
 
 
 def random_playouts(seed: int, count: int, min_plies: int = 0, max_plies: int = 160,

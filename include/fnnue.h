@@ -922,8 +922,8 @@ int fnnue_get_search_draws(const fnnue_ctx *ctx, int *on);
  * more than FNNUE_QUIESCE_RECORDS records (environment, read per call; default
  * and most 16M, least 256): a slice of the leaves whose tree would is cut
  * down and redone; a single leaf's tree is never cut.  Results do not depend on the
- * slicing.  Out of scope: variants, move work, check evasions, quiet
- * promotions, any pruning, extending the pv with the capture line. */
+ * slicing.  Out of scope: move work, check evasions, quiet promotions, any
+ * pruning, extending the pv with the capture line (the variants: ABI 3.15). */
 #define FNNUE_QUIESCE_MAX 4
 typedef struct {            /* 20 bytes */
   int32_t psqt, positional; /* of the line's end, oriented to the position's side to move */
@@ -1006,8 +1006,8 @@ int fnnue_quiesce_slices(const fnnue_ctx *ctx, uint64_t *slices);
  * fnnue_search2[_children|_lines], their _device forms and
  * fnnue_quiesce[_device]; a variant net's context accepts and ignores it.
  * Evasion records count toward FNNUE_QUIESCE_RECORDS like capture records.
- * Out of scope: variants, quiet checks or quiet promotions as candidates,
- * stalemate and draw tests inside the tree, pruning. */
+ * Out of scope: quiet checks or quiet promotions as candidates, stalemate and
+ * draw tests inside the tree, pruning (the variants: ABI 3.15). */
 #define FNNUE_VALUE_MATE 32000
 #define FNNUE_QUIET_DECIDED 1
 int fnnue_set_search_quiesce_checks(fnnue_ctx *ctx, int on);
@@ -1018,6 +1018,93 @@ int fnnue_get_search_quiesce_checks(const fnnue_ctx *ctx, int *on);
  * other its captures. */
 int fnnue_game_quiet_moves(const char *fen, const char *moves, fnnue_pos *out, size_t cap, fnnue_move *mv,
                            int *in_check, size_t *n_out);
+
+/* ---- capture quiescence for the variant searches (ABI 3.15) ----
+ * The same tree for crazyhouse, atomic, kingofthehill, racingkings and
+ * threecheck, with the variant's legality and its end of the game inside the
+ * tree.  For a variant position X (board, pockets, en-passant square and
+ * threecheck counters as the variant's replay gives them), a remaining depth d
+ * in 0..FNNUE_QUIESCE_MAX and the setting `checks`:
+ *  - s(X) = trunc((psqt + positional) / 16), as above.
+ *  - over(X), decided without generating a move, at every d (0 included), with
+ *    checks on or off: X's side to move has no king (atomic: exploded): lost.
+ *    The variant's own end of the game: lost (a king on the hill; the other
+ *    side's threecheck counter at 0; the other racing king alone on rank 8 with
+ *    no catch-up), won (the own king alone on rank 8; a threecheck position
+ *    whose own counter is 0) or drawn (both racing kings on rank 8).  Lost is
+ *    worth -FNNUE_VALUE_MATE, won +FNNUE_VALUE_MATE, drawn 0; all three are
+ *    decided: line empty, nodes 0, terms (0, 16 * value), reserved =
+ *    FNNUE_QUIET_DECIDED.
+ *  - vcaps(X): X's legal moves (never drops, never castling) whose capture
+ *    square holds an opponent's piece: the target square, or for en passant the
+ *    square behind an empty en-passant square.  Their order is that of X's
+ *    children in fnnue_build_vchildren, one move per promotion piece.  Legality
+ *    is the variant's: an atomic capture that explodes the own king is no
+ *    candidate, one that explodes the other king is, atomic kings never
+ *    capture, and a racingkings capture may not give check.
+ *  - chk(X), with `checks` only: X's side to move's king is in danger by the
+ *    variant's rule (atomic kings next to each other are never in danger);
+ *    racingkings positions are never in check.
+ *  - cand(X): all legal moves in children order when chk(X), crazyhouse drops
+ *    included; vcaps(X) otherwise.
+ *  - A position that is not over: chk(X) without a legal move is mated at every
+ *    d (value -FNNUE_VALUE_MATE, decided).  Otherwise d = 0 gives s(X) (a side
+ *    in check with a move stands pat at the horizon); d >= 1 with chk(X) gives
+ *    the maximum over cand(X) of the negated child results, candidate 0 being
+ *    the first evasion; d >= 1 otherwise has standing pat as candidate 0, then
+ *    the captures.  A later candidate replaces the current one only when it is
+ *    strictly greater.
+ *  - Negating a decided child: v > 0 gives -(v - 1), v < 0 gives -(v + 1), and
+ *    0 stays 0 and stays decided.  Undecided results negate their terms with
+ *    int32 wrap-around.
+ *  - nodes, move, len and the reported terms are as in ABI 3.13 / 3.14; move is
+ *    a variant move code (fnnue_vmove_uci), so a line may start with a drop.
+ *  - Domain: |s| < FNNUE_VALUE_MATE - 64.  A crazyhouse capture keeps the
+ *    pieces on board and in hand constant and an atomic one lowers them, so
+ *    every record of the tree is inside the evaluator's domain; a position with
+ *    one king exploded evaluates to (0, 0) and the rule overrides its value.
+ *  - Stated limits: stalemate and draws by repetition are not recognised
+ *    inside the tree; quiet checks, quiet promotions and quiet drops are no
+ *    candidates; there is no pruning.
+ *
+ * In the variant searches (fnnue_set_search_vquiesce, depth > 0) the leaves
+ * that take part are the records j >= 1 of a ply's STAR group (one ply) or of
+ * a child's (two plies) whose end byte has none of FNNUE_END_NO_MOVES,
+ * FNNUE_END_DRAW, FNNUE_END_WON.  Each gets the reported terms of its Q before
+ * any reduction; a decided non-zero result is written as (0, 16 * v) with |v| =
+ * FNNUE_VALUE_MATE - (p + n), p the leaf's search depth (1 or 2) and n the
+ * distance inside the tree, a decided draw as (0, 0).  Reductions, variant
+ * ranks, kinds, nodes, pv_len and the pv are untouched.  Slicing
+ * (FNNUE_QUIESCE_RECORDS) and fnnue_quiesce_slices are as for chess. */
+#define FNNUE_VQ_CHECK 1 /* chk(X) (with `checks` only, never with an over bit) */
+#define FNNUE_VQ_LOST 2
+#define FNNUE_VQ_WON 4
+#define FNNUE_VQ_DRAWN 8
+/* Host only: the game's last position followed by cand() of it in order, with
+ * the variant move codes (mv[0] = 0); *state: FNNUE_VQ_* bits.  An over
+ * position lists nothing.  Capacity and error protocol are
+ * fnnue_game_quiet_moves's. */
+int fnnue_game_vquiet_moves(int variant, const char *fen, const char *moves, int checks, fnnue_vpos *out, size_t cap,
+                            fnnue_move *mv, int *state, size_t *n_out);
+/* One fnnue_quiet per ply of every game, CHAIN offsets per game: signature
+ * shape, capacity protocol and errors are fnnue_vsearch1[_device]'s.
+ * FNNUE_E_ARCH on a chess net's context or for a variant the net does not
+ * serve; FNNUE_E_ARG for depth > FNNUE_QUIESCE_MAX.  Distances count from the
+ * ply itself (p = 0). */
+int fnnue_vquiesce_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                          const uint32_t *d_moves_off, size_t ngames, uint32_t depth, int checks, fnnue_quiet *d_out,
+                          size_t cap, uint32_t *d_off, size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_vquiesce(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                   const uint32_t *moves_off, size_t ngames, uint32_t depth, int checks, fnnue_quiet *out, size_t cap,
+                   uint32_t *off, size_t off_cap, size_t *n_out, size_t *n_groups);
+/* The quiescence depth (default 0, at most FNNUE_QUIESCE_MAX: FNNUE_E_ARG) and
+ * its checks setting for fnnue_vsearch1[_lines], fnnue_vsearch2[_children|
+ * _lines] and their _device forms.  A chess net's context accepts the setting
+ * and ignores it, as a variant net's context keeps ignoring
+ * fnnue_set_search_quiesce[_checks].  With depth 0 every byte of every result
+ * is that of ABI 3.14. */
+int fnnue_set_search_vquiesce(fnnue_ctx *ctx, int depth, int checks);
+int fnnue_get_search_vquiesce(const fnnue_ctx *ctx, int *depth, int *checks);
 
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware

@@ -448,6 +448,20 @@ int fnnue_backend_quiesce(fnnue_backend *b, int *depth);
 int fnnue_backend_set_quiesce_checks(fnnue_backend *b, int on);
 int fnnue_backend_quiesce_checks(fnnue_backend *b, int *on);
 
+/* ---- capture quiescence for variant batches (ABI 3.15) ----
+ * fnnue_backend_set_variant_quiesce(b, depth, checks) (default 0 / off, depth at
+ * most FNNUE_QUIESCE_MAX: FNNUE_E_ARG): variant analysis batches at one and two
+ * plies, through every go* call, put the variants' quiescence (fnnue.h, ABI
+ * 3.15) below their searches' leaves, at both reduction sites.  With depth > 0
+ * a coded mate (|value| > FNNUE_VALUE_MATE - 64) is answered as Score::Mate by
+ * the conversion of ABI 3.14 at every fill site; the variants' rule decides
+ * finished positions with checks off too, so the condition is the depth alone.
+ * Move work, depth-0 analysis, chess batches and a backend without the setting
+ * are unchanged; fnnue_backend_set_quiesce[_checks] keep applying to chess
+ * batches only. */
+int fnnue_backend_set_variant_quiesce(fnnue_backend *b, int depth, int checks);
+int fnnue_backend_variant_quiesce(fnnue_backend *b, int *depth, int *checks);
+
 /* ---- MultiPV at two plies (ABI 3.11) ----
  * One line of a response with its whole pv, as the reference keeps one
  * Vec<Uci> per MultiPV line at the searched depth ([ref] src/ipc.rs:68-93). */

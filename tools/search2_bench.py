@@ -33,7 +33,7 @@ actor's go_pv() at 1 and 2 variant plies on batches of that variant;
 (fnnue_set_search_draws) off and on, in this process on the same games (phases
 search2_draws_off / _on: median, min, max), and traced calls with the rules on,
 whose line carries history_ms, mark_ms and draw_list (the plies on the list).
-`--quiesce D` (chess) adds interleaved rounds (`--runs` of them, at least 3) of search1 and search2 with the
+`--quiesce D` (chess, or with `--variant` the variants' quiescence: fnnue_set_search_vquiesce) adds interleaved rounds (`--runs` of them, at least 3) of search1 and search2 with the
 capture quiescence depth (fnnue_set_search_quiesce) at 0, 1, .. D, in this process on the same games (phases
 search1_quiesce_d / search2_quiesce_d: median, min, max of the device time between two events, and the host's
 wall time, which holds the level read-backs), and one traced search2 call per depth, whose line carries
@@ -178,7 +178,7 @@ def main():
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
     if a.draws and not a.variant:
         draws_rounds(a, ev, stream, search2, base)
-    if a.quiesce and not a.variant:
+    if a.quiesce:
         quiesce_rounds(a, ev, stream, search1, search2, base)
     ev.close()
     if a.actor and a.variant:
@@ -239,6 +239,13 @@ def quiesce_rounds(a, ev, stream, search1, search2, base):
         ev.check()
         return e0.elapsed_time(e1), wall
 
+    def setting(d, checks):  # a variant net's context has one setter for both (fnnue_set_search_vquiesce)
+        if a.variant:
+            ev.set_search_vquiesce(d, checks)
+        else:
+            ev.set_search_quiesce(d)
+            ev.set_search_quiesce_checks(checks)
+
     depths = [(d, False) for d in range(a.quiesce + 1)]
     if a.quiesce_checks:  # every depth above 0 with the setting off and on, interleaved
         depths = sorted(depths + [(d, True) for d in range(1, a.quiesce + 1)])
@@ -246,8 +253,7 @@ def quiesce_rounds(a, ev, stream, search1, search2, base):
     ms = {(n, d): [] for n in ("search1", "search2") for d in depths}
     for _ in range(rounds):
         for d, checks in depths:
-            ev.set_search_quiesce(d)
-            ev.set_search_quiesce_checks(checks)
+            setting(d, checks)
             ms[("search1", (d, checks))].append(timed(search1))
             ms[("search2", (d, checks))].append(timed(search2))
     for (name, (d, checks)), v in ms.items():
@@ -258,14 +264,12 @@ def quiesce_rounds(a, ev, stream, search1, search2, base):
                               max_ms=round(dev_ms[-1], 4), wall_median_ms=round(wall[len(wall) // 2], 4))), flush=True)
     os.environ["FNNUE_SEARCH2_TRACE"] = "1"
     for d, checks in depths[1:]:
-        ev.set_search_quiesce(d)
-        ev.set_search_quiesce_checks(checks)
+        setting(d, checks)
         with torch.cuda.stream(stream):
             search2()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
-    ev.set_search_quiesce(0)
-    ev.set_search_quiesce_checks(False)
+    setting(0, False)
 
 
 def actor_lines(a):
