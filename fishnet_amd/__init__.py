@@ -8,7 +8,7 @@ from .nnue import (  # noqa: F401
     Best, BEST_DTYPE, BEST_NONE, BEST_CP, BEST_MATE, move_uci, Line, LINE_DTYPE, MAX_CHILDREN,
     BEST2_DTYPE, BEST_MATED, LINE2_DTYPE, END_DRAW, PLY_HISTORY_DTYPE, game_history,
     QUIET_DTYPE, QUIESCE_MAX, game_captures, game_quiet_moves, VALUE_MATE, QUIET_DECIDED,
-    game_vquiet_moves, VQ_CHECK, VQ_LOST, VQ_WON, VQ_DRAWN,
+    game_vquiet_moves, VQ_CHECK, VQ_LOST, VQ_WON, VQ_DRAWN, game_vhistory,
 )
 from ._native import (  # noqa: F401
     GROUP_CHAIN, GROUP_STAR, PLAYOUT_CHILDREN, PLAYOUT_FINAL, PLAYOUT_PLIES, VARIANT_ATOMIC, VARIANT_CRAZYHOUSE,

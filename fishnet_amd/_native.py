@@ -243,6 +243,15 @@ SIGNATURES = {
     "fnnue_get_search_vquiesce": ([_vp, _P(_i32), _P(_i32)], _i32),
     "fnnue_backend_set_variant_quiesce": ([_vp, _i32, _i32], _i32),
     "fnnue_backend_variant_quiesce": ([_vp, _P(_i32), _P(_i32)], _i32),
+    # repetition and fifty-move draws in the variant searches (ABI 3.16)
+    "fnnue_game_vhistory": ([_i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)], _i32),
+    "fnnue_game_vhistory_device": ([_vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz), _vp], _i32),
+    "fnnue_ctx_game_vhistory": ([_vp, _i32, C.c_char_p, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(_sz), _P(_sz)],
+                                _i32),
+    "fnnue_set_search_vdraws": ([_vp, _i32], _i32),
+    "fnnue_get_search_vdraws": ([_vp, _P(_i32)], _i32),
+    "fnnue_backend_set_variant_draw_rules": ([_vp, _i32], _i32),
+    "fnnue_backend_variant_draw_rules": ([_vp, _P(_i32)], _i32),
     "fnnue_backend_set_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_set_variant_analysis_depth": ([_vp, _i32], _i32),
     "fnnue_backend_channel": ([_vp, _i32, _vp, _P(_vp)], _i32),

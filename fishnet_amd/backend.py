@@ -387,6 +387,17 @@ class GpuEvalStub:
         N.check(N.lib.fnnue_backend_variant_quiesce(self._actor._h, C.byref(d), C.byref(on)))
         return d.value, bool(on.value)
 
+    def set_variant_draw_rules(self, on: bool) -> None:
+        """fnnue_backend_set_variant_draw_rules: variant analysis batches at 1 or 2 plies score the moves that
+        repeat a position for the third time, or reach the clock rule of their variant, as draws (fnnue.h, ABI
+        3.16; Cp 0, the pv ends there).  Chess batches keep following set_draw_rules."""
+        N.check(N.lib.fnnue_backend_set_variant_draw_rules(self._actor._h, 1 if on else 0))
+
+    def variant_draw_rules(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_backend_variant_draw_rules(self._actor._h, C.byref(on)))
+        return bool(on.value)
+
     def go_one(self, body: AcquireResponseBody) -> list[PositionResponse]:
         """One batch; raises PositionFailed like StockfishStub::go's Err."""
         r = self.go([body])[0]
@@ -419,7 +430,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
             variant_analysis_plies: int | None = None,
             draw_rules: bool = False, quiesce: int = 0,
             quiesce_checks: bool = False, variant_quiesce: int = 0,
-            variant_quiesce_checks: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
+            variant_quiesce_checks: bool = False,
+            variant_draw_rules: bool = False) -> tuple[GpuEvalStub, GpuEvalActor]:
     """stockfish::channel for the GPU evaluator.  `net` (a fishnet_amd.Net)
     goes to the slot of its variant; `crazyhouse` / `atomic` add variant nets
     (fnnue_backend_channel_nets), `kingofthehill` / `racingkings` / `threecheck` theirs
@@ -434,7 +446,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
     searches' leaves (GpuEvalStub.set_quiesce; 0 by default); `quiesce_checks`: check evasions and mates inside
     that quiescence (GpuEvalStub.set_quiesce_checks; off by default); `variant_quiesce` /
     `variant_quiesce_checks`: the same for the variant nets' batches under the variants' rule
-    (GpuEvalStub.set_variant_quiesce; 0 / off by default)."""
+    (GpuEvalStub.set_variant_quiesce; 0 / off by default); `variant_draw_rules`: repetition and n-move draws in
+    the variant searches, each variant's own rule (GpuEvalStub.set_variant_draw_rules; off by default)."""
     h = C.c_void_p()
     init = _Init(normalize_to_pawn, timeout_ms)
     if kingofthehill is not None or racingkings is not None or threecheck is not None:
@@ -465,6 +478,8 @@ def channel(net=None, device: int = 0, normalize_to_pawn: int = 0, *, crazyhouse
         stub.set_quiesce_checks(True)
     if variant_quiesce or variant_quiesce_checks:
         stub.set_variant_quiesce(variant_quiesce, variant_quiesce_checks)
+    if variant_draw_rules:
+        stub.set_variant_draw_rules(True)
     return stub, actor
 
 

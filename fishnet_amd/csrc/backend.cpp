@@ -526,6 +526,8 @@ struct fnnue_backend {
   // (decided values exist with checks off too: coded mates are answered whenever the depth is set)
   int vquiesce = 0;
   bool vquiesce_checks = false;
+  // fnnue_backend_set_variant_draw_rules: repetition and n-move draws in the variant searches, each variant's rule
+  bool variant_draw_rules = false;
   int job_plies = 0;  // the chess depth of the go() in flight: analysis_depth, 1 for a go_lines() on a 2-plies channel
   int vjob_plies = 0;  // the same for the variant nets: variant_analysis_depth (0, 1 or 2 plies)
   // a search per ply (one ply or two), and the two-ply search
@@ -994,14 +996,15 @@ int fnnue_backend::stage_search(int k, size_t pi) {
   if (int rc = reserve(W.kid_po, total * 4, &g.positional)) return rc;
   g.moves = km;
   HIP_TRY(write_children(rules, g.states, n, coff, g.total, kp, km, g.end, s), "children launch");
-  // The draw rules (fnnue_backend_set_draw_rules, chess batches): a piece holds
+  // The draw rules (fnnue_backend_set_draw_rules for chess batches,
+  // fnnue_backend_set_variant_draw_rules for a variant's): a piece holds
   // whole games (plan() never cuts one), so the history of its plies is
   // complete; the marks go on the listed plies' children here and on their
   // grandchildren behind the second expansion, before the reductions.
   SearchSettings set{nullptr, rules.chess() ? quiesce : vquiesce, rules.chess() ? quiesce_checks : vquiesce_checks};
   DrawHistory hist;
-  if (rules.chess() && draw_rules) {
-    if (int rc = draw_history_level1(dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
+  if (rules.chess() ? draw_rules : variant_draw_rules) {
+    if (int rc = draw_history_level1(rules, dimg, reinterpret_cast<const uint32_t*>(dimg + P.o_fen),
                                      reinterpret_cast<const uint32_t*>(dimg + P.o_mv),
                                      reinterpret_cast<const uint32_t*>(dimg + P.o_ply), P.ng, g.states, n, coff, km,
                                      g.end, s, W.bscratch, &hist, nullptr))
@@ -2019,6 +2022,20 @@ int fnnue_backend_draw_rules(fnnue_backend* b, int* on) {
   if (!b || !on) return fail(FNNUE_E_ARG, "null argument");
   std::lock_guard<std::mutex> lk(b->run_mu);
   *on = b->draw_rules ? 1 : 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_set_variant_draw_rules(fnnue_backend* b, int on) {
+  if (!b) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);  // after the call in flight
+  b->variant_draw_rules = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_backend_variant_draw_rules(fnnue_backend* b, int* on) {
+  if (!b || !on) return fail(FNNUE_E_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(b->run_mu);
+  *on = b->variant_draw_rules ? 1 : 0;
   return FNNUE_OK;
 }
 

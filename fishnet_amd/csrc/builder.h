@@ -161,13 +161,13 @@ BuildResult replay_states_device(int variant, const char* d_text, const uint32_t
                                  uint32_t ngames, size_t max_plies, hipStream_t s, BuilderScratch& ws,
                                  const void** d_states, const uint32_t** d_ply_off);
 
-// ---- draws.hip: repetition and fifty-move draws (include/fnnue.h, ABI 3.12) ----
-// The history of n plies (d_states: the replay's boards, d_ply_off: ngames + 1)
-// in the scratch: per ply its fnnue_ply_history, its 63-bit identity key (bit
-// 63: the move that led to it was irreversible), the first ply of its window
-// (the last irreversible move, or the game's root), and the compacted list of
-// the plies with a descendant that can be drawn at all (list[0] = their number).
-// key_bits: 1..63.  Four small kernels, stream-ordered, no sync.
+// ---- draws.hip: repetition and fifty-move draws (include/fnnue.h, ABI 3.12; the variants: 3.16) ----
+// The history of n plies (game_history_device, search_steps.h) in the scratch:
+// per ply its fnnue_ply_history, its 63-bit identity key (bit 63: the move that
+// led to it was irreversible), the first ply of its window (the last
+// irreversible move, or the game's root; crazyhouse: always the root), and the
+// compacted list of the plies with a descendant that can be drawn at all
+// (list[0] = their number).
 struct DrawHistory {
   const fnnue_ply_history* hist = nullptr;
   const uint64_t* keys = nullptr;
@@ -176,22 +176,8 @@ struct DrawHistory {
   uint32_t key_bits = 63;
 };
 uint32_t draw_key_bits();  // FNNUE_DRAW_KEY_BITS in the environment, read per call (tests); 63 without
-hipError_t game_history_device(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
-                               const uint32_t* d_ply_off, uint32_t ngames, const DBoard* d_states, uint32_t n,
-                               uint32_t key_bits, hipStream_t s, BuilderScratch& ws, DrawHistory* out);
-// The marking passes, over the listed plies alone (an early-out on an empty
-// list).  Level 1: the children of the plies' STAR groups (d_off: n + 1), each
-// record's move code applied to its ply's board.  Level 2: the grandchildren of
-// the plies [p0, p1), parents d_kid_states (dense, child j of ply i at
-// d_off[i] - i + j - 1), their STAR offsets d_kid_off (whole array), the
-// records' arrays starting at record rec0 (a chunk).  own_terms: a drawn
-// child's own terms (its group's first record) into its depth-1 record, behind
-// the first reduction.
-hipError_t mark_draws_level1(const DrawHistory& h, const DBoard* d_states, uint32_t n, const uint32_t* d_off,
-                             const uint16_t* d_moves, uint8_t* d_end, hipStream_t s);
-hipError_t mark_draws_level2(const DrawHistory& h, const DBoard* d_states, uint32_t p0, uint32_t p1,
-                             const uint32_t* d_off, const DBoard* d_kid_states, const uint32_t* d_kid_off,
-                             uint32_t rec0, const uint16_t* d_gmoves, uint8_t* d_gend, hipStream_t s);
+// A drawn child's own terms (its group's first record) into its depth-1 record,
+// behind the first reduction; board-independent.
 hipError_t draw_own_terms(const DrawHistory& h, uint32_t p0, uint32_t p1, const uint32_t* d_off, const uint8_t* d_end,
                           const uint32_t* d_kid_off, uint32_t rec0, const int32_t* d_gps, const int32_t* d_gpo,
                           fnnue_best* d_kid_best, hipStream_t s);

@@ -387,7 +387,10 @@ const char* fnnue_last_error(void) { return g_err.c_str(); }
 // 3.15: capture quiescence for the variant searches: fnnue_vquiesce[_device], fnnue_game_vquiet_moves and the
 //       FNNUE_VQ_* states, fnnue_set_search_vquiesce / fnnue_get_search_vquiesce,
 //       fnnue_backend_set_variant_quiesce / fnnue_backend_variant_quiesce
-uint32_t fnnue_abi_version(void) { return (3u << 16) | 15u; }
+// 3.16: repetition and fifty-move draws in the variant searches, each variant's own rule:
+//       fnnue_game_vhistory[_device], fnnue_ctx_game_vhistory, fnnue_set_search_vdraws / fnnue_get_search_vdraws,
+//       fnnue_backend_set_variant_draw_rules / fnnue_backend_variant_draw_rules
+uint32_t fnnue_abi_version(void) { return (3u << 16) | 16u; }
 
 int fnnue_net_load_mem(const void* buf, size_t len, fnnue_net** out) {
   if (!buf || !out) return fail(FNNUE_E_ARG, "null argument");

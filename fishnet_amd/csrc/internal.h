@@ -47,6 +47,7 @@ struct fnnue_ctx {
   bool search_quiesce_checks = false;  // fnnue_set_search_quiesce_checks: evasions and mates inside that tree
   int search_vquiesce = 0;     // fnnue_set_search_vquiesce: the variant searches' quiescence depth and its checks
   bool search_vquiesce_checks = false;
+  bool search_vdraws = false;  // fnnue_set_search_vdraws: the variants' repetition and n-move draws in fnnue_vsearch1 / 2
   uint64_t quiesce_slices = 0; // slices of root frontiers quiesce.hip has worked through (fnnue_quiesce_slices)
   int32_t acc_bound = 0;       // accumulator_bound of the net (the largest slice bound)
   uint64_t swar_eligible = 0;  // bit s: slice s's bound < 2^15, SWAR rows allowed (plan.swar: the enabled ones)

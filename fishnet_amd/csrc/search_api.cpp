@@ -411,8 +411,8 @@ int search1_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32
   if (set.quiesce > 0 && nrec > 0xFFFFFFFFu) return fail(FNNUE_E_ARG, "batch too large");
   const StarGroups l1{ws.p[BuilderScratch::kStates], (uint32_t)nply, kids.off, (uint32_t)nrec, kids.moves, kids.end, ps, po};
   DrawHistory hist;
-  if (rules.chess() && ctx->search_draws) {  // the plies' history from the boards the replay left
-    if ((rc = draw_history_level1(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, l1.states, l1.n, l1.off,
+  if (rules.chess() ? ctx->search_draws : ctx->search_vdraws) {  // the plies' history from the boards the replay left
+    if ((rc = draw_history_level1(rules, d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, l1.states, l1.n, l1.off,
                                   l1.moves, l1.end, s, ws, &hist, nullptr)))
       return rc;
     set.draws = &hist;
@@ -802,13 +802,13 @@ int search2_device(fnnue_ctx* ctx, int variant, bool vcall, const char* d_text, 
     HIP_TRY(hipMemcpyAsync(d_off, kids.ply_off, (ngames + 1) * 4, hipMemcpyDeviceToDevice, s), "D2D(offsets)");
     return FNNUE_OK;
   }
-  // The draw rules (chess, fnnue_set_search_draws): the plies' history and the
-  // marks on the listed plies' children here, their grandchildren per chunk.
+  // The draw rules (fnnue_set_search_draws, a variant: fnnue_set_search_vdraws): the plies' history
+  // and the marks on the listed plies' children here, their grandchildren per chunk.
   SearchSettings set{nullptr, rules.chess() ? ctx->search_quiesce : ctx->search_vquiesce,
                      rules.chess() ? ctx->search_quiesce_checks : ctx->search_vquiesce_checks};
   DrawHistory hist;
-  if (rules.chess() && ctx->search_draws) {
-    if ((rc = draw_history_level1(d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, l1.states, l1.n,
+  if (rules.chess() ? ctx->search_draws : ctx->search_vdraws) {
+    if ((rc = draw_history_level1(rules, d_text, d_fen_off, d_moves_off, kids.ply_off, (uint32_t)ngames, l1.states, l1.n,
                                   l1.off, l1.moves, l1.end, s, ws, &hist, &hook)))
       return rc;
     set.draws = &hist;
@@ -1254,24 +1254,79 @@ int fnnue_get_search_draws(const fnnue_ctx* ctx, int* on) {
   return FNNUE_OK;
 }
 
-int fnnue_game_history_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
-                              const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap,
-                              uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
-  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
-  *n_out = *n_groups = 0;
+int fnnue_set_search_vdraws(fnnue_ctx* ctx, int on) {
+  if (!ctx) return fail(FNNUE_E_ARG, "null ctx");
+  ctx->search_vdraws = on != 0;
+  return FNNUE_OK;
+}
+
+int fnnue_get_search_vdraws(const fnnue_ctx* ctx, int* on) {
+  if (!ctx || !on) return fail(FNNUE_E_ARG, "null argument");
+  *on = ctx->search_vdraws ? 1 : 0;
+  return FNNUE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// fnnue_game_history_device / fnnue_game_vhistory_device: the replay of `variant`, then its history.
+int history_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                   const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap, uint32_t* d_off,
+                   size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
   const size_t room = d_out && d_off && off_cap >= ngames + 1 ? cap : 0;
-  return replayed_plies(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
+  return replayed_plies(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, room, d_off, n_out, n_groups, stream,
                         [&](const void* states, size_t n, const uint32_t* ply_off, hipStream_t s) {
                           DrawHistory hist;
-                          HIP_TRY(game_history_device(d_text, d_fen_off, d_moves_off, ply_off, (uint32_t)ngames,
-                                                      static_cast<const DBoard*>(states), (uint32_t)n, draw_key_bits(),
-                                                      s, ctx->bscratch, &hist),
+                          HIP_TRY(game_history_device(SearchRules{variant}, d_text, d_fen_off, d_moves_off, ply_off,
+                                                      (uint32_t)ngames, states, (uint32_t)n, draw_key_bits(), s,
+                                                      ctx->bscratch, &hist),
                                   "game history launch");
                           HIP_TRY(hipMemcpyAsync(d_out, hist.hist, n * sizeof(fnnue_ply_history),
                                                  hipMemcpyDeviceToDevice, s),
                                   "D2D(history)");
                           return (int)FNNUE_OK;
                         });
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnnue_game_history_device(fnnue_ctx* ctx, const char* d_text, const uint32_t* d_fen_off,
+                              const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap,
+                              uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  return history_device(ctx, kVariantChess, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, n_out,
+                        n_groups, stream);
+}
+
+int fnnue_game_vhistory_device(fnnue_ctx* ctx, int variant, const char* d_text, const uint32_t* d_fen_off,
+                               const uint32_t* d_moves_off, size_t ngames, fnnue_ply_history* d_out, size_t cap,
+                               uint32_t* d_off, size_t off_cap, size_t* n_out, size_t* n_groups, void* stream) {
+  if (!ctx || !n_out || !n_groups) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (!variant_known(variant) || variant == kVariantChess)
+    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  return history_device(ctx, variant, d_text, d_fen_off, d_moves_off, ngames, d_out, cap, d_off, off_cap, n_out,
+                        n_groups, stream);
+}
+
+int fnnue_ctx_game_vhistory(fnnue_ctx* ctx, int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                            const uint32_t* moves_off, size_t ngames, fnnue_ply_history* out, size_t cap,
+                            uint32_t* off, size_t off_cap, size_t* n_out, size_t* n_groups) {
+  if (!ctx || !n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off)))
+    return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (!variant_known(variant) || variant == kVariantChess)
+    return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (ngames == 0) return FNNUE_OK;
+  return plies_host(ctx, text, text_len, fen_off, moves_off, ngames, out, cap, off, off_cap, n_out, false,
+                    [&](const StagedGames& d, hipStream_t s, auto... outputs) {
+                      return fnnue_game_vhistory_device(ctx, variant, d.text, d.fen_off, d.moves_off, ngames,
+                                                        outputs..., n_out, n_groups, s);
+                    });
 }
 
 int fnnue_ctx_game_history(fnnue_ctx* ctx, const char* text, size_t text_len, const uint32_t* fen_off,

@@ -49,16 +49,16 @@ hipError_t topk_replies(bool vranks, const uint8_t* d_end, const uint16_t* d_mov
                              uniform_k, d_lines, lines_cap, s);
 }
 
-int draw_history_level1(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+int draw_history_level1(SearchRules r, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                         const uint32_t* d_ply_off, uint32_t ngames, const void* d_states, uint32_t n,
                         const uint32_t* d_off, const uint16_t* d_moves, uint8_t* d_end, hipStream_t s,
                         BuilderScratch& ws, DrawHistory* hist, const PhaseHook* hook) {
-  const DBoard* plies = static_cast<const DBoard*>(d_states);
   begin_phase(hook, kPhaseHistory);
-  HIP_TRY(game_history_device(d_text, d_fen_off, d_mv_off, d_ply_off, ngames, plies, n, draw_key_bits(), s, ws, hist),
+  HIP_TRY(game_history_device(r, d_text, d_fen_off, d_mv_off, d_ply_off, ngames, d_states, n, draw_key_bits(), s, ws,
+                              hist),
           "game history launch");
   begin_phase(hook, kPhaseMark);
-  HIP_TRY(mark_draws_level1(*hist, plies, n, d_off, d_moves, d_end, s), "draw marks launch");
+  HIP_TRY(mark_draws_level1(r, *hist, d_states, n, d_off, d_moves, d_end, s), "draw marks launch");
   return FNNUE_OK;
 }
 
@@ -87,8 +87,8 @@ int search_level2_chunk(fnnue_ctx* ctx, BuilderScratch& ws, SearchRules r, const
   HIP_TRY(write_children(r, chunk_states, c.nk, c.ch_off, c.nr, c.pos, c.moves, c.end, s), "children write");
   if (set.draws) {  // behind the expansion, before the reduction reads the end bytes; offsets relative to the chunk
     begin_phase(hook, kPhaseMark);
-    HIP_TRY(mark_draws_level2(*set.draws, static_cast<const DBoard*>(l1.states), c.p0, c.p1, l1.off,
-                              static_cast<const DBoard*>(d_kid_states), d_kid_off, c.rec0, c.moves, c.end, s),
+    HIP_TRY(mark_draws_level2(r, *set.draws, l1.states, c.p0, c.p1, l1.off, d_kid_states, d_kid_off, c.rec0, c.moves,
+                              c.end, s),
             "draw marks launch");
   }
   begin_phase(hook, kPhaseEval);

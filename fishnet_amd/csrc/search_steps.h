@@ -38,8 +38,8 @@ hipError_t topk_replies(bool vranks, const uint8_t* d_end, const uint16_t* d_mov
                         const uint32_t* d_line_off, uint32_t uniform_k, fnnue_line2* d_lines, size_t lines_cap,
                         hipStream_t s);
 
-// A caller's copy of its search settings: the draws are chess's alone, the quiescence the
-// caller's setting for the rules it searches under (a chess one or a variant one).
+// A caller's copy of its search settings: the draws and the quiescence are the caller's
+// settings for the rules it searches under (the chess ones or the variants').
 struct SearchSettings {
   const DrawHistory* draws = nullptr;  // the plies' history (draw_history_level1), or none
   int quiesce = 0;                     // capture quiescence depth below the leaves
@@ -78,10 +78,29 @@ inline void begin_phase(const PhaseHook* h, int phase) {
   if (h) h->begin(h->arg, phase);
 }
 
+// draws.hip, under r's rule (include/fnnue.h: chess ABI 3.12, the variants ABI
+// 3.16).  The history of n plies (d_states: the replay's boards, r.state_bytes()
+// each; d_ply_off: ngames + 1) into the scratch and *out (builder.h
+// DrawHistory).  key_bits: 1..63.  A few small kernels, stream-ordered, no sync.
+hipError_t game_history_device(SearchRules r, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+                               const uint32_t* d_ply_off, uint32_t ngames, const void* d_states, uint32_t n,
+                               uint32_t key_bits, hipStream_t s, BuilderScratch& ws, DrawHistory* out);
+// The marking passes, over the listed plies alone (an early-out on an empty
+// list).  Level 1: the children of the plies' STAR groups (d_off: n + 1), each
+// record's move code applied to its ply's board.  Level 2: the grandchildren of
+// the plies [p0, p1), parents d_kid_states (dense, child j of ply i at
+// d_off[i] - i + j - 1), their STAR offsets d_kid_off (whole array), the
+// records' arrays starting at record rec0 (a chunk).
+hipError_t mark_draws_level1(SearchRules r, const DrawHistory& h, const void* d_states, uint32_t n,
+                             const uint32_t* d_off, const uint16_t* d_moves, uint8_t* d_end, hipStream_t s);
+hipError_t mark_draws_level2(SearchRules r, const DrawHistory& h, const void* d_states, uint32_t p0, uint32_t p1,
+                             const uint32_t* d_off, const void* d_kid_states, const uint32_t* d_kid_off, uint32_t rec0,
+                             const uint16_t* d_gmoves, uint8_t* d_gend, hipStream_t s);
+
 // The draw rules at level 1: the history of the n plies (d_states: the
 // replay's boards, d_ply_off: ngames + 1) into *hist, then the marks on the
 // end bytes of the listed plies' children (d_off: the plies' STAR offsets).
-int draw_history_level1(const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
+int draw_history_level1(SearchRules r, const char* d_text, const uint32_t* d_fen_off, const uint32_t* d_mv_off,
                         const uint32_t* d_ply_off, uint32_t ngames, const void* d_states, uint32_t n,
                         const uint32_t* d_off, const uint16_t* d_moves, uint8_t* d_end, hipStream_t s,
                         BuilderScratch& ws, DrawHistory* hist, const PhaseHook* hook);

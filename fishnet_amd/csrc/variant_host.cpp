@@ -1,6 +1,8 @@
 // variant_host.cpp — host side of the Fairy-Stockfish variant path: FEN with
 // crazyhouse holdings -> fnnue_vpos, and seeded random walks that produce
-// variant positions for tests and the bench (include/fnnue.h).
+// variant positions for tests and the bench, and the variants' draw history on
+// the host replay (fnnue_game_vhistory) (include/fnnue.h).
+#include <algorithm>
 #include <cstring>
 #include <thread>
 #include <string>
@@ -291,6 +293,95 @@ int fnnue_game_end(int variant, const char* fen, const char* moves, int* flags) 
   });
   if (rc) return rc;
   *flags = vb::final_state(last);
+  return FNNUE_OK;
+}
+
+// The variants' draw history on the host (include/fnnue.h, ABI 3.16): the record
+// the device history (draws.hip) is held to.
+int fnnue_game_vhistory(int variant, const char* text, size_t text_len, const uint32_t* fen_off,
+                        const uint32_t* moves_off, size_t ngames, fnnue_ply_history* out, size_t cap, uint32_t* off,
+                        size_t off_cap, size_t* n_out, size_t* n_groups) {
+  if (!n_out || !n_groups || (ngames && (!text || !fen_off || !moves_off))) return fail(FNNUE_E_ARG, "null argument");
+  *n_out = *n_groups = 0;
+  if (!valid_variant(variant)) return fail(FNNUE_E_ARG, "unknown variant " + std::to_string(variant));
+  if (ngames == 0) return FNNUE_OK;
+  if (fen_off[ngames] > text_len) return fail(FNNUE_E_ARG, "offsets exceed the text");
+  for (size_t g = 0; g < ngames; ++g)
+    if (fen_off[g] > moves_off[g] || moves_off[g] > fen_off[g + 1]) return fail(FNNUE_E_ARG, "offsets out of order");
+  size_t plies = 0;
+  for (size_t g = 0; g < ngames; ++g) {
+    uint32_t p = moves_off[g], st;
+    ++plies;
+    while (vb::next_token(text, p, fen_off[g + 1], st) > 0) ++plies;
+  }
+  *n_out = plies;
+  *n_groups = ngames;
+  if (!out || !off || cap < plies || off_cap < ngames + 1) return fail(FNNUE_E_CAPACITY, "output buffer too small");
+  const bool clocked = variant != kVariantCrazyhouse;
+  // The identity: placement, side to move, castling rooks, the en-passant square when a pawn of the side to
+  // move attacks it; crazyhouse: pockets and promoted marks; threecheck: both counters.
+  auto counted_ep = [](const vb::VBoard& b) {
+    return b.ep >= 0 && (vb::pawn_att(b.stm ^ 1, b.ep) & b.bt[vb::PAWN] & vb::colour(b, b.stm)) ? (int)b.ep : -1;
+  };
+  auto same = [&](const vb::VBoard& x, const vb::VBoard& y) {
+    bool eq = x.bc[0] == y.bc[0] && x.bc[1] == y.bc[1] && x.stm == y.stm && std::memcmp(x.cr, y.cr, sizeof x.cr) == 0 &&
+              counted_ep(x) == counted_ep(y);
+    for (int t = vb::PAWN; t <= vb::KING; ++t) eq = eq && x.bt[t] == y.bt[t];
+    if (variant == kVariantCrazyhouse)
+      eq = eq && x.pocket[0] == y.pocket[0] && x.pocket[1] == y.pocket[1] && x.promoted == y.promoted;
+    if (variant == kVariantThreeCheck) eq = eq && x.bt[0] == y.bt[0];
+    return eq;
+  };
+  size_t n = 0;
+  std::vector<vb::VBoard> game;
+  for (size_t g = 0; g < ngames; ++g) {
+    vb::VBoard b;
+    if (!vb::parse_fen(text, fen_off[g], moves_off[g], variant, b))
+      return fail(FNNUE_E_FEN, "unparsable FEN in game " + std::to_string(g));
+    // clock(0): the fifth field, threecheck: the first from the fifth on without a '+'; a number, else 0
+    uint32_t clock = 0;
+    if (clocked) {
+      uint32_t p = fen_off[g], st = 0;
+      int len = 0;
+      for (int field = 0; field < 5; ++field) len = vb::next_token(text, p, moves_off[g], st);
+      while (variant == kVariantThreeCheck && len > 0 && std::memchr(text + st, '+', (size_t)len))
+        len = vb::next_token(text, p, moves_off[g], st);
+      bool number = len > 0;
+      uint32_t v = 0;
+      for (int i = 0; i < len && number; ++i) {
+        const char ch = text[st + i];
+        if (ch < '0' || ch > '9') number = false;
+        else v = std::min<uint32_t>(v * 10u + (uint32_t)(ch - '0'), 65535u);
+      }
+      clock = number ? v : 0;
+    }
+    game.clear();
+    off[g] = (uint32_t)n;
+    uint32_t p = moves_off[g], st;
+    for (size_t i = 0;; ++i) {
+      if (i) {
+        const int len = vb::next_token(text, p, fen_off[g + 1], st);
+        if (len == 0) break;
+        vb::VMove m;
+        if (!vb::match_uci(b, text + st, len, m))
+          return fail(FNNUE_E_MOVE, "illegal move at ply " + std::to_string(i) + " of game " + std::to_string(g));
+        const vb::VBoard before = b;
+        vb::do_move(b, m);
+        // a pawn moved, or a piece left the board (a capture, an atomic explosion): the clock starts again
+        const bool resets = before.bt[vb::PAWN] != b.bt[vb::PAWN] ||
+                            vb::vpopcnt(vb::occupied(before)) != vb::vpopcnt(vb::occupied(b));
+        clock = !clocked || resets ? 0 : std::min<uint32_t>(clock + 1, 65535u);
+      }
+      size_t seen = 0;
+      for (const vb::VBoard& q : game) seen += same(q, b) ? 1 : 0;
+      game.push_back(b);
+      out[n].clock = (uint16_t)clock;
+      out[n].seen = (uint8_t)std::min<size_t>(seen, 255);
+      out[n].reserved = 0;
+      ++n;
+    }
+  }
+  off[ngames] = (uint32_t)n;
   return FNNUE_OK;
 }
 

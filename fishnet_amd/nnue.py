@@ -205,6 +205,12 @@ def game_history(games) -> tuple[np.ndarray, np.ndarray]:
     return _game_history(N.lib.fnnue_game_history, (), games)
 
 
+def game_vhistory(variant: int, games) -> tuple[np.ndarray, np.ndarray]:
+    """fnnue_game_vhistory (host variant replay): game_history() under the variant's rule (ABI 3.16: crazyhouse
+    has no clock and counts pockets and promoted marks, threecheck counts its check counters)."""
+    return _game_history(N.lib.fnnue_game_vhistory, (variant,), games)
+
+
 def game_end(fen: str, moves: str | list[str] = "", variant: int = 0) -> int:
     """FNNUE_END_* flags of the position after `moves` (host replay): no legal
     move, side to move in check, its king exploded (atomic)."""
@@ -538,6 +544,22 @@ class Evaluator:
                                                 C.c_void_p(d_off), off_cap, C.byref(n), C.byref(g),
                                                 C.c_void_p(stream)))
         return n.value, g.value
+
+    # repetition and fifty-move draws in the variant searches (ABI 3.16)
+    def set_search_vdraws(self, on: bool) -> None:
+        """fnnue_set_search_vdraws: vsearch1 / vsearch1_lines / vsearch2 / vsearch2_lines mark the searched
+        positions drawn under their variant's rule (END_DRAW); a chess net's context ignores it."""
+        N.check(N.lib.fnnue_set_search_vdraws(self._h, 1 if on else 0))
+
+    def search_vdraws(self) -> bool:
+        on = C.c_int()
+        N.check(N.lib.fnnue_get_search_vdraws(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def game_vhistory(self, variant: int, games) -> tuple[np.ndarray, np.ndarray]:
+        """fnnue_ctx_game_vhistory: game_vhistory() computed on the device from the variant replay's boards
+        (any net's context serves)."""
+        return _game_history(N.lib.fnnue_ctx_game_vhistory, (self._h, variant), games)
 
     # capture quiescence below the search's leaves (ABI 3.13)
     def set_search_quiesce(self, depth: int) -> None:

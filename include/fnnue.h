@@ -818,7 +818,7 @@ int fnnue_vsearch2_lines(fnnue_ctx *ctx, int variant, const char *text, size_t t
  *
  * A drawn record carries FNNUE_END_DRAW in its end byte and ranks, in
  * fnnue_best_children, fnnue_topk_children, fnnue_best_replies and
- * fnnue_topk_replies (and the variants' forms, whose callers never set it),
+ * fnnue_topk_replies (and the variants' forms: ABI 3.16 sets it there),
  * exactly as a record whose end byte is FNNUE_END_NO_MOVES alone: worth 0, the
  * pv ends there, kind FNNUE_BEST_CP, its terms those of a one-move pv.
  * Checkmate (NO_MOVES with a deciding flag) and FNNUE_END_WON take precedence,
@@ -829,10 +829,9 @@ int fnnue_vsearch2_lines(fnnue_ctx *ctx, int variant, const char *text, size_t t
  * a child without a legal move).  End bytes without the bit give the results of
  * ABI 3.11 byte for byte.
  *
- * Out of scope: variant batches and the fnnue_vsearch* calls (crazyhouse
- * identities need the pockets, and Fairy-Stockfish's n-move rules differ per
- * variant: the shared key functions honour the bit, nothing sets it there);
- * move work; insufficient material; draw tests on the root. */
+ * Out of scope: move work; insufficient material; draw tests on the root.
+ * (Variant batches and the fnnue_vsearch* calls have their own rule and their
+ * own switch: ABI 3.16, below.) */
 #define FNNUE_END_DRAW 0x10
 /* One per ply: its clock and the number of earlier plies of the same game with
  * its identity (saturating at 255). */
@@ -1105,6 +1104,73 @@ int fnnue_vquiesce(fnnue_ctx *ctx, int variant, const char *text, size_t text_le
  * is that of ABI 3.14. */
 int fnnue_set_search_vquiesce(fnnue_ctx *ctx, int depth, int checks);
 int fnnue_get_search_vquiesce(const fnnue_ctx *ctx, int *depth, int *checks);
+
+/* ---- repetition and fifty-move draws in the variant searches (ABI 3.16) ----
+ * The rule of ABI 3.12 for crazyhouse, atomic, kingofthehill, racingkings and
+ * threecheck.  It is this project's own (no engine output pins it); everything
+ * not named here is ABI 3.12's text unchanged: P itself is never tested; the
+ * history of a searched position X is the game's plies 0..P plus the path's
+ * intermediate position; X is drawn when seen(X) >= 2, or when clock(X) >= 100
+ * and X is not decided; `nodes` is unchanged; a drawn child's depth-1 record
+ * holds the child's own terms; keys are filters, every mark is confirmed on the
+ * boards.
+ *  - Identity, all variants: chess's.  Placement, side to move, the castling
+ *    rooks as the rules keep them, and the en-passant square counted only when a
+ *    pawn of the side to move attacks it.
+ *  - Identity, crazyhouse: also both pockets and the promoted marks (two
+ *    positions that differ only in which queen turns into a pawn when captured
+ *    are different positions).
+ *  - Identity, threecheck: also both check counters (a placement that returns
+ *    after a check was given is a different position).
+ *  - Clock (atomic, kingofthehill, racingkings, threecheck): clock(i+1) is 0
+ *    when move i moves a pawn or removes a piece from the board (a capture; an
+ *    atomic explosion removes at least two), else clock(i) + 1, saturating at
+ *    65535.  Castling counts up, and so does a checking move in threecheck.
+ *    clock(0) is the FEN's fifth field by chess's rule; in threecheck it is the
+ *    first field from the fifth on that contains no '+' (so "... - 3+3 98 60",
+ *    whose fifth field holds the counters, has clock 98, and "... - 0 1 +0+0"
+ *    has clock 0).
+ *  - Crazyhouse has no clock rule: a captured piece comes back from the pocket,
+ *    so neither a capture nor a pawn move makes a position unreachable, and
+ *    lichess, whose games these are, does not apply the fifty-move rule there.
+ *    fnnue_ply_history.clock is 0 on every crazyhouse ply, nothing is drawn by a
+ *    clock, and the repetition history is the whole game: no window cuts it.
+ *  - "Not checkmate" becomes "not decided": a record is never marked when its
+ *    end byte has FNNUE_END_WON, or FNNUE_END_NO_MOVES together with the check,
+ *    exploded-king or FNNUE_END_VARIANT bit (a mate, an exploded king, a king on
+ *    the hill or on rank 8, a third check).  A racingkings draw and a stalemate
+ *    (NO_MOVES alone) may be marked; they are worth 0 either way.
+ *  - The window: in the four clocked variants equal identities cannot straddle
+ *    a clock-resetting move, so the walk stops there (an optimisation, as in
+ *    3.12; a threecheck counter change needs none, the identities differ).  In
+ *    crazyhouse the walk goes back to the root, and a ply is on the marking
+ *    list as soon as any ply of its game up to it has been seen before.
+ * Out of scope: move work, antichess and horde, insufficient material, draw
+ * tests on the root, draws inside the quiescence tree.
+ *
+ * The history calls follow fnnue_game_history's protocol and errors, with
+ * FNNUE_E_ARG for chess or an unknown variant.  fnnue_game_vhistory is host
+ * only (the host variant replay).  The other two replay on the device and need
+ * a context only for its device, stream and scratch: any net's context serves,
+ * a chess net's included, whatever variant is asked for. */
+int fnnue_game_vhistory(int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                        const uint32_t *moves_off, size_t ngames, fnnue_ply_history *out, size_t cap, uint32_t *off,
+                        size_t off_cap, size_t *n_out, size_t *n_groups);
+int fnnue_game_vhistory_device(fnnue_ctx *ctx, int variant, const char *d_text, const uint32_t *d_fen_off,
+                               const uint32_t *d_moves_off, size_t ngames, fnnue_ply_history *d_out, size_t cap,
+                               uint32_t *d_off, size_t off_cap, size_t *n_out, size_t *n_groups, void *stream);
+int fnnue_ctx_game_vhistory(fnnue_ctx *ctx, int variant, const char *text, size_t text_len, const uint32_t *fen_off,
+                            const uint32_t *moves_off, size_t ngames, fnnue_ply_history *out, size_t cap,
+                            uint32_t *off, size_t off_cap, size_t *n_out, size_t *n_groups);
+/* The switch (default off) for fnnue_vsearch1[_lines], fnnue_vsearch2[_children|
+ * _lines] and their _device forms, at the place fnnue_set_search_draws acts for
+ * chess: the marks are set behind the expansion and before the quiescence and
+ * the reductions, so a drawn leaf is not quiesced.  A chess net's context
+ * accepts the setting and ignores it, as a variant net's context keeps ignoring
+ * fnnue_set_search_draws.  FNNUE_DRAW_KEY_BITS applies.  With the setting off
+ * every byte of every result is that of ABI 3.15. */
+int fnnue_set_search_vdraws(fnnue_ctx *ctx, int on);
+int fnnue_get_search_vdraws(const fnnue_ctx *ctx, int *on);
 
 /* ---- diagnostics ----
  * Runs the int8 MFMA operand-layout self test on `device`; 0 if the hardware

@@ -416,7 +416,7 @@ int fnnue_backend_set_variant_analysis_plies(fnnue_backend *b, int plies);
  * best move answers as a stalemating one does: Score::Cp(0), depth = the pv's
  * length, "pv":"f6g8".  A piece holds whole games, so the history is complete.
  * The ply itself is never tested; nodes do not change.  Depth 0, move work and
- * variant batches are unchanged. */
+ * variant batches are unchanged (variant batches: ABI 3.16, below). */
 int fnnue_backend_set_draw_rules(fnnue_backend *b, int on);
 int fnnue_backend_draw_rules(fnnue_backend *b, int *on);
 
@@ -461,6 +461,19 @@ int fnnue_backend_quiesce_checks(fnnue_backend *b, int *on);
  * batches only. */
 int fnnue_backend_set_variant_quiesce(fnnue_backend *b, int depth, int checks);
 int fnnue_backend_variant_quiesce(fnnue_backend *b, int *depth, int *checks);
+
+/* ---- repetition and fifty-move draws for variant batches (ABI 3.16) ----
+ * fnnue_backend_set_variant_draw_rules(b, on) (default off): on, every variant
+ * analysis batch searched at 1 or 2 plies, through every go* call, marks the
+ * searched positions that are drawn under its variant's rule (fnnue.h, ABI
+ * 3.16: crazyhouse has repetition only, with pockets and promoted marks in the
+ * identity; threecheck's identity has the check counters), at the place
+ * fnnue_backend_set_draw_rules acts for chess batches and before the variant
+ * quiescence.  A drawn best move answers Score::Cp(0), depth 1, a one-move pv.
+ * Move work, depth-0 analysis and chess batches are unchanged, and
+ * fnnue_backend_set_draw_rules keeps applying to chess batches only. */
+int fnnue_backend_set_variant_draw_rules(fnnue_backend *b, int on);
+int fnnue_backend_variant_draw_rules(fnnue_backend *b, int *on);
 
 /* ---- MultiPV at two plies (ABI 3.11) ----
  * One line of a response with its whole pv, as the reference keeps one

@@ -29,8 +29,10 @@ lichess-shaped chess batches; with `--lines` also go_lines_pv() on the same
 random legal games of that variant instead (a synthetic variant net; the atomic
 net for kingofthehill, racingkings and threecheck), and with `--actor` the
 actor's go_pv() at 1 and 2 variant plies on batches of that variant;
-`--draws N` (chess) adds N interleaved rounds of search2 with the draw rules
-(fnnue_set_search_draws) off and on, in this process on the same games (phases
+`--draws N` adds N interleaved rounds of search2 with the draw rules
+(fnnue_set_search_draws; with `--variant` the variants': fnnue_set_search_vdraws; `--shuffle` makes every game
+of the variant a long knight shuffle, whose plies are nearly all on the rules' list) off and on, in this process
+on the same games (phases
 search2_draws_off / _on: median, min, max), and traced calls with the rules on,
 whose line carries history_ms, mark_ms and draw_list (the plies on the list).
 `--quiesce D` (chess, or with `--variant` the variants' quiescence: fnnue_set_search_vquiesce) adds interleaved rounds (`--runs` of them, at least 3) of search1 and search2 with the
@@ -76,6 +78,7 @@ def main():
     ap.add_argument("--piece-plies", default="")
     ap.add_argument("--lines", default="")
     ap.add_argument("--draws", type=int, default=0)
+    ap.add_argument("--shuffle", action="store_true")
     ap.add_argument("--quiesce", type=int, default=0)
     ap.add_argument("--quiesce-checks", action="store_true")
     a = ap.parse_args()
@@ -87,6 +90,9 @@ def main():
     if a.variant:
         root = VARIANTS[a.variant][1]
         games = [(root, F.random_vgame(a.seed * 1_000_003 + i, vid, root, a.plies)) for i in range(a.games)]
+        if a.shuffle:  # knights going out and back from the start: every ply after the 8th is on the draw rules' list
+            back = "e2g3 d2b3 g3e2 b3d2" if a.variant == "racingkings" else "g1f3 g8f6 f3g1 f6g8"
+            games = [(root, " ".join(back.split() * (a.plies // 4))) for _ in range(a.games)]
     else:
         games = [(START, F.random_game(a.seed * 1_000_003 + i, START, a.plies)) for i in range(a.games)]
     text, fen_off, mv_off = F.pack_games(games)
@@ -176,7 +182,7 @@ def main():
             (search2_lines(ks[0]) if ks else search2)()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
-    if a.draws and not a.variant:
+    if a.draws:
         draws_rounds(a, ev, stream, search2, base)
     if a.quiesce:
         quiesce_rounds(a, ev, stream, search1, search2, base)
@@ -202,24 +208,26 @@ def draws_rounds(a, ev, stream, search2, base):
         ev.check()
         return e0.elapsed_time(e1)
 
+    # a variant net's context has its own switch (fnnue_set_search_vdraws)
+    set_draws = ev.set_search_vdraws if a.variant else ev.set_search_draws
     ms = {False: [], True: []}
     for _ in range(a.draws):
         for on in (False, True):
-            ev.set_search_draws(on)
+            set_draws(on)
             ms[on].append(timed())
     for on in (False, True):
         v = sorted(ms[on])
         print(json.dumps(dict(base, phase="search2_draws_" + ("on" if on else "off"), rounds=a.draws,
                               ms=[round(x, 4) for x in v], median_ms=round(v[len(v) // 2], 4), min_ms=round(v[0], 4),
                               max_ms=round(v[-1], 4))), flush=True)
-    ev.set_search_draws(True)
+    set_draws(True)
     os.environ["FNNUE_SEARCH2_TRACE"] = "1"
     for _ in range(a.runs):
         with torch.cuda.stream(stream):
             search2()
         stream.synchronize()
     os.environ["FNNUE_SEARCH2_TRACE"] = "0"
-    ev.set_search_draws(False)
+    set_draws(False)
 
 
 def quiesce_rounds(a, ev, stream, search1, search2, base):
